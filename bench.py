@@ -15,6 +15,13 @@ N > 1 (torchrun): every rank runs an independent what-if replica of the workload
 (BASELINE.json configs[3] style: cluster replica × pod trace, seed ^ rank) on its own GPU;
 no data-path collective — weak scaling; value = all ranks' evals ÷ the slowest rank's time.
 
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the result line
+(metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step
+returned (DIR/binds_<field>.npy) and the per-node usage after it (DIR/usage.npy), float64: the
+same arguments give the same inputs, so two builds can be compared output for output.  Everything
+below — the profiled step's per-kernel breakdown and roofline, the usage queries, the drop-in,
+C3q, reference-literal, C4 and C5 legs, the CPU baseline — runs only with --full.
+
 Alongside (field "c5_sharded", every N): BASELINE.json configs[4] — one 1M-node cluster
 node-sharded across the N ranks (ks_shard: each rank scans its node range, one RCCL all-gather
 of the per-pod candidate lists per batch), total work fixed as N grows (strong scaling): the
@@ -289,6 +296,25 @@ def roofline_block(value, st, ks, nodes, config, stream_gbs=None):
     }
 
 
+def dump_outputs(out_dir, binds, usage):
+    """--dump-outputs: what the last timed step returned to its caller — the binds' fields (pod, node,
+    status, tick), one array each — and the per-node usage [N][3] the engine holds after it (ks_usage:
+    the sum of every step's placements), as float64 (every value is an integer far below 2^53, so
+    the conversion is exact).  About 2 MB at the default sizes; an array of more than 2^20 rows
+    is cut to a fixed, seeded sample of 2^20 (the same rows every run): under 64 MB in all."""
+    import numpy as np
+
+    def rows(a, cap=1 << 20):
+        if len(a) <= cap:
+            return a
+        return a[np.sort(np.random.default_rng(0x5EED).choice(len(a), cap, replace=False))]
+
+    os.makedirs(out_dir, exist_ok=True)
+    for f in binds.dtype.names:
+        np.save(os.path.join(out_dir, f"binds_{f}.npy"), rows(binds[f]).astype(np.float64))
+    np.save(os.path.join(out_dir, "usage.npy"), rows(usage).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -298,6 +324,12 @@ def main():
     ap.add_argument("--nodes", type=int, default=50_000)
     ap.add_argument("--pods", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=0, help="pods per scan/resolve batch (0 = engine default: 192 on the chunk resolver)")
+    ap.add_argument("--full", action="store_true",
+                    help="c3: after the timed steps also run the profiled step (per-kernel breakdown, roofline), "
+                         "the usage queries, the drop-in / C3q / reference-literal / C4 / C5 legs and the CPU "
+                         "baseline (the legs and the baseline each have a --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's binds and the node usage after it as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-sample-pods", type=int, default=40000)
     ap.add_argument("--cpu-budget-s", type=float, default=12.0, help="per CPU-baseline leg (multi-core, single-thread)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -321,6 +353,8 @@ def main():
     ap.add_argument("--c5-timeout", type=float, default=240.0,
                     help="c3: seconds the C5 leg may take before it is abandoned (the C3 line still prints)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "c3":
+        ap.error("--dump-outputs writes the C3 headline's outputs (--config c3)")
     if args.config == "c4":
         return main_c4(args)
     if args.config == "c5":
@@ -351,9 +385,11 @@ def main():
     log(f"[rank {rank}] trace {args.nodes} nodes x {n_pods} pods ready in {time.perf_counter() - t0:.1f}s")
 
     S = args.pods_per_step
-    kept = []  # every step's binds (the usage kernel's algorithmic bytes need the placements)
+    kept = []  # --full: every step's binds (the usage kernel's algorithmic bytes need the placements)
     for _ in range(args.warmup):
-        kept.append(eng.step(S))
+        b = eng.step(S)
+        if args.full:
+            kept.append(b)
 
     def barrier():
         # ks_step synchronises the engine's stream before returning; the extra device-wide
@@ -370,10 +406,12 @@ def main():
     barrier()
     t_start = time.perf_counter()
     binds = 0
+    b = None
     for _ in range(args.steps):
         b = eng.step(S)   # ks_step returns after its last kernel has completed
         binds += len(b)
-        kept.append(b)
+        if args.full:
+            kept.append(b)
     t_el = time.perf_counter() - t_start
     barrier()
     if dist is not None:
@@ -387,48 +425,53 @@ def main():
     else:
         total_binds = binds
 
-    # per-kernel breakdown on one more (profiled) step: HIP events on the engine's stream
-    eng.set_profiling(True)
-    kept.append(eng.step(S))
-    st = eng.last_step_stats()
-    kst = eng.last_step_kernels()
-    eng.set_profiling(False)
-    # per-tick node usage: ks_usage_at = zero + usage kernel over the pod
-    # blocks that may run at t (run-interval index) + the [N][3] copy; the digest covers every
-    # tick of the last step's window
-    t_now = eng.tick
-    eng.usage_at(t_now)
-    t_u = time.perf_counter()
-    q_ticks = [max(0, t_now - 1000 * k) for k in range(10)]
-    for t_q in q_ticks:
-        eng.usage_at(t_q)
-    usage_ms = (time.perf_counter() - t_u) * 100.0
-    # the usage kernel's roofline: the same ten queries with HIP events around the kernel alone
-    eng.set_profiling(True)
-    for t_q in q_ticks:
-        eng.usage_at(t_q)
-    ku = eng.last_step_kernels()
-    eng.set_profiling(False)
-    usage_roof = usage_roofline(trace, kept, q_ticks, ku)
-    t_u = time.perf_counter()
-    eng.usage_digest(max(0, t_now - S + 1), t_now + 1)
-    digest_ms = (time.perf_counter() - t_u) * 1e3
+    if rank == 0 and args.dump_outputs and b is not None:
+        dump_outputs(args.dump_outputs, b, eng.usage())
+    st = kst = usage_roof = dropin = c3q = c3lit = c4 = None
+    if args.full:
+        # per-kernel breakdown on one more (profiled) step: HIP events on the engine's stream
+        eng.set_profiling(True)
+        kept.append(eng.step(S))
+        st = eng.last_step_stats()
+        kst = eng.last_step_kernels()
+        eng.set_profiling(False)
+        # per-tick node usage: ks_usage_at = zero + usage kernel over the pod
+        # blocks that may run at t (run-interval index) + the [N][3] copy; the digest covers every
+        # tick of the last step's window
+        t_now = eng.tick
+        eng.usage_at(t_now)
+        t_u = time.perf_counter()
+        q_ticks = [max(0, t_now - 1000 * k) for k in range(10)]
+        for t_q in q_ticks:
+            eng.usage_at(t_q)
+        usage_ms = (time.perf_counter() - t_u) * 100.0
+        # the usage kernel's roofline: the same ten queries with HIP events around the kernel alone
+        eng.set_profiling(True)
+        for t_q in q_ticks:
+            eng.usage_at(t_q)
+        ku = eng.last_step_kernels()
+        eng.set_profiling(False)
+        usage_roof = usage_roofline(trace, kept, q_ticks, ku)
+        t_u = time.perf_counter()
+        eng.usage_digest(max(0, t_now - S + 1), t_now + 1)
+        digest_ms = (time.perf_counter() - t_u) * 1e3
     eng.close()
-    dropin = dropin_leg(trace, enc, scorers, local) if rank == 0 and not args.no_dropin else None
-    c3q = c3q_leg(args, scorers, local) if rank == 0 and not args.no_c3q else None
-    c3lit = c3_literal_leg(args, trace, enc, scorers, local) if rank == 0 and not args.no_c3_literal else None
-    # C4 (BASELINE configs[3]) on every rank: disjoint scenario ranges, weak scaling
-    c4 = None
-    if not args.no_c4:
-        try:
-            c4 = c4_leg(args, rank, world, local, dist)
-        except Exception as ex:  # never fatal to the headline line on one rank
-            if world > 1:
-                # (a rank that skipped the leg's collectives would pair the C5 leg's
-                # collectives with the other ranks' C4 ones — fail the run cleanly instead)
-                raise
-            log(f"[rank {rank}] C4 leg failed: {ex!r}")
-            c4 = {"error": repr(ex)[:500]}
+    if args.full:
+        dropin = dropin_leg(trace, enc, scorers, local) if rank == 0 and not args.no_dropin else None
+        c3q = c3q_leg(args, scorers, local) if rank == 0 and not args.no_c3q else None
+        c3lit = c3_literal_leg(args, trace, enc, scorers, local) if rank == 0 and not args.no_c3_literal else None
+        # C4 (BASELINE configs[3]) on every rank: disjoint scenario ranges, weak scaling
+        c4 = None
+        if not args.no_c4:
+            try:
+                c4 = c4_leg(args, rank, world, local, dist)
+            except Exception as ex:  # never fatal to the headline line on one rank
+                if world > 1:
+                    # (a rank that skipped the leg's collectives would pair the C5 leg's
+                    # collectives with the other ranks' C4 ones — fail the run cleanly instead)
+                    raise
+                log(f"[rank {rank}] C4 leg failed: {ex!r}")
+                c4 = {"error": repr(ex)[:500]}
     line = None
 
     if rank == 0:
@@ -436,14 +479,6 @@ def main():
         evals = total_binds * nodes
         value = evals / t_el
         pods_per_s = total_binds / t_el
-        launches = max(st["launches"], 1)
-        pods_per_launch = st["pods"] / launches
-        scan_avg_ms = st["scan_ms"] / launches
-        res_avg_ms = st["resolve_ms"] / launches
-        other_avg_ms = st["other_ms"] / launches
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure
-            cpu = cpu_baseline(trace, scorers, args.cpu_sample_pods, args.cpu_budget_s)
         line = {
             "metric": "pod-node Filter+Score evals/sec and pods bound/sec at 50k nodes, 1-8 GPUs",
             "value": value,
@@ -463,24 +498,37 @@ def main():
                        "parallelism": "replicas" if world > 1 else "single-gpu",
                        "batch_pods": args.batch or 192},
             "pods_per_s": pods_per_s,
-            "roofline": roofline_block(value, st, kst, nodes, "c3", stream_copy_gbs(local)),
-            "kernels": {"launches_per_step": launches, "pods_per_launch": pods_per_launch,
-                        "scan_avg_ms": scan_avg_ms, "resolve_avg_ms": res_avg_ms,
-                        "other_avg_ms": other_avg_ms,
-                        "profiled_step_ms": st["step_ms"], "per_kernel": kst},
-            "usage_query": {"ms_per_call": usage_ms, "nodes": nodes, "tick": t_now,
-                            "digest_ms": digest_ms, "digest_ticks": S, "roofline": usage_roof,
-                            "note": "ks_usage_at wall time at ticks near the end of the run, incl. the "
-                                    "24 B/node copy to the host; digest = every tick of the last step's window"},
-            "dropin": dropin,
-            "c3q": c3q,
-            "c3_literal": c3lit,
-            "c4": c4,
-            "c5_sharded": None,
-            "cpu_baseline": cpu,
             "host": {"cpu": platform.processor() or platform.machine(), "nproc": os.cpu_count()},
         }
-    if not args.no_c5:
+        if args.full:
+            launches = max(st["launches"], 1)
+            pods_per_launch = st["pods"] / launches
+            scan_avg_ms = st["scan_ms"] / launches
+            res_avg_ms = st["resolve_ms"] / launches
+            other_avg_ms = st["other_ms"] / launches
+            cpu = None
+            if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure
+                cpu = cpu_baseline(trace, scorers, args.cpu_sample_pods, args.cpu_budget_s)
+            host = line.pop("host")  # stays the line's last key
+            line.update({
+                "roofline": roofline_block(value, st, kst, nodes, "c3", stream_copy_gbs(local)),
+                "kernels": {"launches_per_step": launches, "pods_per_launch": pods_per_launch,
+                            "scan_avg_ms": scan_avg_ms, "resolve_avg_ms": res_avg_ms,
+                            "other_avg_ms": other_avg_ms,
+                            "profiled_step_ms": st["step_ms"], "per_kernel": kst},
+                "usage_query": {"ms_per_call": usage_ms, "nodes": nodes, "tick": t_now,
+                                "digest_ms": digest_ms, "digest_ticks": S, "roofline": usage_roof,
+                                "note": "ks_usage_at wall time at ticks near the end of the run, incl. the "
+                                        "24 B/node copy to the host; digest = every tick of the last step's window"},
+                "dropin": dropin,
+                "c3q": c3q,
+                "c3_literal": c3lit,
+                "c4": c4,
+                "c5_sharded": None,
+                "cpu_baseline": cpu,
+                "host": host,
+            })
+    if args.full and not args.no_c5:
         c5 = c5_leg(args, rank, world, local, dist, line=line)
         if rank == 0:
             line["c5_sharded"] = c5

@@ -1,6 +1,6 @@
 """Dev tool (not a test): bench.py on an A/B engine build in build/diag/ (tests/dev/devlib.py) —
 e.g. a build of an earlier commit's sources, saved before a change:
-    python tests/dev/bench_with_lib.py libks_engine_base.so --no-c4 --no-c5 ...
+    python tests/dev/bench_with_lib.py libks_engine_base.so --full --no-c4 --no-c5 ...
 The provenance check is skipped (the build is of other sources by design)."""
 import os
 import runpy
