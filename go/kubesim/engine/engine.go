@@ -315,6 +315,56 @@ func (e *Engine) UsageAt(t int64) ([]int64, error) {
 	return u[:3*e.n], status(e, C.ks_usage_at(e.h, C.int64_t(t), i64p(u)))
 }
 
+// SeriesCols is KS_SERIES_COLS: the columns of ClusterSeries per tick (running pods, Σ requested
+// cpu / memory / gpu milli, pods bound Ok so far, bound OverCapacity so far, pending pods).
+const SeriesCols = 7
+
+// RequestedAt is Node.totalResourceRequest and runningPodsNum (kubesim/node/node.go:97-118) of
+// every node at tick t <= Tick(): 4 per loaded node (requested cpu, memory, gpu milli; running
+// pods), ks_requested_at.
+func (e *Engine) RequestedAt(t int64) ([]int64, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	r := make([]int64, 4*e.n+1)
+	return r[:4*e.n], status(e, C.ks_requested_at(e.h, C.int64_t(t), i64p(r)))
+}
+
+// FilterMaskAt is FilterMask as it was when the already-bound pod `pod` was scheduled
+// (ks_filter_at; the filtered node list scheduleOne logs, kubesim/kubesim.go:170,184).
+func (e *Engine) FilterMaskAt(pod int64) ([]uint8, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	mask := make([]uint8, e.n+1)
+	return mask[:e.n], status(e, C.ks_filter_at(e.h, C.int64_t(pod), u8p(mask)))
+}
+
+// ScoresAt is Scores as it was when the already-bound pod `pod` was scheduled (ks_score_at; the
+// nodeScore map scheduleOne logs, kubesim/kubesim.go:194,205): its lowest-index maximum is the
+// node the pod was bound to.
+func (e *Engine) ScoresAt(pod int64) ([]int64, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	s := make([]int64, e.n+1)
+	return s[:e.n], status(e, C.ks_score_at(e.h, C.int64_t(pod), i64p(s)))
+}
+
+// ClusterSeries is the cluster-wide curves for ticks tLo <= t < tHi (tHi-1 <= Tick(), at most
+// 2^20 ticks): SeriesCols values per tick (ks_cluster_series).
+func (e *Engine) ClusterSeries(tLo, tHi int64) ([]int64, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	n := 0
+	if tHi > tLo && tHi-tLo <= 1<<20 { // (a longer window is rejected by the call: nothing to hold)
+		n = int(tHi-tLo) * SeriesCols
+	}
+	s := make([]int64, n+1)
+	return s[:n], status(e, C.ks_cluster_series(e.h, C.int64_t(tLo), C.int64_t(tHi), i64p(s)))
+}
+
+// NodePeaks is, per node and column, the maximum of RequestedAt(t) over tLo <= t < tHi (4 per
+// loaded node, ks_node_peaks): how full each node got.
+func (e *Engine) NodePeaks(tLo, tHi int64) ([]int64, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	r := make([]int64, 4*e.n+1)
+	return r[:4*e.n], status(e, C.ks_node_peaks(e.h, C.int64_t(tLo), C.int64_t(tHi), i64p(r)))
+}
+
 // Nodes is the node count of LoadNodes.
 func (e *Engine) Nodes() int { return e.n }
 

@@ -21,6 +21,10 @@
  *                                 (api/scheduler.go:36, kubesim/kubesim.go:193-206)
  *   ks_usage / ks_usage_at ...... Σ Pod.ResourceUsage(clock) per node (kubesim/pod/pod.go:47-63)
  *   ks_usage_digest ............. the same for every tick of a window, as a fingerprint
+ *   ks_requested_at / ks_node_peaks  Node.totalResourceRequest / runningPodsNum (kubesim/node/node.go:97-118)
+ *   ks_filter_at / ks_score_at .. the filtered nodes and nodeScore map scheduleOne logs per pod
+ *                                 (kubesim/kubesim.go:170,184,194,205), for a pod already bound
+ *   ks_cluster_series ........... running / requested / bound / failed / queued curves per tick
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
  *   ks_pod_lookup / ks_node_pods  Node.GetPod / GetPodStatus / GetPodList (kubesim/node/node.go:62-93)
  *   ks_group_* .................. one KubeSim.Run per what-if scenario, stepped together
@@ -231,6 +235,44 @@ ks_status ks_usage_digest(ks_engine* eng, int64_t t_lo, int64_t t_hi, uint64_t* 
 /* the digest's node weight: z = (node + 1) * 0x9E3779B97F4A7C15, then the splitmix64 finaliser
  * (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31) */
 uint64_t ks_node_mix(int64_t node);
+
+/* Scheduler state at past ticks, rebuilt from the binds (final once made).  "At tick t" is sampled
+ * after tick t's bind, as ks_usage_at; 0 <= t <= the current tick.  A pod counts on its node while
+ * it was bound Ok and 0 <= t - bind tick < its run length in ticks (Pod.IsRunning,
+ * kubesim/pod/pod.go:67-69, int32 arithmetic included); OverCapacity pods never count.  Quantities
+ * are int64 milli-units.  All of them answer after an aborted run (KS_ENOTFOUND / KS_EINVAL) on the
+ * binds made before it, on sharded engines and on scenario-group members.  Cost: the pods that
+ * run in, or are bound in, the queried ticks (the usage queries' run-interval index), not the
+ * run's length.
+ *
+ * ks_requested_at: out[n][4] = per node {Σ requested cpu, memory, nvidia.com/gpu, running pods}
+ * over the pods running at t — Node.totalResourceRequest and runningPodsNum
+ * (kubesim/node/node.go:97-118), the state CreatePod's admission test reads (node.go:44-47). */
+ks_status ks_requested_at(ks_engine* eng, int64_t t, int64_t* out);
+/* ks_filter_at / ks_score_at: what ks_filter / ks_score would have returned for the already-bound
+ * pod `pod` at the moment scheduleOne handled it — the filtered node list and the nodeScore map the
+ * reference logs per pod (kubesim/kubesim.go:170,184,194,205): node state = the pods before it in
+ * the FIFO that run at its bind tick, with the cluster's alloc / taints / labels.  The lowest-index
+ * argmax of score_out is the node the pod was bound to (kubesim.go:208-222).  KS_EINVAL for a pod
+ * that is not bound: queued (use ks_filter / ks_score), out of range, or the pod an aborted run
+ * stopped at.  mask_out[n], score_out[n] (-1 = no entry). */
+ks_status ks_filter_at(ks_engine* eng, int64_t pod, uint8_t* mask_out);
+ks_status ks_score_at(ks_engine* eng, int64_t pod, int64_t* score_out);
+/* ks_cluster_series: cluster-wide curves for ticks t_lo <= t < t_hi (t_hi - 1 <= the current tick,
+ * t_hi - t_lo <= 2^20): out[(t - t_lo) * KS_SERIES_COLS + c], c = 0 running pods; 1..3 Σ over nodes
+ * of requested cpu / memory / gpu (Σ_n ks_requested_at(t)); 4 pods bound Ok so far; 5 pods bound
+ * OverCapacity so far (PodFailed, kubesim/pod/pod.go:20-27); 6 pending = pods arrived by t minus
+ * pods taken off the queue by t (len(podQueue) after tick t's scheduleOne, kubesim/podqueue.go:18-42;
+ * the pod an aborted run stopped at was popped, kubesim/kubesim.go:144-158).  Arrival = the tick the
+ * bind-tick recurrence used: an arrival_tick at or before the tick of its ks_submit_pods call counts
+ * as the next tick. */
+#define KS_SERIES_COLS 7
+ks_status ks_cluster_series(ks_engine* eng, int64_t t_lo, int64_t t_hi, int64_t* out);
+/* ks_node_peaks: out[n][4] = per node and column the maximum of ks_requested_at(t) over
+ * t_lo <= t < t_hi (window bounds as ks_cluster_series) — how full each node got; what a sweep of
+ * Node.totalResourceRequest / runningPodsNum (kubesim/node/node.go:97-118) over every tick of the
+ * window would find.  Extra cost: per node, the square of its pods that run in the window. */
+ks_status ks_node_peaks(ks_engine* eng, int64_t t_lo, int64_t t_hi, int64_t* out);
 
 /* Name-keyed queries over the binds made so far (Node.GetPod / GetPodStatus / GetPodList,
  * kubesim/node/node.go:62-93).  ks_pod_lookup: the FIFO index of the pod stored on `node` under

@@ -952,4 +952,26 @@ hipError_t launch_usage_digest(const int32_t* blocks, int64_t nblocks, int64_t q
                                const int32_t* cum_sec, const int64_t* use, unsigned long long* diff,
                                unsigned long long* out, hipStream_t st);
 
+// past-tick state queries (ks_query.hip), over the same candidate blocks
+struct QScale { int64_t f[3]; };  // milli-units per device unit of cpu / memory / gpu (1: device units)
+constexpr int kSeriesCols = 7;
+struct SeriesInit { int64_t v[kSeriesCols]; };  // the columns' values before the window's first tick
+// word k of node nd at out[nd * node_stride + k * col_stride] (zeroed): Σ req[0..2] * sc.f, running pods
+hipError_t launch_requested(const int32_t* blocks, int64_t nblocks, int64_t q_hi, int64_t t, int32_t n_nodes,
+                            const int32_t* b_node, const int32_t* b_status, const int64_t* t0, const int32_t* dur,
+                            const PodRec* pods, const QScale& sc, int64_t node_stride, int64_t col_stride,
+                            unsigned long long* out, hipStream_t st);
+// diff: [kSeriesCols][t_hi - t_lo + 1] zeroed; out: [t_hi - t_lo][kSeriesCols]; pods [q_lo, q_hi) left the
+// queue at ticks inside (t_lo, t_hi); arr[n_arr]: the arrival ticks inside (t_lo, t_hi)
+hipError_t launch_series(const int32_t* blocks, int64_t nblocks, int64_t q_lo, int64_t q_hi, int64_t t_lo,
+                         int64_t t_hi, const int32_t* b_status, const int64_t* t0, const int32_t* dur,
+                         const PodRec* pods, const QScale& sc, const int64_t* arr, int64_t n_arr,
+                         const SeriesInit& init, unsigned long long* diff, unsigned long long* out, hipStream_t st);
+// cnt[n_nodes] zeroed, off[n_nodes + 1], cur[n_nodes], list[list_cap >= nblocks * usage_block_pods()];
+// out: [n_nodes][4]
+hipError_t launch_node_peaks(const int32_t* blocks, int64_t nblocks, int64_t q_hi, int64_t t_lo, int32_t n_nodes,
+                             const int32_t* b_node, const int32_t* b_status, const int64_t* t0, const int32_t* dur,
+                             const PodRec* pods, const QScale& sc, int32_t* cnt, int32_t* off, int32_t* cur,
+                             int32_t* list, int32_t list_cap, long long* out, hipStream_t st);
+
 }  // namespace ks

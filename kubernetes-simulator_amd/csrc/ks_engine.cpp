@@ -253,6 +253,14 @@ struct ks_engine {
     DVec<int32_t> d_blk;                  // usage query: candidate pod blocks
     std::vector<int32_t> h_blk;
     DVec<unsigned long long> d_digest;    // [6][T + 1] difference arrays, then the prefix sums
+    // past-tick state queries (ks_requested_at ... ks_node_peaks): the arrival tick the bind-tick
+    // recurrence used per pod (non-decreasing), prefix counts of Ok / OverCapacity binds over the
+    // pods [0, cum_upto) (extended on each query), 64-bit and 32-bit device scratch
+    std::vector<int64_t> h_arr;
+    std::vector<int64_t> cum_ok{0}, cum_over{0};
+    int64_t cum_upto = 0;
+    DVec<unsigned long long> d_qs;
+    DVec<int32_t> d_qi;
 };
 
 namespace {
@@ -547,6 +555,7 @@ void engine_free(ks_engine* e) {
     e->phase_off.release(); e->cum_sec.release(); e->exp_pod.release(); e->exp_off.release();
     e->t0.release(); e->fin.release(); e->use.release(); e->expired.release(); e->exp_pos.release();
     e->preg.release(); e->d_blk.release(); e->d_digest.release(); e->srec.release();
+    e->d_qs.release(); e->d_qi.release();
     if (e->node_mem) (void)hipFree(e->node_mem);
     if (e->lists) (void)hipFree(e->lists);
     if (e->cand) (void)hipFree(e->cand);
@@ -853,6 +862,7 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
     std::vector<int64_t> t0(m), fin(m), eoff(m);
     std::vector<int32_t> tsec(m);
     std::vector<int64_t> run_end(m);
+    std::vector<int64_t> arr_eff(m);  // the arrival the recurrence uses (ks_cluster_series' pending column)
     std::vector<uint8_t> reg(m);
     std::vector<int32_t> epod;
     epod.reserve(m);
@@ -873,6 +883,7 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
         const int64_t arr = std::max<int64_t>(arrival[i], e->tick + 1);
         const int64_t bt = std::max<int64_t>(prev_bind + 1, arr);
         prev_bind = bt;
+        arr_eff[i] = arr;
         uint32_t acc = 0;  // int32 wrapping, kubesim/pod/pod.go:155-162
         int64_t acc64 = 0;
         bool nonneg = true;
@@ -977,6 +988,7 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
     e->h_status.resize(e->P + m, -1);
     // run-interval index (usage queries)
     e->h_end.insert(e->h_end.end(), run_end.begin(), run_end.end());
+    e->h_arr.insert(e->h_arr.end(), arr_eff.begin(), arr_eff.end());
     for (int64_t q = e->P; q < e->P + m; q++) {
         const int64_t b = q / kUBlk, s = b / kUSup;
         if ((int64_t)e->blk_end.size() <= b) e->blk_end.push_back(std::numeric_limits<int64_t>::min());
@@ -1955,6 +1967,163 @@ ks_status ks_usage_digest(ks_engine* e, int64_t t_lo, int64_t t_hi, uint64_t* ou
                                       e->t0.p, e->dur.p, e->preg.p, e->phase_off.p, e->cum_sec.p, e->use.p, diff, res,
                                       e->st));
     HIPCHK(e, hipMemcpyAsync(out, res, sizeof(uint64_t) * 6 * T, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// ---- past-tick state queries (ks_query.hip) ----------------------------------------------------
+// The node table's rc rm rg nr at any past tick, rebuilt from the binds: the pods q < q_hi that
+// were bound Ok and run at t.  They share the usage queries' run-interval index, read only the
+// bind arrays and the pod records, and leave the live table and the expiry state alone — so they
+// answer after an aborted run too (on the binds made before it).
+
+// upload the candidate blocks usage_blocks() left in h_blk
+static ks_status upload_blocks(ks_engine* e, int64_t nb) {
+    if (!nb) return KS_OK;
+    HIPCHK(e, e->d_blk.reserve(nb, e->st));
+    HIPCHK(e, hipMemcpyAsync(e->d_blk.p, e->h_blk.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, e->st));
+    return KS_OK;
+}
+
+static ks::QScale milli_scale(const ks_engine* e) { return ks::QScale{{e->scale[0], e->scale[1], e->scale[2]}}; }
+
+static ks_status check_window(ks_engine* e, const char* what, int64_t t_lo, int64_t t_hi) {
+    if (t_lo < 0 || t_hi <= t_lo || t_hi - 1 > e->tick || t_hi - t_lo > kMaxDigestTicks)
+        return fail(e, KS_EINVAL, "%s window [%lld, %lld) outside [0, %lld] or longer than %lld ticks", what,
+                    (long long)t_lo, (long long)t_hi, (long long)e->tick + 1, (long long)kMaxDigestTicks);
+    return KS_OK;
+}
+
+ks_status ks_requested_at(ks_engine* e, int64_t t, int64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
+    if (e->n == 0) return KS_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t q_hi = bound_by(e, t);
+    const int64_t nb = usage_blocks(e, t, q_hi);
+    HIPCHK(e, e->d_qs.reserve(4 * e->n, e->st));
+    HIPCHK(e, hipMemsetAsync(e->d_qs.p, 0, sizeof(unsigned long long) * 4 * e->n, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)e->n, e->b_node.p, e->b_status.p, e->t0.p,
+                                   e->dur.p, e->pods.p, milli_scale(e), 4, 1, e->d_qs.p, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, e->d_qs.p, sizeof(int64_t) * 4 * e->n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// Filter mask and score of an already-bound pod as scheduleOne saw them: the evaluator of
+// ks_filter / ks_score on a copy of the node table whose rc rm rg nr are the state rebuilt from the
+// pods q < pod running at the pod's bind tick (every one of them was bound at an earlier tick).
+static ks_status eval_pod_at(ks_engine* e, int64_t pod) {
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (pod < 0 || pod >= e->done || e->h_node[pod] < 0)
+        return fail(e, KS_EINVAL, "pod %lld is not bound (queued pods: ks_filter / ks_score)", (long long)pod);
+    if (e->n == 0) return KS_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t t = e->h_bind_tick[pod];
+    const int64_t nb = usage_blocks(e, t, pod);
+    const int64_t np = e->n_pad;
+    HIPCHK(e, e->d_qs.reserve(4 * np, e->st));
+    HIPCHK(e, hipMemsetAsync(e->d_qs.p, 0, sizeof(unsigned long long) * 4 * np, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, pod, t, (int32_t)e->n, e->b_node.p, e->b_status.p, e->t0.p,
+                                   e->dur.p, e->pods.p, ks::QScale{{1, 1, 1}}, 1, np, e->d_qs.p, e->st));
+    ks::NodeSoA s = e->s;
+    int64_t* b = (int64_t*)e->d_qs.p;
+    s.rc = b; s.rm = b + np; s.rg = b + 2 * np; s.nr = b + 3 * np;
+    HIPCHK(e, ks::launch_eval_pod(e->dc, s, e->pods.p + pod, e->cfg.filters, e->d_mask, e->d_score, e->mode, e->st));
+    return KS_OK;
+}
+
+ks_status ks_filter_at(ks_engine* e, int64_t pod, uint8_t* mask_out) {
+    if (!e || !mask_out) return KS_EINVAL;
+    ks_status r = eval_pod_at(e, pod);
+    if (r != KS_OK) return r;
+    if (e->n) HIPCHK(e, hipMemcpyAsync(mask_out, e->d_mask, e->n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+ks_status ks_score_at(ks_engine* e, int64_t pod, int64_t* score_out) {
+    if (!e || !score_out) return KS_EINVAL;
+    ks_status r = eval_pod_at(e, pod);
+    if (r != KS_OK) return r;
+    if (e->n)
+        HIPCHK(e, hipMemcpyAsync(score_out, e->d_score, sizeof(int64_t) * e->n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// prefix counts of the Ok / OverCapacity binds, extended over the pods [cum_upto, done)
+static void count_binds(ks_engine* e) {
+    for (int64_t q = e->cum_upto; q < e->done; q++) {
+        e->cum_ok.push_back(e->cum_ok.back() + (e->h_status[q] == KS_POD_OK && e->h_node[q] >= 0));
+        e->cum_over.push_back(e->cum_over.back() + (e->h_status[q] == KS_POD_OVER_CAPACITY && e->h_node[q] >= 0));
+    }
+    e->cum_upto = e->done;
+}
+
+static_assert(KS_SERIES_COLS == ks::kSeriesCols, "ks_cluster_series columns");
+
+ks_status ks_cluster_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_window(e, "series", t_lo, t_hi); r != KS_OK) return r;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t T = t_hi - t_lo;
+    // pods off the queue by t_lo / by the window's last tick; arrivals likewise (both FIFO prefixes)
+    const int64_t q_lo = bound_by(e, t_lo), q_hi = bound_by(e, t_hi - 1);
+    const int64_t a_lo = std::upper_bound(e->h_arr.begin(), e->h_arr.end(), t_lo) - e->h_arr.begin();
+    const int64_t a_hi = std::upper_bound(e->h_arr.begin(), e->h_arr.end(), t_hi - 1) - e->h_arr.begin();
+    const int64_t nb = usage_blocks(e, t_lo, q_hi);
+    count_binds(e);
+    ks::SeriesInit init{};
+    init.v[4] = e->cum_ok[q_lo];
+    init.v[5] = e->cum_over[q_lo];
+    init.v[6] = a_lo - q_lo;
+    const int64_t C = ks::kSeriesCols, n_arr = a_hi - a_lo;
+    HIPCHK(e, e->d_qs.reserve(C * (T + 1) + C * T + n_arr, e->st));
+    unsigned long long* diff = e->d_qs.p;
+    unsigned long long* res = diff + C * (T + 1);
+    int64_t* arr = (int64_t*)(res + C * T);
+    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * C * (T + 1), e->st));
+    if (n_arr)
+        HIPCHK(e, hipMemcpyAsync(arr, e->h_arr.data() + a_lo, sizeof(int64_t) * n_arr, hipMemcpyHostToDevice, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_series(e->d_blk.p, nb, q_lo, q_hi, t_lo, t_hi, e->b_status.p, e->t0.p, e->dur.p, e->pods.p,
+                                milli_scale(e), arr, n_arr, init, diff, res, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C * T, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+ks_status ks_node_peaks(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_window(e, "peaks", t_lo, t_hi); r != KS_OK) return r;
+    if (e->n == 0) return KS_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t q_hi = bound_by(e, t_hi - 1);
+    const int64_t nb = usage_blocks(e, t_lo, q_hi);
+    const int64_t n = e->n, cap = nb * kUBlk;
+    if (cap > INT32_MAX) return fail(e, KS_EINVAL, "peaks window holds too many candidate pods");
+    HIPCHK(e, e->d_qs.reserve(4 * n, e->st));
+    HIPCHK(e, e->d_qi.reserve(3 * n + 1 + cap, e->st));
+    int32_t* off = e->d_qi.p;        // [n + 1]
+    int32_t* cur = off + n + 1;      // [n]
+    int32_t* cnt = cur + n;          // [n]
+    int32_t* list = cnt + n;         // [cap]
+    HIPCHK(e, hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_node_peaks(e->d_blk.p, nb, q_hi, t_lo, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p,
+                                    e->dur.p, e->pods.p, milli_scale(e), cnt, off, cur, list, (int32_t)cap,
+                                    (long long*)e->d_qs.p, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, e->d_qs.p, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
     return KS_OK;
 }

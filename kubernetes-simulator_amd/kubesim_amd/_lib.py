@@ -27,6 +27,7 @@ KS_ENGINE_CHUNK_RESOLVER = 64
 KS_ENGINE_NO_OVERLAP = 256
 KS_ENGINE_PRUNED_LISTS = 512
 KS_SELFTEST_LR_MICRO = 0
+KS_SERIES_COLS = 7  # ks_cluster_series: running, requested cpu / memory / gpu, bound Ok, bound OverCapacity, pending
 
 STATUS_NAMES = {KS_OK: "OK", KS_EINVAL: "InvalidArgument", KS_ENOTFOUND: "NotFound",
                 KS_EDEVICE: "DeviceError", KS_ENOMEM: "OutOfMemory", KS_ERANGE: "OutOfDomain"}
@@ -39,6 +40,7 @@ EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods"
                     "ks_group_add", "ks_group_size", "ks_group_step", "ks_pod_status",
                     "ks_usage_at", "ks_usage_digest", "ks_node_mix", "ks_pod_lookup", "ks_node_pods",
                     "ks_shard_layout", "ks_merge_candidates",
+                    "ks_requested_at", "ks_filter_at", "ks_score_at", "ks_cluster_series", "ks_node_peaks",
                     # include/ks_ingest.h
                     "ks_parse_quantity", "ks_parse_simspec", "ks_cluster_parse", "ks_cluster_free",
                     "ks_cluster_nodes", "ks_cluster_tick", "ks_cluster_start_clock", "ks_cluster_arrays",
@@ -190,8 +192,14 @@ def load():
     L.ks_shard_layout.restype = C.c_int
     L.ks_merge_candidates.argtypes = [p, C.c_int32, C.c_int32, p]
     L.ks_merge_candidates.restype = C.c_int
+    L.ks_requested_at.argtypes = [p, C.c_int64, p]
+    L.ks_filter_at.argtypes = [p, C.c_int64, p]
+    L.ks_score_at.argtypes = [p, C.c_int64, p]
+    L.ks_cluster_series.argtypes = [p, C.c_int64, C.c_int64, p]
+    L.ks_node_peaks.argtypes = [p, C.c_int64, C.c_int64, p]
     for f in ("ks_load_nodes", "ks_submit_pods", "ks_step", "ks_filter", "ks_score", "ks_usage", "ks_usage_at",
-              "ks_usage_digest", "ks_pod_lookup", "ks_node_pods"):
+              "ks_usage_digest", "ks_pod_lookup", "ks_node_pods", "ks_requested_at", "ks_filter_at", "ks_score_at",
+              "ks_cluster_series", "ks_node_peaks"):
         getattr(L, f).restype = C.c_int
     L.ks_current_tick.argtypes = [p]
     L.ks_current_tick.restype = C.c_int64

@@ -12,6 +12,8 @@ RegisterScorer         (kubesim/kubesim.go:78-86); built-in device plugins only
 submit (Submitter)     ``submit`` (kubesim/kubesim.go:126-139)
 Run                    ``step(ticks)`` — advances the tick loop (kubesim/kubesim.go:90-123)
 api.Filter / Scorer    ``filter(pod)`` / ``score(pod)``
+scheduleOne's trace    ``filter_at(pod)`` / ``score_at(pod)`` for bound pods; node state at a
+                       past tick: ``requested_at``, ``cluster_series``, ``node_peaks``
 =====================  ==============================================================
 
 Errors come back as :class:`KsError` with the reference's kind (``InvalidArgument`` /
@@ -193,6 +195,40 @@ class Engine:
         """[t_hi - t_lo][6] uint64: per tick Σ_n usage[n][k] (k < 3) and Σ_n mix(n) usage[n][k-3]."""
         out = np.zeros((max(t_hi - t_lo, 0), 6), np.uint64)
         self._check(self._L.ks_usage_digest(self.h, t_lo, t_hi, _p(out)))
+        return out
+
+    # -- scheduler state at past ticks (include/ks_engine.h, ks_requested_at ...) --------------
+    def requested_at(self, t: int):
+        """[n][4] int64 at any past tick 0 <= t <= the current tick: per node Σ requested cpu /
+        memory / gpu (milli-units) and the running pods (kubesim/node/node.go:97-118)."""
+        out = np.zeros((self.n, 4), np.int64)
+        self._check(self._L.ks_requested_at(self.h, t, _p(out)))
+        return out
+
+    def filter_at(self, pod: int):
+        """``filter(pod)`` as it was when the already-bound ``pod`` was scheduled."""
+        mask = np.zeros(self.n, np.uint8)
+        self._check(self._L.ks_filter_at(self.h, pod, _p(mask)))
+        return mask
+
+    def score_at(self, pod: int):
+        """``score(pod)`` as it was when the already-bound ``pod`` was scheduled (-1 = no entry);
+        its lowest-index argmax is the node the pod was bound to."""
+        score = np.zeros(self.n, np.int64)
+        self._check(self._L.ks_score_at(self.h, pod, _p(score)))
+        return score
+
+    def cluster_series(self, t_lo: int, t_hi: int):
+        """[t_hi - t_lo][KS_SERIES_COLS] int64 per tick: running pods, Σ requested cpu / memory /
+        gpu, pods bound Ok so far, bound OverCapacity so far, pending pods."""
+        out = np.zeros((max(t_hi - t_lo, 0), _lib.KS_SERIES_COLS), np.int64)
+        self._check(self._L.ks_cluster_series(self.h, t_lo, t_hi, _p(out)))
+        return out
+
+    def node_peaks(self, t_lo: int, t_hi: int):
+        """[n][4] int64: per node and column the maximum of ``requested_at(t)`` over t_lo <= t < t_hi."""
+        out = np.zeros((self.n, 4), np.int64)
+        self._check(self._L.ks_node_peaks(self.h, t_lo, t_hi, _p(out)))
         return out
 
     def pod_lookup(self, node: int, key_id: int):
