@@ -75,6 +75,7 @@ const (
 const (
 	FlagNoOverlap   = uint32(C.KS_ENGINE_NO_OVERLAP)   // the plain batch chain (no fused next-batch scan)
 	FlagPrunedLists = uint32(C.KS_ENGINE_PRUNED_LISTS) // pruned block lists at any cluster size
+	FlagSmallE      = uint32(C.KS_ENGINE_SMALL_E)      // test only: E overflows at 128 changed nodes (rescan path)
 )
 
 // ScorerSpec is one registered device scorer (registration order is kept).

@@ -115,7 +115,12 @@ enum { KS_ENGINE_FORCE_WIDE = 1, KS_ENGINE_NO_TINY = 2, KS_ENGINE_NO_MICRO = 4,
         * top-L (a running per-pod threshold) and the merge reads only those — the default for chunk-
         * resolver clusters of >= 1,024 scan blocks (262,144 nodes); the flag forces it at every size
         * (same binds; to test the two list forms against each other). */
-       KS_ENGINE_PRUNED_LISTS = 512 };
+       KS_ENGINE_PRUNED_LISTS = 512,
+       /* SMALL_E (test only): the window prep's E overflow test trips at 128 changed nodes instead of
+        * 2,048 (array sizes stay), so small shapes reach the rescan path — on single-shard overlapped
+        * engines an empty round whose fused scan lists the same pods again, elsewhere the conditional
+        * scan.  Same binds; batching differs. */
+       KS_ENGINE_SMALL_E = 2048 };
 
 typedef struct {
     int64_t pod;    /* FIFO index (submission order) */
@@ -319,8 +324,10 @@ typedef struct {
 ks_status ks_last_step_stats(const ks_engine* eng, ks_step_stats* out);
 /* The same per kernel of the batch chain (profiling on): summed HIP-event ms and launch counts of
  * the window prep (launched for a pass's first batch and on the plain chain; an overlapped batch's
- * window is computed inside the previous chunk kernel), the scan (the overlap's conditional rescan
- * included, mostly an empty launch), the list merge (with the candidate lists, a sharded engine's
+ * window is computed inside the previous chunk kernel), the scan (scan_n: the scan launches actually made —
+ * one per batch with, on sharded overlapped engines, the conditional rescan, mostly an empty launch;
+ * on a single-shard overlapped engine only a pass's first batch launches one, so scan_n == prep_n
+ * and the other batches' scan interval brackets nothing), the list merge (with the candidate lists, a sharded engine's
  * per-part merges and exchange), and the resolve launch — the chunk kernel alone, or fused with the
  * next batch's speculative scan and window prep.  Sharded engines: part_ms = the per-part merges
  * and xchg_ms = the exchange (RCCL all-gather, or the host exchange's copies, callback and wait),

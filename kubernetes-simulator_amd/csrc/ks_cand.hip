@@ -99,7 +99,9 @@ constexpr int kEPer = kEMax / 256;
 // list's entries outside E and thr = its last key; the overlap's longer lists keep kTopL exact
 // entries even when the previous batch bound some of the top ones.)
 static_assert(kTopLOverlap >= kTopL, "merged lists kept at the longest list length");
-template <int kMode, int kLL>
+// kDirect (the two-launch chain): a kept entry's slot record from the constants table and the usage
+// fields (load_rec12c) instead of the ten SoA fields.
+template <int kMode, int kLL, bool kDirect>
 __device__ __forceinline__ void cand_list(const EngineArgs& a, WinWS& ws, int i, const uint64_t* cand,
                                           const uint64_t* ek, int n_e) {
     static_assert(kLL >= kTopL && kLL <= kWave, "one list entry per lane");
@@ -156,8 +158,13 @@ __device__ __forceinline__ void cand_list(const EngineArgs& a, WinWS& ws, int i,
         // the record and E index read before the claim (a claimer needs them; the reads overlap
         // the claim's round trip)
         NodeV rec{};
+        uint4 rw[3] = {};
         int32_t eix = -1;
-        if (valid) { rec = load_node(a.s, nd); eix = a.e_idx[nd]; }
+        if (valid) {
+            if constexpr (kDirect) load_rec12c(a, nd, rw);
+            else rec = load_node(a.s, nd);
+            eix = a.e_idx[nd];
+        }
         // the node's first kept entry in pod order (the chunk kernel numbers the batch's candidates by
         // it: deterministic ids, so every rank cuts a batch at the same pod)
         if (valid && a.det_cids) atomicMin(&a.n_first[nd], i * kR + lane);
@@ -174,7 +181,12 @@ __device__ __forceinline__ void cand_list(const EngineArgs& a, WinWS& ws, int i,
             sl = base + __popcll(cm & ((1ull << lane) - 1ull));
             ws.slot_node[sl] = nd;
             if (sl < kSlotMax) {
-                put_rec(ws.slot_rec[sl], rec);
+                if constexpr (kDirect) {
+                    uint4* o = reinterpret_cast<uint4*>(ws.slot_rec[sl]);
+                    o[0] = rw[0]; o[1] = rw[1]; o[2] = rw[2];
+                } else {
+                    put_rec(ws.slot_rec[sl], rec);
+                }
                 ws.slot_eix[sl] = eix;
             }
             atomicExch(&a.n_slot[nd], sl);
@@ -211,7 +223,7 @@ constexpr int kMergeMaxWaves = 16;
 thread_local const EngineArgs* ks_mcl_host_args = nullptr;  // (diagnostic build: set by step_body before each launch)
 #endif
 namespace sq {
-template <int kMode, int kLL>
+template <int kMode, int kLL, bool kDirect>
 #ifdef KS_MCL_BYVAL  // (diagnostic build only: the engine arguments by value, VERDICT r5 item 1's A/B)
 __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs av, const uint64_t* src,
                                                          int64_t pod_stride, int32_t nl, int64_t list_stride, int own_fb) {
@@ -258,42 +270,36 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
 #pragma unroll
     for (int k = 0; k < kLL; ++k) top[k] = 0;
     const uint64_t* lists = src + (int64_t)(reuse ? 0 : sb) * pod_stride;
-    // independent reads first: this thread's first block list, then the E nodes' keys (dependent
-    // chains: node, slots, expiring requests) while it is in flight
-    uint64_t lv0[kLL];
-    const bool has0 = tid < nfl;
-    {
-        const int l0 = has0 ? (pruned ? scn::flagged_block(tid, 0, nl, F) : tid) : 0;
-        const ulonglong2* lp = reinterpret_cast<const ulonglong2*>(lists + (int64_t)l0 * list_stride);
-#pragma unroll
-        for (int k = 0; k < kLL / 2; ++k) {
-            const ulonglong2 w = has0 ? lp[k] : make_ulonglong2(0, 0);
-            lv0[2 * k] = w.x;
-            lv0[2 * k + 1] = w.y;
-        }
-    }
-    // The E nodes' keys, into LDS, from the records the window prep staged (ws.e_rec: three 16-byte
-    // words per E node).  The first two per thread (E nodes tid, tid + nthr) have their reads issued
-    // with the counts (unconditionally, clamped into the arrays: one dependent round trip fewer);
-    // any further ones (more than 2 nthr E nodes) in a plain loop.
+    // The E nodes' keys, into LDS.  Staged form: from the records the scan launch staged (ws.e_rec:
+    // three 16-byte words per E node).  Direct form (kDirect, the two-launch chain: no scan launch
+    // runs before this kernel): from the node table — the constants table's two words and the four
+    // usage fields (load_rec12c), one dependent round trip after ws.e_node; those reads stay in
+    // flight over the block-list merge, and the keys are computed after it.  The first two E nodes
+    // per thread (tid, tid + nthr) have their reads issued with the counts (unconditionally,
+    // clamped into the arrays: one dependent round trip fewer); any further ones (more than 2 nthr E
+    // nodes) in a plain loop.
     __shared__ uint64_t ek[kEMax];
-    const int n_e = ws.n_e;
-    {
-        const int64_t start = a.ctr[kCtrStart];
-        const int hi = ws.win_hi[b], n_es = ws.n_es;
-        uint4 er[2][3];
-        int32_t en[2], eu[2], ue[2];
+    const int n_e = ws.n_e, n_es = ws.n_es;
+    const int hi = ws.win_hi[b];
+    const int64_t start = a.ctr[kCtrStart];
+    uint4 er[2][3];
+    int32_t en[2], eu[2], ue[2];
+    auto e_index = [&]() {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int k = tid + q * nthr;
             const int kc = k < kEMax ? k : kEMax - 1;
             const int ks = k < kWinSlots ? k : kWinSlots;
             en[q] = ws.e_node[kc];
-            const uint4* r = reinterpret_cast<const uint4*>(ws.e_rec[kc]);
-            er[q][0] = r[0]; er[q][1] = r[1]; er[q][2] = r[2];
+            if constexpr (!kDirect) {
+                const uint4* r = reinterpret_cast<const uint4*>(ws.e_rec[kc]);
+                er[q][0] = r[0]; er[q][1] = r[1]; er[q][2] = r[2];
+            }
             eu[q] = ws.e_off[ks];
             ue[q] = ws.e_off[ks < kWinSlots ? ks + 1 : ks];
         }
+    };
+    auto e_keys = [&]() {
 #if defined(KS_MCL_DIAG) && KS_MCL_DIAG == 2
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         uint64_t t_e0 = pstamp();
@@ -317,8 +323,13 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
 #pragma unroll 1
         for (int k = tid + 2 * nthr; k < n_e; k += nthr) {
             const int32_t n = ws.e_node[k];
-            const uint4* r = reinterpret_cast<const uint4*>(ws.e_rec[k]);
-            const uint4 w3[3] = {r[0], r[1], r[2]};
+            uint4 w3[3];
+            if constexpr (kDirect) {
+                load_rec12c(a, n, w3);
+            } else {
+                const uint4* r = reinterpret_cast<const uint4*>(ws.e_rec[k]);
+                w3[0] = r[0]; w3[1] = r[1]; w3[2] = r[2];
+            }
             NodeV w = get_rec12(w3);
             const int ue1 = k < n_es ? ws.e_off[k + 1] : 0;
             for (int u = k < n_es ? ws.e_off[k] : 0; u < ue1; ++u) {
@@ -333,6 +344,30 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
         if (tid == 0) { atomicAdd((unsigned long long*)&a.ctr[14], pstamp() - t_e0); atomicAdd((unsigned long long*)&a.ctr[24], (unsigned long long)(n_e > tid) + (n_e > tid + nthr)); }
         if (tid == 0) atomicAdd((unsigned long long*)&a.ctr[25], (unsigned long long)n_e);
 #endif
+    };
+    // independent reads first: (direct form) the E nodes' ids and slot ranges, this thread's first
+    // block list, then the E nodes' records (dependent chains: node, slots, expiring requests) while
+    // it is in flight
+    if constexpr (kDirect) e_index();
+    uint64_t lv0[kLL];
+    const bool has0 = tid < nfl;
+    {
+        const int l0 = has0 ? (pruned ? scn::flagged_block(tid, 0, nl, F) : tid) : 0;
+        const ulonglong2* lp = reinterpret_cast<const ulonglong2*>(lists + (int64_t)l0 * list_stride);
+#pragma unroll
+        for (int k = 0; k < kLL / 2; ++k) {
+            const ulonglong2 w = has0 ? lp[k] : make_ulonglong2(0, 0);
+            lv0[2 * k] = w.x;
+            lv0[2 * k + 1] = w.y;
+        }
+    }
+    if constexpr (kDirect) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q)  // (an index past n_e holds an older batch's node or 0: read node 0)
+            load_rec12c(a, tid + q * nthr < n_e ? en[q] : 0, er[q]);
+    } else {
+        e_index();
+        e_keys();
     }
     if (has0) {  // (the first list is the thread's top as it is: sorted)
 #pragma unroll
@@ -363,6 +398,7 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
         if (lane == 0) wl[wave][r] = m;
         if (hit && lane == __ffsll((unsigned long long)hit) - 1) head++;
     }
+    if constexpr (kDirect) e_keys();  // (cand_list reads ek after its own barriers)
     __syncthreads();
     PDG(MDG_AT(7, pt);)
     if (wave == 0 && nthr <= 256) {  // the wave lists' top kLL: one candidate per lane (4 waves)
@@ -407,7 +443,7 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
     if (reuse) __syncthreads();
     if (tid < kLL) ws.mrg[mpar][b][tid] = pc[tid];
     PDG(MDG_AT(8, pt);)
-    cand_list<kMode, kLL>(a, ws, b, pc, ek, n_e);
+    cand_list<kMode, kLL, kDirect>(a, ws, b, pc, ek, n_e);
 }
 
 }  // namespace sq
@@ -419,7 +455,8 @@ hipError_t launch_window_prep(const EngineArgs* d, bool head, bool spec, int slo
 }
 
 hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t* lists, int64_t pod_stride,
-                           int32_t nl, int64_t list_stride, int nl_max, hipStream_t st, int L, bool own_fallback) {
+                           int32_t nl, int64_t list_stride, int nl_max, hipStream_t st, int L, bool own_fallback,
+                           bool direct) {
     const int fb = own_fallback ? 1 : 0;
     static_assert(sq::kEPer * 256 >= kEMax, "E keys per thread at 256 threads");
     const dim3 g(B), t(nl_max > 1024 ? 1024 : 256);
@@ -428,16 +465,19 @@ hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t*
     const EngineArgs hv = *ks_mcl_host_args;  // (diagnostic: the host copy, as commit 63524d5 passed it)
 #define d hv
 #endif
-#define KS_MCL(LL)                                                                                                   \
+#define KS_MCL(LL, DR)                                                                                                   \
     switch (mode) {                                                                                                  \
-        case kEvalMicro: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalMicro, LL>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break; \
-        case kEvalTiny: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalTiny, LL>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break;   \
-        case kEvalNarrow: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalNarrow, LL>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break; \
-        default: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalWide, LL>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break;          \
+        case kEvalMicro: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalMicro, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break; \
+        case kEvalTiny: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalTiny, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break;   \
+        case kEvalNarrow: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalNarrow, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break; \
+        default: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalWide, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break;          \
     }
-    if (L == kTopL) { KS_MCL(kTopL) }
-    else if (L == kTopLOverlap) { KS_MCL(kTopLOverlap) }
-    else return hipErrorInvalidValue;
+    if (L != kTopL && L != kTopLOverlap) return hipErrorInvalidValue;
+    if (direct) {
+        if (L == kTopL) { KS_MCL(kTopL, true) } else { KS_MCL(kTopLOverlap, true) }
+    } else {
+        if (L == kTopL) { KS_MCL(kTopL, false) } else { KS_MCL(kTopLOverlap, false) }
+    }
 #undef KS_MCL
 #ifdef KS_MCL_BYVAL
 #undef d

@@ -704,7 +704,8 @@ struct WinWS {
     int32_t e_slot[kWinSlots];
     // E node k's record after the window's head (put_rec12), staged by the first workgroups of the
     // scan launch before merge_cl (ks_kernels.hip scan_kernel): each merge_cl workgroup reads three
-    // contiguous 16-byte words per E node instead of gathering ten scattered fields
+    // contiguous 16-byte words per E node instead of gathering ten scattered fields (unused on the
+    // two-launch chain, which has no such launch: EngineArgs::two_launch)
     uint32_t e_rec[kEMax][12];
     // pod i's static candidates, sorted descending
     uint64_t cl_key[kWinMaxB][kChR];
@@ -732,7 +733,11 @@ struct WinWS {
     // be rescanned (the speculative scan covered other pods, or the touched nodes overflow E)
     int32_t touched[kTouchMax];
     int32_t n_touched, rescan;
-    int32_t lset, pad_;                   // pruned lists: the set holding this batch's lists (EngineArgs)
+    int32_t lset;                         // pruned lists: the set holding this batch's lists (EngineArgs)
+    // two-launch chain (EngineArgs::two_launch): the window prep published an empty batch instead of
+    // flagging a rescan — the empty round's fused scan builds fresh lists of the same pods on the
+    // committed table, and the prep after it takes no changed node into E (ks_prep.h)
+    int32_t fresh;
     // Early stop without a rescan (round 6): when the previous batch k stopped early, this batch's
     // first `split` pods are batch k's pods [moff, moff + split) and take the merged top-L lists
     // merge_cl kept for them (mrg[mpar ^ 1]); the others take the speculative scan's lists at slot
@@ -795,9 +800,35 @@ struct EngineArgs {
     int32_t lset;            // the set this argument record's scans write
     int32_t det_cids;        // chunk resolver: number the candidates by first appearance (sharded engines:
                              // every rank must cut its batches at the same pods), not by claim order
-    int32_t pad3_;
+    // The two-launch overlapped chain (single-shard engines on the fused overlap, ks_engine.cpp
+    // step_body): no conditional scan launch between the chunk kernel and merge_cl.  merge_cl
+    // computes its E keys from the node table (no staged WinWS::e_rec), and a window prep that must
+    // rescan publishes an empty batch instead of flagging one (ks_prep.h).
+    int32_t two_launch;
     const ScanRec* srec;     // [P] the pods' scan records (the micro evaluator's scan form)
+    // [n_pad][2] the node fields no batch kernel writes, packed in the 12-word record's format
+    // (put_rec12): {ac am ag ap} and {taint label} — one cache line per node instead of six.  Filled
+    // by launch_node_consts at the start of each step that runs the two-launch chain.
+    const uint4* ncst;
+    int32_t e_lim;           // window prep's E overflow threshold (kEMax; KS_ENGINE_SMALL_E: kSmallE)
+    int32_t pad4_;
 };
+constexpr int kSmallE = 128;
+static_assert(kSmallE <= kEMax, "E threshold within the arrays");
+// Node nd's record from the constants table and the four usage fields of the SoA (the two-launch
+// chain's merge_cl): the same 12 words put_rec12(load_node) gives.
+__device__ __forceinline__ void load_rec12c(const EngineArgs& a, int32_t nd, uint4 (&w)[3]) {
+#ifdef KS_E_FROM_SOA  // (A/B build: every field from the SoA, ten cache lines per node)
+    const NodeV v = load_node(a.s, nd);
+    w[0] = make_uint4((uint32_t)v.ac, (uint32_t)v.am, (uint32_t)v.ag, (uint32_t)(v.ap > 0x7FFFFFFF ? 0x7FFFFFFF : v.ap));
+    w[2] = make_uint4((uint32_t)v.taint, (uint32_t)(v.taint >> 32), (uint32_t)v.label, (uint32_t)(v.label >> 32));
+    w[1] = make_uint4((uint32_t)v.rc, (uint32_t)v.rm, (uint32_t)v.rg, (uint32_t)v.nr);
+#else
+    w[0] = a.ncst[2 * (int64_t)nd];
+    w[2] = a.ncst[2 * (int64_t)nd + 1];
+    w[1] = make_uint4((uint32_t)a.s.rc[nd], (uint32_t)a.s.rm[nd], (uint32_t)a.s.rg[nd], (uint32_t)a.s.nr[nd]);
+#endif
+}
 // pruned lists: pod b's bitmap / threshold in set `set`
 __host__ __device__ __forceinline__ uint64_t* lbit_of(const EngineArgs& a, int set, int b) {
     return a.lbit + ((int64_t)set * a.B + b) * a.nwl;
@@ -848,7 +879,8 @@ int small_resolver_max_nodes();
 // 32-bit words (scaled capacities < 2^32 - 1) and every total + 1 < 2^16; its batch is
 // launch_window_prep(head) -> scan -> launch_merge_cl -> launch_chunk_only, or with the overlap
 // launch_window_prep(head, spec) -> conditional scan -> merge_cl -> chunk, the next batch's scan
-// on a second stream beside the chunk kernel (its commit writes the touched nodes)
+// on a second stream beside the chunk kernel (its commit writes the touched nodes); single-shard
+// engines on the fused overlap: merge_cl(direct) -> chunk_scan (the two-launch chain)
 hipError_t launch_chunk_only(const EngineArgs* d, int mode, hipStream_t st);
 // the same with the next batch's speculative scan fused in (ds: its arguments; `workers` scan
 // workgroups beside the resolver's; 16-bit key tables, so key16 engines only); after its commit the
@@ -869,9 +901,11 @@ extern thread_local const EngineArgs* ks_mcl_host_args;
 #endif
 // own_fallback: when the window prep flagged a rescan, read the engine's own block lists over the
 // whole cluster instead of `lists` (the pipelined engines' rescan scans every block locally)
+// direct: the two-launch chain's form (EngineArgs::two_launch) — E keys and slot records from the
+// node table and the constants table, no staged WinWS::e_rec
 hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t* lists, int64_t pod_stride,
                            int32_t nl, int64_t list_stride, int nl_max, hipStream_t st, int L = kTopL,
-                           bool own_fallback = false);
+                           bool own_fallback = false, bool direct = false);
 struct BindSeg {
     const int32_t* node;
     const int32_t* status;
@@ -879,6 +913,8 @@ struct BindSeg {
 };
 hipError_t launch_gather_binds(const BindSeg* segs, int S, int64_t max_n, int32_t* node, int32_t* status,
                                hipStream_t st);
+// the node constants table (EngineArgs::ncst) of nodes [0, n_pad) from the SoA
+hipError_t launch_node_consts(const NodeSoA& s, int64_t n_pad, uint4* out, hipStream_t st);
 hipError_t launch_rescale(const NodeSoA& s, int64_t n_pad, PodRec* pods, int64_t P, const int64_t f[3], hipStream_t st);
 
 // Host-staged submits (ks_engine.cpp): copy `bytes` from device-visible pinned host memory to dst.

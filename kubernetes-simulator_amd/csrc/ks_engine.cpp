@@ -137,6 +137,7 @@ struct ks_engine {
     int nwb = 0;
     bool nodes_loaded = false;
     void* node_mem = nullptr;
+    uint4* d_ncst = nullptr;  // the node constants table (ks::EngineArgs::ncst), [n_pad][2]
     ks::NodeSoA s{};
 
     // pods (device)
@@ -323,6 +324,9 @@ ks::EngineArgs make_args(ks_engine* e) {
     a.nwl = e->nwl;
     a.lset = 1;  // the engine's own scans (the speculative scan's record: set 0, step_body)
     a.srec = e->srec.p;
+    a.ncst = e->d_ncst;
+    a.two_launch = 0;  // (step_body sets it for the chain it runs)
+    a.e_lim = (e->flags & KS_ENGINE_SMALL_E) ? ks::kSmallE : ks::kEMax;
     return a;
 }
 
@@ -483,7 +487,7 @@ ks_status engine_init(const ks_config* cfg, ks_engine** out) {
     if (cfg->batch_pods < 0 || cfg->batch_pods > kMaxBatch) return KS_EINVAL;
     if (cfg->engine_flags &
         ~(uint32_t)(KS_ENGINE_FORCE_WIDE | KS_ENGINE_NO_TINY | KS_ENGINE_NO_MICRO | KS_ENGINE_ONE_POD_RESOLVER |
-                    KS_ENGINE_CHUNK_RESOLVER | KS_ENGINE_NO_OVERLAP | KS_ENGINE_PRUNED_LISTS))
+                    KS_ENGINE_CHUNK_RESOLVER | KS_ENGINE_NO_OVERLAP | KS_ENGINE_PRUNED_LISTS | KS_ENGINE_SMALL_E))
         return KS_EINVAL;
     int64_t const_total = 0, w_lr = 0, w_ba = 0;
     for (int i = 0; i < cfg->n_scorers; i++) {
@@ -557,6 +561,7 @@ void engine_free(ks_engine* e) {
     e->preg.release(); e->d_blk.release(); e->d_digest.release(); e->srec.release();
     e->d_qs.release(); e->d_qi.release();
     if (e->node_mem) (void)hipFree(e->node_mem);
+    if (e->d_ncst) (void)hipFree(e->d_ncst);
     if (e->lists) (void)hipFree(e->lists);
     if (e->cand) (void)hipFree(e->cand);
     if (e->cand_all) (void)hipFree(e->cand_all);
@@ -716,6 +721,7 @@ ks_status ks_load_nodes(ks_engine* e, int64_t n, const int64_t* alloc, const uin
     }
     HIPCHK(e, hipMalloc(&e->node_mem, sizeof(int64_t) * 10 * np));
     HIPCHK(e, hipMemcpyAsync(e->node_mem, h.data(), sizeof(int64_t) * 10 * np, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipMalloc(&e->d_ncst, sizeof(uint4) * 2 * np));
     int64_t* b = (int64_t*)e->node_mem;
     e->s.ac = b; e->s.am = b + np; e->s.ag = b + 2 * np; e->s.ap = b + 3 * np;
     e->s.rc = b + 4 * np; e->s.rm = b + 5 * np; e->s.rg = b + 6 * np; e->s.nr = b + 7 * np;
@@ -1347,7 +1353,6 @@ static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t ca
     const int which = resolver_of(e);
     const bool fused = which == kResolveChunk;
     HIPCHK(e, hipMemcpyAsync(e->d_ctr, e->h_ctr, 5 * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(e->d_args, e->h_args, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
     // the overlap (chunk class, 16-bit keys, not profiling): batch b + 1's scan fused into batch b's
     // chunk kernel, over the pods after batch b (the speculative counters window prep writes) and
     // this rank's scan blocks.  Sharded engines too: every rank's lists are speculative alike and its
@@ -1367,6 +1372,16 @@ static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t ca
     // so the exchanged lists always serve; when E overflows, the conditional rescan scans every block
     // locally (no second exchange: every rank holds the whole table) and merge_cl merges those.
     const bool pipe = fused && !overlap && e->overlap && e->st2 && e->world * e->vsh > 1;
+    // The two-launch chain (single-shard engines on the fused overlap): an overlapped batch is merge_cl
+    // -> chunk kernel, with no conditional scan launch in front (a launch that scanned 0-4 times per
+    // 32,768-pod step at C3 and otherwise only staged E records).  merge_cl reads its E nodes from
+    // the node table and the constants table filled here (after the stage flush, and after any
+    // rescale: ks_submit_pods runs it); a window prep that must rescan publishes an empty batch
+    // instead, whose round's fused scan lists the same pods again (ks_prep.h).
+    const bool two = overlap && e->world * e->vsh == 1;
+    e->h_args->two_launch = two ? 1 : 0;
+    HIPCHK(e, hipMemcpyAsync(e->d_args, e->h_args, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
+    if (two) HIPCHK(e, ks::launch_node_consts(e->s, e->n_pad, e->d_ncst, st));
     // the overlap's single-shard lists are longer (ks_device.h kTopLOverlap, ks_cand.hip cand_list)
     // (and the pipelined chain's: its speculative lists go stale like the overlap's)
     e->L = (overlap && e->world * e->vsh == 1 && !e->prune) || pipe ? ks::kTopLOverlap : ks::kTopL;
@@ -1393,7 +1408,7 @@ static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t ca
     int64_t launches = 0;
     double scan_ms = 0, res_ms = 0;
     ks_kernel_stats ks{};
-    std::vector<uint8_t> kind;  // per launch: 1 window prep launched, 2 fused resolve
+    std::vector<uint8_t> kind;  // per launch: 1 window prep launched, 2 fused resolve, 16 scan launched
     while (true) {
         const int64_t nbat = (p_hi - start + e->B - 1) / e->B;
         for (int64_t b = 0; b < nbat; b++) {
@@ -1424,14 +1439,16 @@ static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t ca
             // (an overlapped batch's window was computed by the previous chunk kernel after its commit)
             if (!spec) HIPCHK(e, fused ? ks::launch_window_prep(d, true, false, (int)(b & 1), st) : ks::launch_expire_head(d, 1, st));
             if (ev[1]) HIPCHK(e, hipEventRecord(ev[1], st));
-            // (chunk class: the scan launch also stages the batch's E records for merge_cl)
-            HIPCHK(e, ks::launch_scan(d, 1, e->blk_n, e->B, e->PG, e->mode, key16(e), st, spec, e->prune, e->L, fused));
+            // (chunk class: the scan launch also stages the batch's E records for merge_cl; the
+            // two-launch chain has neither the staging nor an overlapped batch's conditional scan)
+            const bool scan = !(two && spec);
+            if (scan) HIPCHK(e, ks::launch_scan(d, 1, e->blk_n, e->B, e->PG, e->mode, key16(e), st, spec, e->prune, e->L, fused && !two));
             if (ev[2]) HIPCHK(e, hipEventRecord(ev[2], st));
             const int G = e->world * e->vsh;
             hipEvent_t evx[2] = {ev[5], ev[6]};  // part merges | exchange | merge (sharded engines)
             const int64_t L = ks::kTopL, BL = (int64_t)e->B * L;
             if (G == 1) {
-                HIPCHK(e, fused ? ks::launch_merge_cl(d, e->mode, e->B, nullptr, 0, 0, 0, e->nblk, st, e->L)
+                HIPCHK(e, fused ? ks::launch_merge_cl(d, e->mode, e->B, nullptr, 0, 0, 0, e->nblk, st, e->L, false, two)
                                 : ks::launch_merge(d, 1, e->B, nullptr, 0, 0, 0, nullptr, e->nblk, st));
             } else {
                 HIPCHK(e, part_merges(e, d, st, -1));
@@ -1448,7 +1465,7 @@ static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t ca
             else
                 HIPCHK(e, fused ? ks::launch_chunk_only(d, e->mode, st) : launch_resolver(d, 1, e->mode, which, st));
             if (ev[4]) HIPCHK(e, hipEventRecord(ev[4], st));
-            if (e->profiling) kind.push_back((uint8_t)((!spec ? 1 : 0) | (overlap && b + 1 < nbat ? 2 : 0) | (G > 1 ? 4 : 0)));
+            if (e->profiling) kind.push_back((uint8_t)((!spec ? 1 : 0) | (overlap && b + 1 < nbat ? 2 : 0) | (G > 1 ? 4 : 0) | (scan ? 16 : 0)));
             launches++;
         }
         HIPCHK(e, hipMemcpyAsync(e->h_ctr, e->d_ctr, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -1511,7 +1528,7 @@ static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t ca
             scan_ms += t[1];
             res_ms += t[3];
             ks.prep_ms += t[0]; ks.prep_n += kind[l] & 1;
-            ks.scan_ms += t[1]; ks.scan_n += 1;
+            ks.scan_ms += t[1]; ks.scan_n += kind[l] & 16 ? 1 : 0;  // (scan launches actually made)
             ks.merge_ms += t[2]; ks.merge_n += 1;
             if (kind[l] & 2) { ks.fused_ms += t[3]; ks.fused_n += 1; }
             else { ks.resolve_ms += t[3]; ks.resolve_n += 1; }

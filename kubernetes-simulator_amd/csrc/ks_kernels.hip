@@ -1245,6 +1245,24 @@ hipError_t launch_gather_binds(const BindSeg* segs, int S, int64_t max_n, int32_
     return hipGetLastError();
 }
 
+// The node constants table (EngineArgs::ncst): per node the six fields no batch kernel writes, in
+// the 12-word record's words 0 and 2 (put_rec12).
+__global__ __launch_bounds__(256) void node_consts_kernel(const NodeSoA s, int64_t n_pad, uint4* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    const int64_t ap = s.ap[i];
+    const uint64_t t = s.taint[i], l = s.label[i];
+    out[2 * i] = make_uint4((uint32_t)s.ac[i], (uint32_t)s.am[i], (uint32_t)s.ag[i],
+                            (uint32_t)(ap > 0x7FFFFFFF ? 0x7FFFFFFF : ap));
+    out[2 * i + 1] = make_uint4((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)l, (uint32_t)(l >> 32));
+}
+
+hipError_t launch_node_consts(const NodeSoA& s, int64_t n_pad, uint4* out, hipStream_t st) {
+    if (n_pad <= 0) return hipSuccess;
+    hipLaunchKernelGGL(node_consts_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, s, n_pad, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_rescale(const NodeSoA& s, int64_t n_pad, PodRec* pods, int64_t P, const int64_t f[3], hipStream_t st) {
     hipLaunchKernelGGL(rescale_kernel, dim3(1024), dim3(256), 0, st, s, n_pad, pods, P, f[0], f[1], f[2]);
     return hipGetLastError();

@@ -14,7 +14,9 @@
 //     block lists come from the speculative scan that ran beside the previous batch's resolve, on
 //     the node table as it was then — exact for every other node.  The speculative scan covered the
 //     pods after the previous batch; if that batch stopped early (this batch starts elsewhere) or the
-//     changed nodes overflow E, `rescan` asks the conditional scan to redo the lists;
+//     changed nodes overflow E, `rescan` asks the conditional scan to redo the lists — or, on the
+//     two-launch chain (EngineArgs::two_launch: no such launch), the window is published empty and
+//     the next round's fused scan lists the same pods again (`fresh`);
 //   * the speculative counters for the next scan (the pods after this batch), double-buffered by
 //     batch parity `slot`.
 #pragma once
@@ -75,7 +77,7 @@ __device__ __forceinline__ void prep_body(const EngineArgs& a, int64_t start, in
     int nb = (int)min<int64_t>(min<int64_t>(a.B, kWinMaxB), end - start);
     if (err != 0 || nb <= 0) {
         if (tid == 0) {
-            ws.nb = 0; ws.e_cnt = 0; ws.n_e = 0; ws.n_es = 0; ws.rescan = 0; ws.lset = 1;
+            ws.nb = 0; ws.e_cnt = 0; ws.n_e = 0; ws.n_es = 0; ws.rescan = 0; ws.lset = 1; ws.fresh = 0;
             ws.split = 0; ws.moff = 0; ws.mpar = slot;
             spec_out[kCtrStart] = end; spec_out[kCtrEnd] = end; spec_out[kCtrErr] = 0; spec_out[kSpecPrev] = start;
         }
@@ -92,9 +94,12 @@ __device__ __forceinline__ void prep_body(const EngineArgs& a, int64_t start, in
     const int64_t mypos = tid < nb ? a.exp_pos[start + tid] : 0;
     const int64_t sp_start = spec ? spec_in[kCtrStart] : 0;
     const int64_t prev_start = spec ? spec_in[kSpecPrev] : 0;
-    const int n_touched = spec ? ws.n_touched : 0;
+    // two-launch chain: the previous prep published an empty batch, and the empty round's fused
+    // scan has just listed these pods on the committed table (below)
+    const bool fresh = spec && a.two_launch && ws.fresh != 0;
+    const int n_touched = spec && !fresh ? ws.n_touched : 0;
     // the previous batch's E (its nodes join this batch's E when this batch reuses its lists)
-    const int n_eold = spec ? ws.n_e : 0;
+    const int n_eold = spec && !fresh ? ws.n_e : 0;
     constexpr int kOPer = (kEMax + NT - 1) / NT;
     int32_t eold[kOPer];
 #pragma unroll
@@ -122,9 +127,15 @@ __device__ __forceinline__ void prep_body(const EngineArgs& a, int64_t start, in
     // table is in the previous batch's E or was changed by that batch (touched) or this batch's head.
     const bool reuse = spec && start != sp_start && start > prev_start && start < sp_start;
     int rescan = 0;
-    if (spec) rescan = (start != sp_start && !reuse) ||
-                       (int64_t)e_cnt + (e1 - e0) + n_touched + (reuse ? n_eold : 0) > kEMax;
-    const bool touch = spec && !rescan;
+    if (spec && !fresh) rescan = (start != sp_start && !reuse) ||
+                                 (int64_t)e_cnt + (e1 - e0) + n_touched + (reuse ? n_eold : 0) > a.e_lim;
+    // Fresh lists reflect every change so far (the head's expiries included: the prep that published
+    // the empty batch applied them), so E is the window's slot nodes alone — no overflow test
+    // (e_cnt <= kWinSlots < kEMax): a retried batch never flags again.
+    const bool touch = spec && !rescan && !fresh;
+    // two-launch chain: no conditional scan follows.  The head expiries below, then an empty batch
+    // (merge_cl and the resolver do nothing) whose fused scan lists the same pods again.
+    const bool empty = rescan && a.two_launch;
     const int32_t hq = head && tid < e1 - e0 ? a.exp_pod[e0 + tid] : -1;
     const int32_t wq = tid < e_cnt ? a.exp_pod[e_base + tid] : -1;
     int32_t hst = 1, hex = 1, hnd = 0, wst = 1, wex = 1, wnd = 0;
@@ -160,6 +171,16 @@ __device__ __forceinline__ void prep_body(const EngineArgs& a, int64_t start, in
             a.expired[q] = 1;
             if (touch) L.xn[atomicAdd(&L.s_nx, 1)] = nd;
         }
+    }
+    if (empty) {  // (uniform; before any E node is hashed or marked in e_idx: no commit follows to reset it)
+        if (tid == 0) {
+            ws.nb = 0; ws.e_cnt = 0; ws.n_e = 0; ws.n_es = 0; ws.nslot = 0; ws.rescan = 0; ws.lset = 0; ws.fresh = 1;
+            ws.split = 0; ws.moff = 0; ws.mpar = slot;
+            a.ctr[kCtrRescan] += 1;
+            // the next speculative scan: the same pods
+            spec_out[kCtrStart] = start; spec_out[kCtrEnd] = end; spec_out[kCtrErr] = 0; spec_out[kSpecPrev] = start;
+        }
+        return;
     }
     if (touch) {
 #pragma unroll
@@ -257,7 +278,8 @@ __device__ __forceinline__ void prep_body(const EngineArgs& a, int64_t start, in
     for (int k = tid; k < n_e; k += NT) a.e_idx[ws.e_node[k]] = k;
     if (tid == 0) {
         ws.nb = nb; ws.e_cnt = e_cnt; ws.n_e = n_e; ws.n_es = n_es; ws.nslot = 0; ws.rescan = rescan;
-        ws.lset = touch ? 0 : 1;  // pruned lists: the speculative scan's set, or the engine's own scan's
+        ws.lset = touch || fresh ? 0 : 1;  // pruned lists: the speculative scan's set, or the engine's own scan's
+        ws.fresh = 0;
         if (rescan) a.ctr[kCtrRescan] += 1;  // (diagnostics: ks_debug_counters [5])
         if (touch && reuse) a.ctr[kCtrReuse] += 1;
         ws.split = touch && reuse ? (int32_t)(sp_start - start) : 0;

@@ -26,6 +26,7 @@ KS_ENGINE_ONE_POD_RESOLVER = 8
 KS_ENGINE_CHUNK_RESOLVER = 64
 KS_ENGINE_NO_OVERLAP = 256
 KS_ENGINE_PRUNED_LISTS = 512
+KS_ENGINE_SMALL_E = 2048  # test only: window prep's E overflow test at 128 nodes (the rescan path)
 KS_SELFTEST_LR_MICRO = 0
 KS_SERIES_COLS = 7  # ks_cluster_series: running, requested cpu / memory / gpu, bound Ok, bound OverCapacity, pending
 

@@ -61,6 +61,10 @@ def _config(tick_seconds, filter_mode, filters, scorers, device, batch_pods, eng
 
 
 class Engine:
+    """``engine_flags``: ``_lib.KS_ENGINE_*`` bits (include/ks_engine.h) — A/B and test switches that
+    never change the binds.  ``KS_ENGINE_SMALL_E`` is test-only: the batch window's changed-node set
+    overflows at 128 nodes instead of 2,048, so small clusters reach the rescan path."""
+
     def __init__(self, *, tick_seconds=10, filter_mode=_lib.KS_FILTER_REFERENCE_LITERAL, filters=0,
                  scorers=((_lib.KS_SCORER_CONST, 1, 1),), device=0, batch_pods=0, engine_flags=0,
                  _group=None):
