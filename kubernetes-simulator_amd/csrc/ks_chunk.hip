@@ -1052,7 +1052,8 @@ __device__ __forceinline__ void chunk_body(const EngineArgs* __restrict__ A, ChS
                 // ballots sat in the two arms of `half ? ... : ...` — a divergent branch, so each
                 // ballot saw only its own half's lanes: a row whose state overflowed its segments on
                 // the other half's lane was dropped from D instead of stopping the batch, and the pod
-                // could bind a lower node — tests/test_resolvers_gpu.py segment-overflow test.)
+                // could bind a lower node —
+                // tests/test_engine_gpu_c5.py::test_c5_segment_overflow_row_on_either_lane_half.)
 #ifdef KS_BALLOT_LEGACY  // (diagnostic build only: the pre-round-6 form, for the regression test's A/B)
                 const bool bad = half ? ((__ballot(badB) >> gsh) & 0xFFFFu) != 0 : ((__ballot(badA) >> gsh) & 0xFFFFu) != 0;
 #else

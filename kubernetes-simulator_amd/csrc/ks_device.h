@@ -720,12 +720,9 @@ struct WinWS {
     // slot -> node for every claim.  (Until round 6 this array had kSlotMax entries: a batch with more
     // than kSlotMax distinct candidates wrote slot_node[kSlotMax + s] over slot_eix[s] — racing the
     // claimer of slot s, so a candidate's E index could come out as a node id — and the commit's
-    // reset missed the claims past kSlotMax.)
-#ifdef KS_SLOT_IDS_LEGACY  // (diagnostic build only: the round-3..5 layout, for the regression test's A/B)
-    int32_t slot_node[kSlotMax];
-#else
+    // reset missed the claims past kSlotMax.  Batches past kSlotMax claims run under the oracle in
+    // tests/test_candidate_capacity_gpu.py.)
     int32_t slot_node[kSlotIds];
-#endif
     int32_t slot_eix[kSlotMax];           // the node's index in E, -1 if not an E node
     uint32_t slot_rec[kSlotMax][kRecDw];  // the node's record at the batch start (narrow: 12 dwords)
     // overlap (scan of batch k+1 beside the resolve of batch k): the nodes batch k changed (its

@@ -27,6 +27,11 @@ KS_ENGINE_CHUNK_RESOLVER = 64
 KS_ENGINE_NO_OVERLAP = 256
 KS_ENGINE_PRUNED_LISTS = 512
 KS_ENGINE_SMALL_E = 2048  # test only: window prep's E overflow test at 128 nodes (the rescan path)
+# the chunk resolver's per-batch candidate capacities (mirrors of the device constants, for the tests)
+KS_WIN_MAX_B = 256    # csrc/ks_device.h kWinMaxB: pods per batch at the most
+KS_CHR = 20           # csrc/ks_device.h kChR: static candidates kept per pod
+KS_SLOT_MAX = 1536    # csrc/ks_device.h kSlotMax: candidate slots whose record merge_cl stages
+KS_CHUNK_CIDS = 1024  # csrc/ks_chunk.hip kCid: candidates the chunk kernel numbers per batch
 KS_SELFTEST_LR_MICRO = 0
 KS_SERIES_COLS = 7  # ks_cluster_series: running, requested cpu / memory / gpu, bound Ok, bound OverCapacity, pending
 

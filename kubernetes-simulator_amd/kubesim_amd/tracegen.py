@@ -408,7 +408,38 @@ def wide_trace(n_nodes=50_000, n_pods=20_000, seed=0x5EED0006, n_taint_keys=30, 
     return tr
 
 
-def c2_trace(n_nodes=5000, n_pods=100_000, seed=0x5EED0002, **kw):
+def spread_trace(seed, n_pods, period=256, groups=256, per_group=16):
+    """Pods whose selectors are pairwise disjoint: ``groups * per_group`` nodes with the C2
+    distributions, node ``i`` labelled ``spread/k0..k7`` = the bits of ``i % groups`` (the groups are
+    interleaved, so every 256-node scan block holds all of them), pod ``p`` selecting all 8 pairs of
+    group ``p % period``.  Any ``period`` consecutive pods select disjoint ``per_group``-node groups,
+    so the kept candidates of a batch are nearly all distinct nodes (the chunk resolver's candidate
+    slots, ks_device.h WinWS).  16 label pairs in all: inside one mask."""
+    if not 0 < groups <= 256 or not 0 < period <= groups:
+        raise ValueError("spread_trace: 0 < period <= groups <= 256")
+    tr = synth_trace(groups * per_group, n_pods, seed, taints=False, labels=False, tolerations=False,
+                     selectors=False, config="spread")
+    st = StringTable()
+    st.strings = list(tr["strings"])
+    st.index = {x: i for i, x in enumerate(st.strings)}
+    N, P = groups * per_group, int(n_pods)
+    keys = np.array([st.intern(f"spread/k{b}") for b in range(8)], dtype=np.int32)
+    vals = np.array([st.intern("0"), st.intern("1")], dtype=np.int32)
+
+    def pairs(g):  # [len(g), 8, 2]: the 8 pairs spelling each group number
+        bits = (np.asarray(g)[:, None] >> np.arange(8)[None, :]) & 1
+        return np.stack([np.broadcast_to(keys, bits.shape), vals[bits]], axis=2).astype(np.int32)
+
+    nodes, pods = tr["nodes"], tr["pods"]
+    nodes["label"] = pairs(np.arange(N) % groups).reshape(-1, 2)
+    nodes["label_off"] = np.arange(0, 8 * N + 1, 8, dtype=np.int32)
+    pods["sel"] = pairs(np.arange(P) % period).reshape(-1, 2)
+    pods["sel_off"] = np.arange(0, 8 * P + 1, 8, dtype=np.int32)
+    tr["strings"] = st.strings
+    return tr
+
+
+def c2_trace(n_nodes=5000,n_pods=100_000, seed=0x5EED0002, **kw):
     """BASELINE.json configs[1]: 5k nodes / 100k pods, cpu+mem+gpu, multi-phase simSpec."""
     return synth_trace(n_nodes, n_pods, seed, taints=False, labels=False, tolerations=False,
                        selectors=False, config="C2", **kw)

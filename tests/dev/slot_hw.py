@@ -1,8 +1,8 @@
 """Dev tool (not a test): candidate-slot high-water marks and the between-step invariants
 (ks_debug_invariants) of chunk-resolver engines at the bench's configurations — which of them claim
 more than kSlotMax candidate slots in a batch (the round-6 slot_node overflow, ks_device.h WinWS).
-KS_LIB selects a build (tests/dev/devlib.py), e.g. the legacy layout:
-  make -C kubernetes-simulator_amd/csrc variant NAME=legacy DEFS=-DKS_SLOT_IDS_LEGACY"""
+KS_LIB selects a build (tests/dev/devlib.py).  The suite that does pass kSlotMax under the oracle is
+tests/test_candidate_capacity_gpu.py."""
 import os
 import sys
 import threading

@@ -76,6 +76,73 @@ def encoded(trace):
     return encode.encode_trace(trace)
 
 
+# The candidate-capacity inputs (tracegen.spread_trace on 4,096 nodes), pinned on the oracle alone by
+# tests/test_candidate_capacity.py and run on the engines by tests/test_candidate_capacity_gpu.py:
+# "over" claims more candidate slots per 256-pod batch than merge_cl stages, "mid" more than the
+# chunk kernel numbers but fewer than merge_cl stages, "notfound" is "mid" at a seed whose run stops
+# with NotFound.
+SPREAD_CASES = {
+    "over": dict(seed=7, n_pods=2048, period=256),
+    "mid": dict(seed=7, n_pods=1536, period=128),
+    "notfound": dict(seed=9, n_pods=1536, period=128),
+}
+SPREAD_MODES = {
+    "all_lrba": "feeds_all_lrba",
+    "lr2": (1, 7, ((1, 2, 0),)),
+    "ba3_const": (1, 7, ((2, 3, 0), (0, 2, 5))),
+}
+_spread = {}
+
+
+def spread_case(name):
+    """(trace, encoded trace) of a SPREAD_CASES entry, built once."""
+    if name not in _spread:
+        tr = tracegen.spread_trace(**SPREAD_CASES[name])
+        _spread[name] = (tr, encoded(tr))
+    return _spread[name]
+
+
+def shard_ranks(tr, enc, world, vshards, mode="feeds_all_lrba", **kw):
+    """`world` engines on one device as the ranks of a node-sharded run, exchanging candidates
+    through the host (LocalExchange); every rank holds the whole trace.  Returns (engines, exchange)."""
+    from kubesim_amd.engine import Engine, LocalExchange
+    x = LocalExchange(world)
+    fm, fl, sc = MODES[mode] if isinstance(mode, str) else mode
+    engs = []
+    for r in range(world):
+        e = Engine(tick_seconds=tr["tick_seconds"], filter_mode=fm, filters=fl, scorers=sc, **kw)
+        e.shard_host(world, r, x, vshards)
+        e.load_nodes(enc["alloc"], enc["taint"], enc["label"])
+        e.submit(enc["pods"])
+        engs.append(e)
+    return engs, x
+
+
+def step_ranks(engs, k, x=None):
+    """Step every rank `k` ticks, one thread each; a rank that has not returned after the join
+    timeout fails the caller.  Returns each rank's binds."""
+    import threading
+    out = [None] * len(engs)
+
+    def run(r):
+        try:
+            out[r] = engs[r].step(k)
+        except Exception as ex:  # noqa: BLE001 - reported below
+            out[r] = ex
+            if x is not None:  # the other ranks would wait for this one's deposit
+                x.abort()
+    th = [threading.Thread(target=run, args=(r,)) for r in range(len(engs))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(600)
+    assert not any(t.is_alive() for t in th), "a rank hung in the exchange"
+    for o in out:
+        if isinstance(o, Exception):
+            raise o
+    return out
+
+
 _EFF = {1: "NoSchedule", 2: "PreferNoSchedule", 3: "NoExecute"}
 _TOL_EFF = {0: "", 1: "NoSchedule", 2: "PreferNoSchedule", 3: "NoExecute"}
 _OPS = {0: "Equal", 1: "Exists", 2: "Bogus"}

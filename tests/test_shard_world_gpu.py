@@ -11,49 +11,12 @@ import numpy as np
 import pytest
 
 import full_run_digest
-from harness import assert_same_binds, encoded, make_engine, make_oracle, small_trace
+from harness import assert_same_binds, encoded, make_oracle, small_trace
+from harness import shard_ranks as _ranks, step_ranks as _step_all
 from kubesim_amd import _lib, shard, tracegen
-from kubesim_amd.engine import LocalExchange
 
 pytestmark = pytest.mark.gpu
 MODE = "feeds_all_lrba"
-
-
-def _ranks(tr, enc, world, vshards, mode=MODE, **kw):
-    x = LocalExchange(world)
-    engs = []
-    for r in range(world):
-        from kubesim_amd.engine import Engine
-        from harness import MODES
-        fm, fl, sc = MODES[mode]
-        e = Engine(tick_seconds=tr["tick_seconds"], filter_mode=fm, filters=fl, scorers=sc, **kw)
-        e.shard_host(world, r, x, vshards)
-        e.load_nodes(enc["alloc"], enc["taint"], enc["label"])
-        e.submit(enc["pods"])
-        engs.append(e)
-    return engs, x
-
-
-def _step_all(engs, k, x=None):
-    out = [None] * len(engs)
-
-    def run(r):
-        try:
-            out[r] = engs[r].step(k)
-        except Exception as ex:  # noqa: BLE001 - reported below
-            out[r] = ex
-            if x is not None:  # the other ranks would wait for this one's deposit
-                x.abort()
-    th = [threading.Thread(target=run, args=(r,)) for r in range(len(engs))]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(600)
-    assert not any(t.is_alive() for t in th), "a rank hung in the exchange"
-    for o in out:
-        if isinstance(o, Exception):
-            raise o
-    return out
 
 
 @pytest.mark.parametrize("world,vshards", [(2, 1), (2, 3), (3, 2)])
@@ -118,7 +81,8 @@ def _c5_golden_ranks(world, **kw):
     """Every pod of the C5 leg on `world` thread-ranks (one part each) against the committed oracle
     digests, window by window on every rank, with the between-step invariants of every rank's
     engine (ks_debug_invariants: no candidate-slot or E-index mark left set).  Returns the largest
-    number of candidate slots a batch claimed on any rank."""
+    number of candidate slots a batch claimed on any rank (C5 stays far below the slots merge_cl
+    stages; the batches past them run in tests/test_candidate_capacity_gpu.py)."""
     g = full_run_digest.load("c5")
     if g is None:
         pytest.skip("no c5 golden")
@@ -144,16 +108,21 @@ def test_c5_whole_trace_sixteen_ranks_overlapped_match_oracle_golden():
     """BASELINE configs[4] as 16 ranks: 256 scan blocks per rank, so every rank runs the overlap
     (its speculative scan fused into its chunk kernel; ks_engine.cpp kOverlapMaxBlocks) on pruned
     lists (1M nodes), with the exchange every batch — every pod of the C5 leg against
-    tests/golden/full_run.json on every rank."""
-    _c5_golden_ranks(16)
+    tests/golden/full_run.json on every rank.  (The candidate slots stay within the claims a batch
+    can make; their overflow past the staged ones is tests/test_candidate_capacity_gpu.py's.)"""
+    hw = _c5_golden_ranks(16)
+    assert 0 < hw <= _lib.KS_WIN_MAX_B * _lib.KS_CHR, hw
 
 
 def test_c5_whole_trace_eight_ranks_deployment_layout_match_oracle_golden():
     """BASELINE configs[4] in the 8-GPU deployment layout: 8 thread-ranks x 1 part, 512 scan blocks
-    per rank — above kOverlapMaxBlocks, so every rank runs the plain chain on pruned lists (1M
-    nodes) with the exchange every batch; every pod against tests/golden/full_run.json on every
-    rank."""
-    _c5_golden_ranks(8)
+    per rank — above kOverlapMaxBlocks, so every rank runs the pipelined chain (ks_engine.cpp
+    pipe_batch; no rescans here: tests/test_pipe_rescan_gpu.py) on pruned lists (1M nodes) with the
+    exchange every batch; every pod against tests/golden/full_run.json on every
+    rank.  (The candidate slots stay within the claims a batch can make; their overflow past the
+    staged ones is tests/test_candidate_capacity_gpu.py's.)"""
+    hw = _c5_golden_ranks(8)
+    assert 0 < hw <= _lib.KS_WIN_MAX_B * _lib.KS_CHR, hw
 
 
 def test_ranks_without_scan_blocks_match_oracle():
