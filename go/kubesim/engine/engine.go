@@ -418,3 +418,68 @@ func (e *Engine) PodStatus(lo, n int64) ([]PodInfo, error) {
 	}
 	return r, nil
 }
+
+// Device self-tests of ks_selftest (include/ks_engine.h): no engine needed, a deployment can run
+// them once at start-up.
+const (
+	SelftestLRMicro     = int32(C.KS_SELFTEST_LR_MICRO)     // the micro evaluator's LeastRequested floor, every (x, A)
+	SelftestMicroStates = int32(C.KS_SELFTEST_MICRO_STATES) // the micro evaluator and its scan form, every usage of 13 capacity pairs
+)
+
+// Selftest runs one device self-test and returns the number of mismatching cases (0 = pass).
+func Selftest(device int, test int32) (int64, error) {
+	var n C.int64_t
+	if err := status(nil, C.ks_selftest(C.int32_t(device), C.int32_t(test), &n)); err != nil {
+		return -1, err
+	}
+	return int64(n), nil
+}
+
+// EvalConfig is the ks_eval_cfg of SelftestEval: the filter and scorer configuration in the
+// engine's summed form.
+type EvalConfig struct {
+	FeedsScore         bool
+	Filters            uint32
+	HasScorers         bool
+	WeightLR, WeightBA int32
+	ConstTotal         int32
+}
+
+// Column counts and bits of SelftestEval (include/ks_engine.h).
+const (
+	EvalTotalCols = int(C.KS_EVAL_TOTAL_COLS)
+	EvalPruneCols = int(C.KS_EVAL_PRUNE_COLS)
+	EvalScanMicro = uint(C.KS_EVAL_SCAN_MICRO)
+	EvalPruneBit  = uint(C.KS_EVAL_PRUNE_BIT)
+)
+
+// SelftestEval runs n (node, pod) cases through the device evaluators (ks_selftest_eval,
+// diagnostics): alloc and run hold 4 values per case, req 3, masks 4 (taint, label, tolerations,
+// selector), keymask 1.  It returns total1 (EvalTotalCols columns of n), tmax and live
+// (EvalPruneCols columns of n); only the columns whose bit `variants` sets are filled.  A batch
+// outside a requested evaluator's domain is InvalidArgument.
+func SelftestEval(device int, c EvalConfig, alloc, run, req []int64, keymask []uint32, masks []uint64,
+	variants uint32) (total1, tmax, live []uint32, err error) {
+	n := len(keymask)
+	if n == 0 || len(alloc) != 4*n || len(run) != 4*n || len(req) != 3*n || len(masks) != 4*n {
+		return nil, nil, nil, strongerrors.InvalidArgument(errors.New("SelftestEval: slice lengths"))
+	}
+	b := func(v bool) C.int32_t {
+		if v {
+			return 1
+		}
+		return 0
+	}
+	cc := C.ks_eval_cfg{filter_feeds: b(c.FeedsScore), filters: C.uint32_t(c.Filters), has_scorers: b(c.HasScorers),
+		w_lr: C.int32_t(c.WeightLR), w_ba: C.int32_t(c.WeightBA), const_total: C.int32_t(c.ConstTotal)}
+	total1 = make([]uint32, EvalTotalCols*n)
+	tmax = make([]uint32, EvalPruneCols*n)
+	live = make([]uint32, EvalPruneCols*n)
+	u32p := func(s []uint32) *C.uint32_t { return (*C.uint32_t)(unsafe.Pointer(&s[0])) }
+	rc := C.ks_selftest_eval(C.int32_t(device), &cc, C.int64_t(n), i64p(alloc), i64p(run), i64p(req),
+		u32p(keymask), u64p(masks), C.uint32_t(variants), u32p(total1), u32p(tmax), u32p(live))
+	if err = status(nil, rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return total1, tmax, live, nil
+}

@@ -367,8 +367,36 @@ ks_status ks_debug_watch(ks_engine* eng, int64_t pod);
 /* Device self-test of an evaluator identity the exactness argument rests on (no engine needed).
  * test 0: the micro evaluator's correction-free LeastRequested floor for every (x, A) with
  * 0 <= x <= A < 2^16 (ks_device.h).  *failures = mismatching cases (0 = pass). */
-enum { KS_SELFTEST_LR_MICRO = 0 };
+/* test 1: the whole micro evaluator and its scan form on every usage (uc, um) in [0, Ac + 2] x
+ * [0, Am + 2] of thirteen capacity pairs with Ac * Am < 2^24 (both domain edges, primes, multiples
+ * of ten, degenerate ones), filters off, three scorer configurations, against exact 64-bit integers. */
+enum { KS_SELFTEST_LR_MICRO = 0, KS_SELFTEST_MICRO_STATES = 1 };
 ks_status ks_selftest(int32_t device, int32_t test, int64_t* failures);
+/* Device batch of the fused Filter + Score evaluator (diagnostics / tests; no engine needed): case i is
+ * one node (alloc[i][4] cpu memory gpu pods, -1 absent; run[i][4] requested cpu memory gpu of the running
+ * pods and their count; masks[i][0..1] taint, label) and one pod (req[i][3], keymask[i], masks[i][2..3]
+ * tolerations, selector), all in device units, under the configuration cfg.  Bit b < 17 of `variants`
+ * asks for total1[b][n] (total + 1, 0 = not a candidate): b = 4 g + m is evaluator m (0 wide, 1 narrow,
+ * 2 tiny, 3 micro) on state form g (0 the 64-bit node, 1 the 12-word record, 2 the chunk resolver's
+ * 32-bit words, 3 the register resolver's entry), b = 16 the scan's form of the micro evaluator.  Bit
+ * 17 + j asks for tmax[j][n] and live[j][n], the resolvers' float upper bound of the total and whether
+ * any pod can make the node a candidate: j = 4 g + m with g = 0 the 64-bit node, 1 the 32-bit words,
+ * 2 the register entry.  Columns not asked for are left untouched.  KS_EINVAL when a value is out of
+ * the range ks_load_nodes / ks_submit_pods admit, a usage exceeds its capacity, or the batch leaves
+ * the domain of a requested evaluator (micro: capacities < 2^16, cpu * memory < 2^24, weights < 2^24;
+ * tiny: capacities and cpu * memory < 2^26; narrow: capacities < 2^29; 32-bit words: < 2^32 - 1). */
+typedef struct ks_eval_cfg {
+    int32_t filter_feeds;  /* 1: the filters gate the candidates (KS_FILTER_FEEDS_SCORE) */
+    uint32_t filters;      /* KS_FILTER_* bits */
+    int32_t has_scorers;
+    int32_t w_lr, w_ba;    /* summed LeastRequested / BalancedAllocation weights */
+    int32_t const_total;   /* sum of weight * value over the constant scorers */
+} ks_eval_cfg;
+enum { KS_EVAL_TOTAL_COLS = 17, KS_EVAL_PRUNE_COLS = 12, KS_EVAL_SCAN_MICRO = 16, KS_EVAL_PRUNE_BIT = 17,
+       KS_EVAL_MAX_CASES = 1 << 22 };
+ks_status ks_selftest_eval(int32_t device, const ks_eval_cfg* cfg, int64_t n, const int64_t* alloc,
+                           const int64_t* run, const int64_t* req, const uint32_t* keymask, const uint64_t* masks,
+                           uint32_t variants, uint32_t* total1, uint32_t* tmax, uint32_t* live);
 void ks_set_profiling(ks_engine* eng, int enable);
 /* Provenance: the first 16 hex digits of the SHA-256 of the sources the library was built from
  * (kubernetes-simulator_amd/csrc/Makefile HASHED, in that order); the Python binding refuses a

@@ -485,4 +485,31 @@ hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t*
     return hipGetLastError();
 }
 
+// ks_selftest_eval, the 12-word record's columns: each evaluator on put_rec12 -> get_rec12 of the
+// case's node, as merge_cl evaluates the E nodes' staged records
+namespace sq {
+template <int kMode>
+__device__ __forceinline__ void evtest_rec12_one(const EvalCases& e, int64_t i, const PodRec& p, const uint4 (&w)[3]) {
+    if (evcase_wants(e, 4 + kMode)) evcase_total(e, 4 + kMode, i, eval_t<kMode>(e.c, p, get_rec12(w)));
+}
+__global__ __launch_bounds__(256) void evtest_rec12_kernel(EvalCases e) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= e.n) return;
+    const PodRec p = evcase_pod(e, i);
+    alignas(16) uint32_t rec[12];
+    put_rec12(rec, evcase_node(e, i));
+    const uint4* r = reinterpret_cast<const uint4*>(rec);
+    const uint4 w[3] = {r[0], r[1], r[2]};
+    evtest_rec12_one<kEvalWide>(e, i, p, w);
+    evtest_rec12_one<kEvalNarrow>(e, i, p, w);
+    evtest_rec12_one<kEvalTiny>(e, i, p, w);
+    evtest_rec12_one<kEvalMicro>(e, i, p, w);
+}
+}  // namespace sq
+
+hipError_t launch_evtest_rec12(const EvalCases& e, hipStream_t st) {
+    hipLaunchKernelGGL(sq::evtest_rec12_kernel, dim3((unsigned)((e.n + 255) / 256)), dim3(256), 0, st, e);
+    return hipGetLastError();
+}
+
 }  // namespace ks

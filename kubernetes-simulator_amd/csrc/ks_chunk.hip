@@ -1428,4 +1428,33 @@ hipError_t launch_chunk_only(const EngineArgs* d, int mode, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ks_selftest_eval, the NS32 columns: eval32 and prune32 of every mode on the case's node held in
+// 32-bit words (the words of put_rec12, as store_prec reads them) — the wide mode through wide_node
+namespace chk {
+template <int kMode>
+__device__ __forceinline__ void evtest_ns32_one(const EvalCases& e, int64_t i, const PodRec& p, const NS32& n) {
+    if (evcase_wants(e, 8 + kMode)) evcase_total(e, 8 + kMode, i, eval32<kMode>(e.c, p, n));
+    if (evcase_wants(e, kEvPruneBit + 4 + kMode)) evcase_prune(e, 4 + kMode, i, p, prune32<kMode>(e.c, n));
+}
+__global__ __launch_bounds__(256) void evtest_ns32_kernel(EvalCases e) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= e.n) return;
+    const PodRec p = evcase_pod(e, i);
+    const NodeV v = evcase_node(e, i);
+    NS32 n;
+    n.ac = word32(v.ac); n.am = word32(v.am); n.ag = word32(v.ag); n.ap = clamp32(v.ap);
+    n.rc = word32(v.rc); n.rm = word32(v.rm); n.rg = word32(v.rg); n.nr = (int32_t)v.nr;
+    n.taint = v.taint; n.label = v.label;
+    evtest_ns32_one<kEvalWide>(e, i, p, n);
+    evtest_ns32_one<kEvalNarrow>(e, i, p, n);
+    evtest_ns32_one<kEvalTiny>(e, i, p, n);
+    evtest_ns32_one<kEvalMicro>(e, i, p, n);
+}
+}  // namespace chk
+
+hipError_t launch_evtest_ns32(const EvalCases& e, hipStream_t st) {
+    hipLaunchKernelGGL(chk::evtest_ns32_kernel, dim3((unsigned)((e.n + 255) / 256)), dim3(256), 0, st, e);
+    return hipGetLastError();
+}
+
 }  // namespace ks

@@ -326,8 +326,12 @@ __host__ __device__ __forceinline__ uint32_t eval_total1_tiny(const Cfg& c, cons
 // trunc(fma(x, r, 2^-17)) with r = 10 * rcp(A).  The fma's value is within 2.3e-6 of 10x/A + 2^-17
 // (v_rcp 1 ulp, two roundings, 10x/A <= 10).  At an integer k = 10x/A the bias (7.6e-6) keeps it
 // >= k; otherwise 10x/A <= k + 1 - 1/A and bias + error (9.9e-6) < 1/A (> 1.5e-5) keeps it < k + 1.
-// Checked on the device for every (x, A) pair (ks_selftest).  BalancedAllocation keeps the exact
-// correction step of the tiny evaluator.
+// Checked on the device for every (x, A) pair (ks_selftest test 0).  BalancedAllocation keeps the exact
+// correction step of the tiny evaluator.  The whole evaluator and its scan form are checked on the
+// device against exact 64-bit integers on every usage of thirteen capacity pairs (ks_selftest test 1),
+// and — with the wide, narrow and tiny evaluators, every node-state type the resolvers feed them and
+// the prune bound — on boundary-biased batches against Python integers (ks_selftest_eval,
+// tests/test_evaluator_device_gpu.py).
 // ---------------------------------------------------------------------------------------------
 constexpr int64_t kMicroCap = 1LL << 16;
 constexpr int64_t kMicroProd = 1LL << 24;
@@ -454,7 +458,8 @@ __host__ __device__ __forceinline__ uint32_t eval_total1_micro(const Cfg& c, con
 // work per (pod, wave) drops from ~38 to a handful of instructions (the scan issues on one scalar
 // unit per CU beside four SIMDs: C5 scan 0.31 -> 0.26 ms for the clamp and key tests alone), and
 // the filters combine as integers in VALU instead of as lane masks.  Results are those of
-// eval_total1_micro bit for bit (tests/test_evaluator_host.py):
+// eval_total1_micro bit for bit (tests/test_evaluator_host.py on the host build,
+// tests/test_evaluator_device_gpu.py and ks_selftest test 1 on the device):
 //   fit (node.go:44-47): every requested key k satisfies f_k = (A_k - r_k) - q_k >= 0 and
 //     nr < ap  <=>  min(f_c', f_m', f_g', npen) >= 0 with f_k' = (A_k - r_k) - qf_k, qf_k = q_k
 //     for a requested key and -2^30 otherwise (f_k' > 0: A_k - r_k >= -1 - 2^16), npen = -1 when
@@ -972,6 +977,57 @@ hipError_t launch_eval_pod(const Cfg& c, const NodeSoA& s, const PodRec* pod, ui
 hipError_t launch_flush(const NodeSoA& s, const PodRec* pods, const int64_t* fin, int64_t t, int64_t n_done,
                         const int32_t* b_node, const int32_t* b_status, uint8_t* expired, hipStream_t st);
 hipError_t launch_selftest_lr_micro(unsigned long long* bad, hipStream_t st);
+// every state of a fixed list of micro capacity pairs, eval_total1_micro and eval_scan_micro against
+// exact 64-bit integers (ks_selftest test 1)
+hipError_t launch_selftest_micro_states(unsigned long long* bad, hipStream_t st);
+
+// ks_selftest_eval: a batch of (node, pod) cases through every evaluator variant and state type.
+// Only this case layout is shared; each kernel lives in the translation unit that owns its state
+// type, so the checked code is the code the resolvers run.  Columns (include/ks_engine.h):
+//   total1[g * 4 + mode][n], g = 0 NodeV, 1 the 12-word record, 2 NS32, 3 conv(); total1[16] the scan form
+//   tmax / live[g * 4 + mode][n], g = 0 NodeV, 1 NS32 (prune32), 2 conv()
+constexpr int kEvTotalCols = 17, kEvPruneCols = 12, kEvScanCol = 16, kEvPruneBit = kEvTotalCols;
+struct EvalCases {
+    Cfg c;
+    int64_t n;
+    const int64_t* alloc;     // [n][4]
+    const int64_t* run;       // [n][4]: rc rm rg nr
+    const int64_t* req;       // [n][3]
+    const uint32_t* keymask;  // [n]
+    const uint64_t* masks;    // [n][4]: taint label tol sel
+    const ScanRec* scan;      // [n]: scan_rec_micro of case i's pod, built on the host (ks_submit_pods)
+    uint32_t variants, pad_;
+    uint32_t* total1;         // [kEvTotalCols][n]
+    uint32_t* tmax;           // [kEvPruneCols][n]
+    uint32_t* live;           // [kEvPruneCols][n]
+};
+__host__ __device__ __forceinline__ NodeV evcase_node(const EvalCases& e, int64_t i) {
+    NodeV v;
+    v.ac = e.alloc[i * 4 + 0]; v.am = e.alloc[i * 4 + 1]; v.ag = e.alloc[i * 4 + 2]; v.ap = e.alloc[i * 4 + 3];
+    v.rc = e.run[i * 4 + 0]; v.rm = e.run[i * 4 + 1]; v.rg = e.run[i * 4 + 2]; v.nr = e.run[i * 4 + 3];
+    v.taint = e.masks[i * 4 + 0]; v.label = e.masks[i * 4 + 1];
+    return v;
+}
+__host__ __device__ __forceinline__ PodRec evcase_pod(const EvalCases& e, int64_t i) {
+    PodRec p{};
+    p.req[0] = e.req[i * 3 + 0]; p.req[1] = e.req[i * 3 + 1]; p.req[2] = e.req[i * 3 + 2];
+    p.tol = e.masks[i * 4 + 2]; p.sel = e.masks[i * 4 + 3];
+    p.keymask = e.keymask[i];
+    return p;
+}
+__device__ __forceinline__ bool evcase_wants(const EvalCases& e, int bit) { return (e.variants >> bit) & 1u; }
+__device__ __forceinline__ void evcase_total(const EvalCases& e, int col, int64_t i, uint32_t t1) {
+    e.total1[(int64_t)col * e.n + i] = t1;
+}
+// the bound as the resolvers take it: the request floats are (float)p.req[k], unclamped
+__device__ __forceinline__ void evcase_prune(const EvalCases& e, int col, int64_t i, const PodRec& p, const PruneF& f) {
+    e.tmax[(int64_t)col * e.n + i] = prune_tmax(e.c, f, (float)p.req[0], (float)p.req[1]);
+    e.live[(int64_t)col * e.n + i] = (uint32_t)f.live;
+}
+hipError_t launch_evtest_nodev(const EvalCases& e, hipStream_t st);  // ks_kernels.hip
+hipError_t launch_evtest_rec12(const EvalCases& e, hipStream_t st);  // ks_cand.hip
+hipError_t launch_evtest_ns32(const EvalCases& e, hipStream_t st);   // ks_chunk.hip
+hipError_t launch_evtest_conv(const EvalCases& e, hipStream_t st);   // ks_resolve.hip
 // usage queries: grids of candidate pod blocks of usage_block_pods() pods each (pods < q_hi)
 int usage_block_pods();
 hipError_t launch_usage(const int32_t* blocks, int64_t nblocks, int64_t q_hi, int64_t t, int32_t tick_s,

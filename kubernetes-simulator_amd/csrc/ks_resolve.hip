@@ -534,10 +534,36 @@ void launch_t(const EngineArgs* d, int S, int mode, hipStream_t st) {
     }
 }
 
+// ks_selftest_eval, the register-entry columns: conv() of the case's node into the mode's entry type
+// (NodeS32, NodeM with its cached invariants, NodeV), then eval_t and the bound prepared from the
+// entry (prune_prep), as the resolver's owner lanes do
+template <int kMode>
+__device__ __forceinline__ void evtest_conv_one(const EvalCases& e, int64_t i, const PodRec& p, const NodeV& v) {
+    typename NodeSel<kMode>::T n;
+    conv(v, n);
+    if (evcase_wants(e, 12 + kMode)) evcase_total(e, 12 + kMode, i, eval_t<kMode>(e.c, p, n));
+    if (evcase_wants(e, kEvPruneBit + 8 + kMode)) evcase_prune(e, 8 + kMode, i, p, prune_prep(e.c, n));
+}
+__global__ __launch_bounds__(256) void evtest_conv_kernel(EvalCases e) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= e.n) return;
+    const PodRec p = evcase_pod(e, i);
+    const NodeV v = evcase_node(e, i);
+    evtest_conv_one<kEvalWide>(e, i, p, v);
+    evtest_conv_one<kEvalNarrow>(e, i, p, v);
+    evtest_conv_one<kEvalTiny>(e, i, p, v);
+    evtest_conv_one<kEvalMicro>(e, i, p, v);
+}
+
 }  // namespace
 
 hipError_t launch_resolve_small(const EngineArgs* d, int S, int mode, hipStream_t st) {
     launch_t<RSmall>(d, S, mode, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_evtest_conv(const EvalCases& e, hipStream_t st) {
+    hipLaunchKernelGGL(evtest_conv_kernel, dim3((unsigned)((e.n + 255) / 256)), dim3(256), 0, st, e);
     return hipGetLastError();
 }
 

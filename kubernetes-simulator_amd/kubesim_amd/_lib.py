@@ -33,6 +33,13 @@ KS_CHR = 20           # csrc/ks_device.h kChR: static candidates kept per pod
 KS_SLOT_MAX = 1536    # csrc/ks_device.h kSlotMax: candidate slots whose record merge_cl stages
 KS_CHUNK_CIDS = 1024  # csrc/ks_chunk.hip kCid: candidates the chunk kernel numbers per batch
 KS_SELFTEST_LR_MICRO = 0
+KS_SELFTEST_MICRO_STATES = 1
+# ks_selftest_eval (include/ks_engine.h): total1 column 4 * form + mode, tmax / live column 4 * form + mode
+KS_EVAL_TOTAL_COLS = 17
+KS_EVAL_PRUNE_COLS = 12
+KS_EVAL_SCAN_MICRO = 16
+KS_EVAL_PRUNE_BIT = 17
+KS_EVAL_MAX_CASES = 1 << 22
 KS_SERIES_COLS = 7  # ks_cluster_series: running, requested cpu / memory / gpu, bound Ok, bound OverCapacity, pending
 
 STATUS_NAMES = {KS_OK: "OK", KS_EINVAL: "InvalidArgument", KS_ENOTFOUND: "NotFound",
@@ -41,7 +48,7 @@ STATUS_NAMES = {KS_OK: "OK", KS_EINVAL: "InvalidArgument", KS_ENOTFOUND: "NotFou
 # every symbol include/*.h declares
 EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods", "ks_step",
                     "ks_filter", "ks_score", "ks_usage", "ks_current_tick", "ks_tick_seconds", "ks_queued_pods",
-                    "ks_last_error", "ks_last_step_stats", "ks_last_step_kernels", "ks_set_profiling", "ks_debug_counters", "ks_debug_invariants", "ks_debug_window", "ks_debug_watch", "ks_build_id", "ks_selftest",
+                    "ks_last_error", "ks_last_step_stats", "ks_last_step_kernels", "ks_set_profiling", "ks_debug_counters", "ks_debug_invariants", "ks_debug_window", "ks_debug_watch", "ks_build_id", "ks_selftest", "ks_selftest_eval",
                     "ks_comm_unique_id", "ks_shard", "ks_shard_host", "ks_group_create", "ks_group_destroy",
                     "ks_group_add", "ks_group_size", "ks_group_step", "ks_pod_status",
                     "ks_usage_at", "ks_usage_digest", "ks_node_mix", "ks_pod_lookup", "ks_node_pods",
@@ -68,6 +75,11 @@ class KsConfig(C.Structure):
                 ("filters", C.c_uint32), ("n_scorers", C.c_int32), ("scorers", KsScorer * 8),
                 ("device", C.c_int32), ("batch_pods", C.c_int32), ("engine_flags", C.c_uint32),
                 ("reserved", C.c_int32 * 7)]
+
+
+class KsEvalCfg(C.Structure):
+    _fields_ = [("filter_feeds", C.c_int32), ("filters", C.c_uint32), ("has_scorers", C.c_int32),
+                ("w_lr", C.c_int32), ("w_ba", C.c_int32), ("const_total", C.c_int32)]
 
 
 class KsBind(C.Structure):
@@ -231,6 +243,8 @@ def load():
     L.ks_set_profiling.restype = None
     L.ks_selftest.argtypes = [C.c_int32, C.c_int32, p]
     L.ks_selftest.restype = C.c_int
+    L.ks_selftest_eval.argtypes = [C.c_int32, C.POINTER(KsEvalCfg), C.c_int64, p, p, p, p, p, C.c_uint32, p, p, p]
+    L.ks_selftest_eval.restype = C.c_int
     L.ks_comm_unique_id.argtypes = [p]
     L.ks_comm_unique_id.restype = C.c_int
     L.ks_shard.argtypes = [p, C.c_int32, C.c_int32, p, C.c_int32]

@@ -325,6 +325,30 @@ def selftest(test: int = _lib.KS_SELFTEST_LR_MICRO, device: int = 0) -> int:
     return n.value
 
 
+def selftest_eval(cfg: dict, alloc, run, req, keymask, masks, variants: int, device: int = 0):
+    """One (node, pod) case per row through the device evaluators (include/ks_engine.h,
+    ks_selftest_eval).  cfg: filter_feeds, filters, has_scorers, w_lr, w_ba, const_total.
+    Returns (total1 [KS_EVAL_TOTAL_COLS][n], tmax [KS_EVAL_PRUNE_COLS][n], live [same]) as uint32;
+    only the columns whose bit `variants` sets are filled.  A batch outside a requested evaluator's
+    domain raises KsError(KS_EINVAL)."""
+    L = _lib.load()
+    alloc, run, req = _c(alloc, np.int64), _c(run, np.int64), _c(req, np.int64)
+    keymask, masks = _c(keymask, np.uint32), _c(masks, np.uint64)
+    n = len(keymask)
+    if alloc.shape != (n, 4) or run.shape != (n, 4) or req.shape != (n, 3) or masks.shape != (n, 4):
+        raise ValueError("selftest_eval: alloc[n][4], run[n][4], req[n][3], keymask[n], masks[n][4]")
+    c = _lib.KsEvalCfg(**{k: int(cfg[k]) for k in ("filter_feeds", "filters", "has_scorers", "w_lr", "w_ba",
+                                                   "const_total")})
+    total1 = np.zeros((_lib.KS_EVAL_TOTAL_COLS, n), np.uint32)
+    tmax = np.zeros((_lib.KS_EVAL_PRUNE_COLS, n), np.uint32)
+    live = np.zeros((_lib.KS_EVAL_PRUNE_COLS, n), np.uint32)
+    rc = L.ks_selftest_eval(device, C.byref(c), n, _p(alloc), _p(run), _p(req), _p(keymask), _p(masks),
+                            int(variants), _p(total1), _p(tmax), _p(live))
+    if rc != 0:
+        raise KsError(rc, "ks_selftest_eval failed")
+    return total1, tmax, live
+
+
 class LocalExchange:
     """An in-process all-gather for ``world`` engines sharded with :meth:`Engine.shard_host`
     (ks_local_allgather, include/ks_kubesim.h)."""

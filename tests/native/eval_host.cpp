@@ -85,3 +85,36 @@ extern "C" void ks_host_scan_micro_batch(const ks::Cfg* c, int64_t n, const int6
         total1_s[i] = ks::eval_scan_micro(*c, ks::scan_rec_micro(*c, p), v, ks::scan_npen(*c, v));
     }
 }
+// the host counterpart of ks_selftest_eval's 64-bit-node columns (tests/evaluator_cases.py): per case
+// total1[m][n] of evaluator m = 0 wide, 1 narrow, 2 tiny, 3 micro, total1[4][n] of the scan's form,
+// and tmax / live[m][n] of the prune bound prepared by prune_prep (m = 0) / prune_prep_t<m>; only the
+// columns whose bit `variants` sets (bit m, bit 4, bit 5 + m) — the caller keeps each evaluator inside
+// its domain
+extern "C" void ks_host_eval_batch(const ks::Cfg* c, int64_t n, const int64_t* alloc /*[n][4]*/,
+                                   const int64_t* run /*[n][4]: rc rm rg nr*/, const int64_t* req /*[n][3]*/,
+                                   const uint32_t* keymask, const uint64_t* masks /*[n][4]: taint label tol sel*/,
+                                   uint32_t variants, uint32_t* total1, uint32_t* tmax, uint32_t* live) {
+    ks::EvalCases e{};
+    e.c = *c; e.n = n;
+    e.alloc = alloc; e.run = run; e.req = req; e.keymask = keymask; e.masks = masks;
+    auto want = [&](int b) { return (variants >> b) & 1u; };
+    for (int64_t i = 0; i < n; i++) {
+        const ks::NodeV v = ks::evcase_node(e, i);
+        const ks::PodRec p = ks::evcase_pod(e, i);
+        if (want(0)) total1[0 * n + i] = ks::eval_t<ks::kEvalWide>(*c, p, v);
+        if (want(1)) total1[1 * n + i] = ks::eval_t<ks::kEvalNarrow>(*c, p, v);
+        if (want(2)) total1[2 * n + i] = ks::eval_t<ks::kEvalTiny>(*c, p, v);
+        if (want(3)) total1[3 * n + i] = ks::eval_t<ks::kEvalMicro>(*c, p, v);
+        if (want(4)) total1[4 * n + i] = ks::eval_scan_micro(*c, ks::scan_rec_micro(*c, p), v, ks::scan_npen(*c, v));
+        ks::PruneF f[4];
+        f[0] = ks::prune_prep(*c, v);
+        if (want(6)) f[1] = ks::prune_prep_t<ks::kEvalNarrow>(*c, v);
+        if (want(7)) f[2] = ks::prune_prep_t<ks::kEvalTiny>(*c, v);
+        if (want(8)) f[3] = ks::prune_prep_t<ks::kEvalMicro>(*c, v);
+        for (int m = 0; m < 4; m++) {
+            if (!want(5 + m)) continue;
+            tmax[m * n + i] = ks::prune_tmax(*c, f[m], (float)p.req[0], (float)p.req[1]);
+            live[m * n + i] = (uint32_t)f[m].live;
+        }
+    }
+}
