@@ -366,6 +366,72 @@ func (e *Engine) NodePeaks(tLo, tHi int64) ([]int64, error) {
 	return r[:4*e.n], status(e, C.ks_node_peaks(e.h, C.int64_t(tLo), C.int64_t(tHi), i64p(r)))
 }
 
+// Headroom constants (include/ks_engine.h): the columns of HeadroomAt per shape (Σ over nodes of the
+// count, nodes with a count >= 1, the largest count, its lowest node or -1, eligible nodes limited by
+// cpu / memory / gpu / pods, ineligible nodes), the most shapes per call, the per-node clamp.
+const (
+	HeadroomCols      = 9
+	HeadroomMaxShapes = 64
+	HeadroomNodeMax   = 2147483647
+)
+
+// Shapes are pod templates for the headroom queries, in SubmitPods' fields and units: nothing is
+// appended to the FIFO and no engine state changes.
+type Shapes struct {
+	Req      []int64 // 3 per shape, milli-units
+	KeyMask  []uint8 // request keys present: 1 cpu, 2 memory, 4 gpu
+	Tol, Sel []uint64
+}
+
+func (s *Shapes) count() (int, error) {
+	k := len(s.KeyMask)
+	if k < 1 || k > HeadroomMaxShapes || len(s.Req) != 3*k || len(s.Tol) != k || len(s.Sel) != k {
+		return 0, strongerrors.InvalidArgument(errors.New("headroom: 1..64 shapes with consistent array lengths"))
+	}
+	return k, nil
+}
+
+// HeadroomAt is, per shape, how many more pods of it the cluster would take at tick t <= Tick():
+// Node.CreatePod's admission test (kubesim/node/node.go:44-47) applied repeatedly on every node
+// against RequestedAt(t) (ks_headroom_at).  Returns HeadroomCols values per shape and, with
+// perNode, the per-node counts (Nodes() per shape).
+func (e *Engine) HeadroomAt(t int64, s *Shapes, perNode bool) ([]int64, []int32, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	k, err := s.count()
+	if err != nil {
+		return nil, nil, err
+	}
+	out := make([]int64, k*HeadroomCols)
+	var pn []int32
+	if perNode {
+		pn = make([]int32, k*e.n+1)
+	}
+	err = status(e, C.ks_headroom_at(e.h, C.int64_t(t), C.int32_t(k), i64p(s.Req), u8p(s.KeyMask), u64p(s.Tol),
+		u64p(s.Sel), i64p(out), i32p(pn)))
+	if perNode {
+		pn = pn[:k*e.n]
+	}
+	return out, pn, err
+}
+
+// HeadroomSeries is columns 0 and 1 of HeadroomAt (Σ over nodes of the count, nodes with room) for
+// every tick tLo <= t < tHi: 2 values per shape per tick (ks_headroom_series; window bounds as
+// ClusterSeries, and at most 2^22 shape-ticks).
+func (e *Engine) HeadroomSeries(tLo, tHi int64, s *Shapes) ([]int64, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	k, err := s.count()
+	if err != nil {
+		return nil, err
+	}
+	n := 0
+	if tHi > tLo && int64(k)*(tHi-tLo) <= 1<<22 { // (a longer window is rejected by the call: nothing to hold)
+		n = int(tHi-tLo) * k * 2
+	}
+	out := make([]int64, n+1)
+	return out[:n], status(e, C.ks_headroom_series(e.h, C.int64_t(tLo), C.int64_t(tHi), C.int32_t(k), i64p(s.Req),
+		u8p(s.KeyMask), u64p(s.Tol), u64p(s.Sel), i64p(out)))
+}
+
 // Nodes is the node count of LoadNodes.
 func (e *Engine) Nodes() int { return e.n }
 

@@ -25,6 +25,8 @@
  *   ks_filter_at / ks_score_at .. the filtered nodes and nodeScore map scheduleOne logs per pod
  *                                 (kubesim/kubesim.go:170,184,194,205), for a pod already bound
  *   ks_cluster_series ........... running / requested / bound / failed / queued curves per tick
+ *   ks_headroom_at / _series .... Node.CreatePod's admission test (kubesim/node/node.go:44-47) applied
+ *                                 repeatedly: how many more pods of a shape each node would take
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
  *   ks_pod_lookup / ks_node_pods  Node.GetPod / GetPodStatus / GetPodList (kubesim/node/node.go:62-93)
  *   ks_group_* .................. one KubeSim.Run per what-if scenario, stepped together
@@ -278,6 +280,56 @@ ks_status ks_cluster_series(ks_engine* eng, int64_t t_lo, int64_t t_hi, int64_t*
  * Node.totalResourceRequest / runningPodsNum (kubesim/node/node.go:97-118) over every tick of the
  * window would find.  Extra cost: per node, the square of its pods that run in the window. */
 ks_status ks_node_peaks(ks_engine* eng, int64_t t_lo, int64_t t_hi, int64_t* out);
+
+/* Headroom: how many more pods of a shape fit, at any past tick ("at tick t" as above: after tick
+ * t's bind, 0 <= t <= the current tick).  A shape is a pod template in ks_submit_pods' fields and
+ * units: req[3] (cpu, memory, nvidia.com/gpu; int64 milli-units), keymask (1 cpu, 2 memory, 4 gpu),
+ * tol and sel masks.  Shapes are never appended to the FIFO and change no engine state (no unit
+ * rescale: a request need not be a multiple of anything the engine holds).
+ *
+ * The count c(node, shape) is the number of copies of the shape Node.CreatePod would give status Ok
+ * when handed them one after another at tick t with nothing finishing in between — its admission
+ * test (kubesim/node/node.go:44-47) against Node.totalResourceRequest / runningPodsNum
+ * (node.go:97-118, ks_requested_at(t)), applied repeatedly.  In closed form, with A the node's
+ * alloc, r its requested state at t and q the shape's request, as exact integers:
+ *   per key k in keymask: 0 if the node lacks the key (alloc -1; also for a request of 0,
+ *     kubesim/node/resource.go:54-55); no bound if q[k] = 0; else floor((A[k] - r[k]) / q[k]);
+ *   pods: max(alloc pods - running pods, 0) (runningPodsNum >= cap.Pods(), node.go:47);
+ *   every bound is clamped to KS_HEADROOM_NODE_MAX = 2^31 - 1 (per-node counts stay int32, every
+ *   sum stays inside int64) and c is the minimum of the bounds.
+ * The limiting key is the first bound, in the order cpu, memory, gpu, pods, that attains the minimum
+ * (a key without a bound never limits; at the clamp it is the first bound that reaches the clamp).
+ * Every eligible node has exactly one limiting key, also when c = 0.  The admission test always
+ * applies, whatever filters are registered.  A node is eligible for a shape unless the engine runs
+ * KS_FILTER_FEEDS_SCORE with KS_FILTER_TAINT and / or KS_FILTER_SELECTOR and the shape fails that
+ * predicate on it ((taint & ~tol) == 0, (label & sel) == sel: toleration.go:37-56 and the
+ * nodeSelector match, as ks_filter); in KS_FILTER_REFERENCE_LITERAL mode every node is eligible
+ * (kubesim/kubesim.go:182 discards the Filter result).  An ineligible node has c = 0 and no
+ * limiting key.
+ *
+ * ks_headroom_at: out[k][KS_HEADROOM_COLS] per shape: 0 = sum over nodes of c; 1 = nodes with
+ * c >= 1; 2 = the largest c; 3 = the lowest node index attaining column 2, or -1 when column 2 is 0;
+ * 4..7 = eligible nodes whose limiting key is cpu / memory / gpu / pods; 8 = ineligible nodes
+ * (columns 4..8 sum to n).  per_node_out (may be NULL): [k][n] the counts.  With n = 0: KS_OK,
+ * zeros and column 3 = -1.
+ * ks_headroom_series: out[t_hi - t_lo][k][2] = columns 0 and 1 of ks_headroom_at at every tick
+ * t_lo <= t < t_hi (window bounds as ks_cluster_series; also k * (t_hi - t_lo) <= 2^22).  Cost: the
+ * pods that run in the window (per node, the square of them, as ks_node_peaks) times k — not one
+ * pass over the cluster per tick.
+ * KS_EINVAL: a NULL engine, req, keymask, tol, sel or out (before the handle is read); k outside
+ * 1..KS_HEADROOM_MAX_SHAPES; a keymask bit above 4; a request that is negative or >= 2^59 in a
+ * masked key (unmasked keys are ignored); t or the window out of range; no nodes loaded.  Both
+ * answer after an aborted run, on sharded engines and on scenario-group members, like the state
+ * queries above. */
+#define KS_HEADROOM_COLS 9
+#define KS_HEADROOM_MAX_SHAPES 64
+#define KS_HEADROOM_NODE_MAX 2147483647
+ks_status ks_headroom_at(ks_engine* eng, int64_t t, int32_t k, const int64_t* req /* [k][3] */,
+                         const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel,
+                         int64_t* out /* [k][KS_HEADROOM_COLS] */, int32_t* per_node_out /* [k][n] or NULL */);
+ks_status ks_headroom_series(ks_engine* eng, int64_t t_lo, int64_t t_hi, int32_t k, const int64_t* req,
+                             const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel,
+                             int64_t* out /* [t_hi - t_lo][k][2] */);
 
 /* Name-keyed queries over the binds made so far (Node.GetPod / GetPodStatus / GetPodList,
  * kubesim/node/node.go:62-93).  ks_pod_lookup: the FIFO index of the pod stored on `node` under

@@ -1063,4 +1063,105 @@ hipError_t launch_node_peaks(const int32_t* blocks, int64_t nblocks, int64_t q_h
                              const PodRec* pods, const QScale& sc, int32_t* cnt, int32_t* off, int32_t* cur,
                              int32_t* list, int32_t list_cap, long long* out, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------
+// Headroom (ks_headroom_at / ks_headroom_series): how many copies of a pod shape Node.CreatePod
+// (kubesim/node/node.go:44-47) would admit one after another on a node, nothing finishing in
+// between.  Per masked key the bound is 0 on a node that lacks the key (even for a request of 0,
+// kubesim/node/resource.go:54-55), none for a request of 0, else floor((A - r) / q); the pods
+// bound is max(ap - nr, 0) (runningPodsNum >= cap.Pods(), node.go:47).  Every bound is clamped to
+// kHeadMax, the count is their minimum and the limiting key the first bound, in the order cpu,
+// memory, gpu, pods, that attains it (so at the clamp: the first bound that reaches the clamp).
+//
+// The node is in device units (alloc -1 absent; rc rm rg nr the rebuilt state), sc the milli-units
+// per device unit, the shape's requests in milli-units and not necessarily multiples of sc: the
+// numerator (A - r) * sc is the free amount in milli-units, < 2^59 like every admitted quantity.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kHeadMax = 2147483647;        // KS_HEADROOM_NODE_MAX
+constexpr uint64_t kHeadFloat = 1ull << 22;     // numerators below it: float estimate
+constexpr uint64_t kHeadDouble = 1ull << 53;    // numerators below it: double estimate
+constexpr uint64_t kHeadClampQ = 1ull << 28;    // requests at or above it never reach the clamp (q * kHeadMax >= 2^59)
+constexpr int64_t kHeadReqMax = 1LL << 59;      // a masked request is 0 <= q < 2^59
+
+// min(floor(num / q), kHeadMax) for q >= 1, num < 2^59.  gfx950 has no 64-bit divide: an estimate
+// from the float (num < 2^22: error < 1) or double (num < 2^53, one Newton step on the reciprocal)
+// pipe, one exact step either way, and the result is proved (t <= num < t + q) before it is
+// returned; anything else takes the compiler's exact 64-bit division.
+__host__ __device__ __forceinline__ int64_t head_div(uint64_t num, uint64_t q) {
+    if (num < q) return 0;
+    if (q < kHeadClampQ && num >= q * (uint64_t)kHeadMax) return kHeadMax;  // early clamp: the quotient is < 2^31 below
+    uint64_t c;
+    if (num < kHeadFloat) {
+        c = (uint64_t)(uint32_t)((float)(uint32_t)num * rcp_est((float)(uint32_t)q));
+    } else if (num < kHeadDouble) {
+        const double d = (double)q;
+        double y = rcp_est(d);
+        y = __builtin_fma(__builtin_fma(-d, y, 1.0), y, y);
+        const double est = (double)num * y;
+        c = est > 0.0 ? (uint64_t)est : 0ull;
+    } else {
+        return (int64_t)(num / q);
+    }
+    // a sane estimate has c q ~ num < 2^53; one whose product could leave 64 bits is not used
+    if (bitlen(c) + bitlen(q) > 62) return (int64_t)(num / q);
+    uint64_t t = c * q;
+    if (t > num) { c -= 1; t -= q; }
+    else if (num - t >= q) { c += 1; t += q; }
+    if (t <= num && num - t < q) return (int64_t)c;
+    return (int64_t)(num / q);
+}
+
+// one key's bound: -1 = none (the key is not masked, or its request is 0 on a node that has it)
+__host__ __device__ __forceinline__ int64_t head_key_bound(bool masked, int64_t A, int64_t r, int64_t sc, int64_t q) {
+    if (!masked) return -1;
+    if (A < 0) return 0;
+    if (q == 0) return -1;
+    return A > r ? head_div((uint64_t)(A - r) * (uint64_t)sc, (uint64_t)q) : 0;
+}
+
+// The count (0..kHeadMax) and, in *key, the limiting key (0 cpu, 1 memory, 2 gpu, 3 pods).  Taints
+// and selectors are the caller's (head_eligible): an ineligible node has count 0 and no key.
+__host__ __device__ __forceinline__ int32_t headroom_count(const NodeV& n, const QScale& sc, const PodRec& shape,
+                                                           int32_t* key) {
+    const int64_t free_pods = n.ap - n.nr;
+    int64_t c = free_pods > 0 ? (free_pods < kHeadMax ? free_pods : kHeadMax) : 0;
+    int32_t lim = 3;
+    // gpu, memory, cpu: a tie goes to the key that comes first
+    const int64_t bg = head_key_bound(shape.keymask & 4, n.ag, n.rg, sc.f[2], shape.req[2]);
+    if (bg >= 0 && bg <= c) { c = bg; lim = 2; }
+    const int64_t bm = head_key_bound(shape.keymask & 2, n.am, n.rm, sc.f[1], shape.req[1]);
+    if (bm >= 0 && bm <= c) { c = bm; lim = 1; }
+    const int64_t bc = head_key_bound(shape.keymask & 1, n.ac, n.rc, sc.f[0], shape.req[0]);
+    if (bc >= 0 && bc <= c) { c = bc; lim = 0; }
+    *key = lim;
+    return (int32_t)c;
+}
+
+// eligibility of a node for a shape: the taint / selector predicates of the fused evaluator
+// (eval_total1), applied only when the engine's filters gate the candidates
+__host__ __device__ __forceinline__ bool head_eligible(int32_t filter_feeds, uint32_t filters, const NodeV& n,
+                                                       const PodRec& shape) {
+    if (!filter_feeds) return true;
+    bool ok = true;
+    if (filters & kFilterTaint) ok &= (n.taint & ~shape.tol) == 0;
+    if (filters & kFilterSelector) ok &= (n.label & shape.sel) == shape.sel;
+    return ok;
+}
+
+constexpr int kHeadCols = 9;        // KS_HEADROOM_COLS
+constexpr int kHeadMaxShapes = 64;  // KS_HEADROOM_MAX_SHAPES (= one wave: the series gives a lane to each shape)
+// state: rc rm rg nr at t in device units, [4][n_pad] (launch_requested with unit scale, strides (1, n_pad));
+// shapes[k]: requests in milli-units; part: [ceil(n / 256)][k][3] scratch; out: [k][kHeadCols];
+// per_node: [k][n_nodes] or null
+hipError_t launch_headroom(const NodeSoA& s, const int64_t* state, int64_t n_pad, int32_t n_nodes, int32_t filter_feeds,
+                           uint32_t filters, const QScale& sc, const PodRec* shapes, int32_t k,
+                           unsigned long long* part, long long* out, int32_t* per_node, hipStream_t st);
+// cnt / off / cur / list: launch_node_peaks' counting sort scratch; diff: [2 k][t_hi - t_lo + 1] zeroed;
+// out: [t_hi - t_lo][k][2]
+hipError_t launch_headroom_series(const int32_t* blocks, int64_t nblocks, int64_t q_hi, int64_t t_lo, int64_t t_hi,
+                                  const NodeSoA& s, int32_t n_nodes, int32_t filter_feeds, uint32_t filters,
+                                  const QScale& sc, const PodRec* shapes, int32_t k, const int32_t* b_node,
+                                  const int32_t* b_status, const int64_t* t0, const int32_t* dur, const PodRec* pods,
+                                  int32_t* cnt, int32_t* off, int32_t* cur, int32_t* list, int32_t list_cap,
+                                  unsigned long long* diff, unsigned long long* out, hipStream_t st);
+
 }  // namespace ks

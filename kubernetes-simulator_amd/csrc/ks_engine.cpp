@@ -262,6 +262,7 @@ struct ks_engine {
     int64_t cum_upto = 0;
     DVec<unsigned long long> d_qs;
     DVec<int32_t> d_qi;
+    std::vector<ks::PodRec> h_shapes;  // ks_headroom_*: the call's shape records (requests in milli-units)
 };
 
 namespace {
@@ -2141,6 +2142,117 @@ ks_status ks_node_peaks(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) 
                                     e->dur.p, e->pods.p, milli_scale(e), cnt, off, cur, list, (int32_t)cap,
                                     (long long*)e->d_qs.p, e->st));
     HIPCHK(e, hipMemcpyAsync(out, e->d_qs.p, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// ---- headroom queries (ks_query.hip) -----------------------------------------------------------
+// How many more pods of a shape Node.CreatePod (kubesim/node/node.go:44-47) would admit per node at a
+// past tick: the rebuilt rc rm rg nr against the cluster's alloc / taints / labels.  Shapes live only
+// for the call: nothing is appended, rescaled or written back (their requests stay in milli-units,
+// the device multiplies the free amount by e->scale instead of dividing the request).
+static_assert(KS_HEADROOM_COLS == ks::kHeadCols && KS_HEADROOM_MAX_SHAPES == ks::kHeadMaxShapes &&
+              KS_HEADROOM_NODE_MAX == ks::kHeadMax, "ks_headroom_* constants");
+constexpr int64_t kMaxHeadSeries = 1LL << 22;  // k * (t_hi - t_lo) at the most
+
+static ks_status head_shapes(ks_engine* e, int32_t k, const int64_t* req, const uint8_t* keymask, const uint64_t* tol,
+                             const uint64_t* sel) {
+    if (k < 1 || k > KS_HEADROOM_MAX_SHAPES)
+        return fail(e, KS_EINVAL, "headroom: %d shapes outside [1, %d]", (int)k, KS_HEADROOM_MAX_SHAPES);
+    e->h_shapes.assign(k, ks::PodRec{});
+    for (int32_t j = 0; j < k; j++) {
+        if (keymask[j] & ~7u) return fail(e, KS_EINVAL, "headroom shape %d: keymask %u has bits above 4", (int)j, (unsigned)keymask[j]);
+        ks::PodRec& r = e->h_shapes[j];
+        for (int c = 0; c < 3; c++) {
+            if (!(keymask[j] >> c & 1)) continue;  // unmasked keys are ignored
+            const int64_t q = req[j * 3 + c];
+            if (q < 0 || q >= ks::kHeadReqMax) return fail(e, KS_EINVAL, "headroom shape %d: request %d out of range", (int)j, c);
+            r.req[c] = q;
+        }
+        r.tol = tol[j];
+        r.sel = sel[j];
+        r.keymask = keymask[j];
+    }
+    return KS_OK;
+}
+
+ks_status ks_headroom_at(ks_engine* e, int64_t t, int32_t k, const int64_t* req, const uint8_t* keymask,
+                         const uint64_t* tol, const uint64_t* sel, int64_t* out, int32_t* per_node_out) {
+    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, k, req, keymask, tol, sel); r != KS_OK) return r;
+    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
+    if (e->n == 0) {
+        for (int32_t j = 0; j < k; j++)
+            for (int c = 0; c < KS_HEADROOM_COLS; c++) out[j * KS_HEADROOM_COLS + c] = c == 3 ? -1 : 0;
+        return KS_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t q_hi = bound_by(e, t);
+    const int64_t nb = usage_blocks(e, t, q_hi);
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long);
+    HIPCHK(e, e->d_qs.reserve(4 * np + W * k + nblk * k * 3 + (int64_t)k * KS_HEADROOM_COLS, e->st));
+    if (per_node_out) HIPCHK(e, e->d_qi.reserve((int64_t)k * n, e->st));
+    unsigned long long* state = e->d_qs.p;                 // [4][np]: rc rm rg nr at t, device units
+    ks::PodRec* shapes = (ks::PodRec*)(state + 4 * np);    // [k]
+    unsigned long long* part = state + 4 * np + W * k;     // [nblk][k][3]
+    long long* res = (long long*)(part + nblk * k * 3);    // [k][KS_HEADROOM_COLS]
+    HIPCHK(e, hipMemsetAsync(state, 0, sizeof(unsigned long long) * 4 * np, e->st));
+    HIPCHK(e, hipMemcpyAsync(shapes, e->h_shapes.data(), sizeof(ks::PodRec) * k, hipMemcpyHostToDevice, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
+                                   e->pods.p, ks::QScale{{1, 1, 1}}, 1, np, state, e->st));
+    HIPCHK(e, ks::launch_headroom(e->s, (const int64_t*)state, np, (int32_t)n, e->dc.filter_feeds, e->cfg.filters,
+                                  milli_scale(e), shapes, k, part, res, per_node_out ? e->d_qi.p : nullptr, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * k * KS_HEADROOM_COLS, hipMemcpyDeviceToHost, e->st));
+    if (per_node_out)
+        HIPCHK(e, hipMemcpyAsync(per_node_out, e->d_qi.p, sizeof(int32_t) * k * n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+ks_status ks_headroom_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int32_t k, const int64_t* req,
+                             const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel, int64_t* out) {
+    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, k, req, keymask, tol, sel); r != KS_OK) return r;
+    if (ks_status r = check_window(e, "headroom", t_lo, t_hi); r != KS_OK) return r;
+    const int64_t T = t_hi - t_lo, C2 = 2 * (int64_t)k;
+    if (k * T > kMaxHeadSeries)
+        return fail(e, KS_EINVAL, "headroom series: %d shapes x %lld ticks is more than %lld", (int)k, (long long)T,
+                    (long long)kMaxHeadSeries);
+    if (e->n == 0) {
+        std::fill(out, out + C2 * T, (int64_t)0);
+        return KS_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t q_hi = bound_by(e, t_hi - 1);
+    const int64_t nb = usage_blocks(e, t_lo, q_hi);
+    const int64_t n = e->n, cap = nb * kUBlk;
+    if (cap > INT32_MAX) return fail(e, KS_EINVAL, "headroom window holds too many candidate pods");
+    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long);
+    HIPCHK(e, e->d_qs.reserve(C2 * (T + 1) + C2 * T + W * k, e->st));
+    HIPCHK(e, e->d_qi.reserve(3 * n + 1 + cap, e->st));
+    unsigned long long* diff = e->d_qs.p;                            // [2 k][T + 1]
+    unsigned long long* res = diff + C2 * (T + 1);                   // [T][k][2]
+    ks::PodRec* shapes = (ks::PodRec*)(res + C2 * T);                // [k] (an even number of words before it)
+    int32_t* off = e->d_qi.p;        // [n + 1]
+    int32_t* cur = off + n + 1;      // [n]
+    int32_t* cnt = cur + n;          // [n]
+    int32_t* list = cnt + n;         // [cap]
+    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * C2 * (T + 1), e->st));
+    HIPCHK(e, hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, e->st));
+    HIPCHK(e, hipMemcpyAsync(shapes, e->h_shapes.data(), sizeof(ks::PodRec) * k, hipMemcpyHostToDevice, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    // the listed pods' requests stay in device units (QScale 1): the count takes e->scale itself
+    HIPCHK(e, ks::launch_headroom_series(e->d_blk.p, nb, q_hi, t_lo, t_hi, e->s, (int32_t)n, e->dc.filter_feeds,
+                                         e->cfg.filters, milli_scale(e), shapes, k, e->b_node.p, e->b_status.p,
+                                         e->t0.p, e->dur.p, e->pods.p, cnt, off, cur, list, (int32_t)cap, diff, res,
+                                         e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C2 * T, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
     return KS_OK;
 }

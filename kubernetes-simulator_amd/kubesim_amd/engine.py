@@ -14,6 +14,8 @@ Run                    ``step(ticks)`` — advances the tick loop (kubesim/kubes
 api.Filter / Scorer    ``filter(pod)`` / ``score(pod)``
 scheduleOne's trace    ``filter_at(pod)`` / ``score_at(pod)`` for bound pods; node state at a
                        past tick: ``requested_at``, ``cluster_series``, ``node_peaks``
+Node.CreatePod's test  ``headroom_at`` / ``headroom_series``: how many more pods of a shape
+                       each node would admit at a past tick (kubesim/node/node.go:44-47)
 =====================  ==============================================================
 
 Errors come back as :class:`KsError` with the reference's kind (``InvalidArgument`` /
@@ -233,6 +235,38 @@ class Engine:
         """[n][4] int64: per node and column the maximum of ``requested_at(t)`` over t_lo <= t < t_hi."""
         out = np.zeros((self.n, 4), np.int64)
         self._check(self._L.ks_node_peaks(self.h, t_lo, t_hi, _p(out)))
+        return out
+
+    # -- headroom (include/ks_engine.h, ks_headroom_at / ks_headroom_series) --------------------
+    @staticmethod
+    def _shapes(shapes: dict):
+        """The shape arrays of a dict with encode.encode_pods' keys (req, keymask, tol, sel); a slice
+        of an encoded pod set passes as it is."""
+        req = _c(shapes["req"], np.int64).reshape(-1, 3)
+        km, tol, sel = _c(shapes["keymask"], np.uint8), _c(shapes["tol"], np.uint64), _c(shapes["sel"], np.uint64)
+        k = len(req)
+        if not (len(km) == len(tol) == len(sel) == k):
+            raise ValueError(f"shapes: req has {k} rows, keymask {len(km)}, tol {len(tol)}, sel {len(sel)}")
+        return k, req, km, tol, sel
+
+    def headroom_at(self, t: int, shapes: dict, per_node: bool = False):
+        """How many more pods of each shape fit at tick t (Node.CreatePod's admission test,
+        kubesim/node/node.go:44-47, applied repeatedly).  Returns [k][KS_HEADROOM_COLS] int64: Σ over
+        nodes of the count, nodes with a count >= 1, the largest count, its lowest node (-1 if none),
+        the eligible nodes limited by cpu / memory / gpu / pods, the ineligible nodes; with
+        ``per_node`` also the [k][n] int32 counts."""
+        k, req, km, tol, sel = self._shapes(shapes)
+        out = np.zeros((k, _lib.KS_HEADROOM_COLS), np.int64)
+        pn = np.zeros((k, self.n), np.int32) if per_node else None
+        self._check(self._L.ks_headroom_at(self.h, t, k, _p(req), _p(km), _p(tol), _p(sel), _p(out),
+                                           _p(pn) if per_node else None))
+        return (out, pn) if per_node else out
+
+    def headroom_series(self, t_lo: int, t_hi: int, shapes: dict):
+        """[t_hi - t_lo][k][2] int64: columns 0 and 1 of ``headroom_at`` at every tick t_lo <= t < t_hi."""
+        k, req, km, tol, sel = self._shapes(shapes)
+        out = np.zeros((max(t_hi - t_lo, 0), k, 2), np.int64)
+        self._check(self._L.ks_headroom_series(self.h, t_lo, t_hi, k, _p(req), _p(km), _p(tol), _p(sel), _p(out)))
         return out
 
     def pod_lookup(self, node: int, key_id: int):
