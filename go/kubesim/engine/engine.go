@@ -432,6 +432,62 @@ func (e *Engine) HeadroomSeries(tLo, tHi int64, s *Shapes) ([]int64, error) {
 		u8p(s.KeyMask), u64p(s.Tol), u64p(s.Sel), i64p(out)))
 }
 
+// Placement preview constants (include/ks_engine.h): the most pods per PlaceAt call, the status of
+// a pod no node was selected for, the words of Placements.Info.
+const (
+	PlaceMaxPods  = 1024
+	PlaceNotFound = -1
+	PlaceInfo     = 4
+)
+
+// Placement is one preview pod's outcome (ks_placement): the bind node (-1: none), the status
+// (0 Ok, 1 OverCapacity, PlaceNotFound), the chosen node's aggregated score (-1: none) and the
+// number of nodes with an entry in the nodeScore map at this pod's turn.
+type Placement struct {
+	Node, Status      int32
+	Score, Candidates int64
+}
+
+// Placements is the result of PlaceAt: one Placement per pod, with after the requested state
+// (4 values per node: cpu, memory, gpu in milli-units, running pods) at t plus every Ok placement,
+// and Info = rounds of the device algorithm, pods placed Ok, placed OverCapacity, not found.
+type Placements struct {
+	Pods  []Placement
+	After []int64
+	Info  [PlaceInfo]int64
+}
+
+// PlaceAt is where len(shapeOf) more pods would be bound at tick t <= Tick(): scheduleOne
+// (kubesim/kubesim.go:143-225) for the pods one after another on a private copy of the state at t
+// (ks_place_at).  Pod j has shape shapeOf[j] of s; a nil shapeOf places one pod per shape, in
+// order.  No engine state changes; a pod without a candidate is reported PlaceNotFound and the
+// preview goes on.
+func (e *Engine) PlaceAt(t int64, s *Shapes, shapeOf []int32, after bool) (*Placements, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	ns, err := s.count()
+	if err != nil {
+		return nil, err
+	}
+	k := ns
+	if shapeOf != nil {
+		k = len(shapeOf)
+	}
+	if k < 1 || k > PlaceMaxPods {
+		return nil, strongerrors.InvalidArgument(errors.New("place: 1..1024 pods"))
+	}
+	r := &Placements{Pods: make([]Placement, k)}
+	if after {
+		r.After = make([]int64, 4*e.n+1)
+	}
+	err = status(e, C.ks_place_at(e.h, C.int64_t(t), C.int32_t(ns), i64p(s.Req), u8p(s.KeyMask), u64p(s.Tol),
+		u64p(s.Sel), C.int32_t(k), i32p(shapeOf), (*C.ks_placement)(unsafe.Pointer(&r.Pods[0])), i64p(r.After),
+		(*C.int64_t)(unsafe.Pointer(&r.Info[0]))))
+	if after {
+		r.After = r.After[:4*e.n]
+	}
+	return r, err
+}
+
 // Nodes is the node count of LoadNodes.
 func (e *Engine) Nodes() int { return e.n }
 

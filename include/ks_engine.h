@@ -27,6 +27,8 @@
  *   ks_cluster_series ........... running / requested / bound / failed / queued curves per tick
  *   ks_headroom_at / _series .... Node.CreatePod's admission test (kubesim/node/node.go:44-47) applied
  *                                 repeatedly: how many more pods of a shape each node would take
+ *   ks_place_at ................. scheduleOne (kubesim/kubesim.go:143-225) for k preview pods on a
+ *                                 private copy of a past tick's state: where they would be bound
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
  *   ks_pod_lookup / ks_node_pods  Node.GetPod / GetPodStatus / GetPodList (kubesim/node/node.go:62-93)
  *   ks_group_* .................. one KubeSim.Run per what-if scenario, stepped together
@@ -330,6 +332,56 @@ ks_status ks_headroom_at(ks_engine* eng, int64_t t, int32_t k, const int64_t* re
 ks_status ks_headroom_series(ks_engine* eng, int64_t t_lo, int64_t t_hi, int32_t k, const int64_t* req,
                              const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel,
                              int64_t* out /* [t_hi - t_lo][k][2] */);
+
+/* Placement preview: where k more pods would be bound, at any past tick ("at tick t" as above: after
+ * tick t's bind, 0 <= t <= the current tick).  The k preview pods are handed, one after another in
+ * the order given and all at tick t with nothing finishing in between, to scheduleOne
+ * (kubesim/kubesim.go:143-225) on a private copy of the state at t: no engine state changes.
+ *
+ * A pod's shape is exactly a headroom shape: req[3] in int64 milli-units, keymask, tol, sel; unmasked
+ * keys are ignored, a request need not be a multiple of anything the engine holds (it is never
+ * queued, there is no unit rescale).  Pod j has shape shape_of[j]; with shape_of NULL, k must equal
+ * n_shapes and pod j has shape j.
+ *
+ * Each pod goes through the engine's configured filter mode, filters and scorers exactly as in
+ * ks_step: the Filter loop (kubesim.go:168-188; its result gates the candidates only in
+ * KS_FILTER_FEEDS_SCORE mode, kubesim.go:182 discards it) and the score aggregation
+ * (kubesim.go:190-206) on ks_requested_at(t) plus the preview pods already placed Ok; the highest
+ * aggregated score wins, the lowest node index among equals (kubesim.go:208-222).  Node.CreatePod's
+ * admission test then gives KS_POD_OK or KS_POD_OVER_CAPACITY (kubesim/node/node.go:44-47); only an Ok
+ * placement adds the pod's masked requests and one running pod to its node (node.go:58, 97-118).
+ * Preview pods carry fresh keys (no Store replaces a stored pod), no flags, and never expire.
+ * A pod for which the nodeScore map is empty — no candidate node, or no scorer registered — gets
+ * KS_PLACE_NOT_FOUND, node -1, score -1; it changes nothing and the preview goes on with the next
+ * pod.  (A run aborts there with KS_ENOTFOUND, kubesim.go:218-220; a preview reports it per pod.)
+ *
+ * out[k]: node (-1: none), status, score (the chosen node's aggregated score as ks_score gives it,
+ * -1: none), candidates (the nodes with an entry in the nodeScore map at this pod's turn; in
+ * KS_FILTER_REFERENCE_LITERAL mode with scorers: n).  after_out (may be NULL): [n][4]
+ * ks_requested_at(t) plus every Ok placement, milli-units and running pods.  info_out (may be NULL):
+ * {rounds of the device algorithm (0 with n = 0), pods placed Ok, pods placed OverCapacity, pods
+ * not found}.  With n = 0: KS_OK and every pod is KS_PLACE_NOT_FOUND with 0 candidates.
+ * KS_EINVAL: a NULL engine, req, keymask, tol, sel or out (before the handle is read); n_shapes
+ * outside 1..KS_PLACE_MAX_SHAPES; k outside 1..KS_PLACE_MAX_PODS; a shape_of entry outside
+ * [0, n_shapes); a NULL shape_of with k != n_shapes; a keymask bit above 4; a request that is negative
+ * or >= 2^59 in a masked key; t out of range; no nodes loaded.  It answers after an aborted run, on
+ * sharded engines and on scenario-group members, like the state queries above: it reads the bind
+ * arrays, the pod records and the cluster's alloc / taints / labels only. */
+#define KS_PLACE_MAX_PODS 1024
+#define KS_PLACE_MAX_SHAPES 64 /* = KS_HEADROOM_MAX_SHAPES */
+#define KS_PLACE_NOT_FOUND (-1) /* status of a pod no node was selected for */
+#define KS_PLACE_INFO 4
+typedef struct {
+    int32_t node;       /* bind node, -1 when none */
+    int32_t status;     /* KS_POD_OK, KS_POD_OVER_CAPACITY, KS_PLACE_NOT_FOUND */
+    int64_t score;      /* aggregated score of the chosen node (as ks_score), -1 when none */
+    int64_t candidates; /* nodes with an entry in the nodeScore map at this pod's turn */
+} ks_placement;
+ks_status ks_place_at(ks_engine* eng, int64_t t, int32_t n_shapes, const int64_t* req /* [n_shapes][3] */,
+                      const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel, int32_t k,
+                      const int32_t* shape_of /* [k], or NULL: k == n_shapes, pod j is shape j */,
+                      ks_placement* out /* [k] */, int64_t* after_out /* [n][4] or NULL */,
+                      int64_t* info_out /* [KS_PLACE_INFO] or NULL */);
 
 /* Name-keyed queries over the binds made so far (Node.GetPod / GetPodStatus / GetPodList,
  * kubesim/node/node.go:62-93).  ks_pod_lookup: the FIFO index of the pod stored on `node` under

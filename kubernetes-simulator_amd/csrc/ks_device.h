@@ -1164,4 +1164,168 @@ hipError_t launch_headroom_series(const int32_t* blocks, int64_t nblocks, int64_
                                   int32_t* cnt, int32_t* off, int32_t* cur, int32_t* list, int32_t list_cap,
                                   unsigned long long* diff, unsigned long long* out, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------
+// Placement preview (ks_place_at, ks_place.hip): scheduleOne's Filter -> Score -> argmax ->
+// CreatePod (kubesim/kubesim.go:143-225, kubesim/node/node.go:36-60) for k preview pods one after
+// another on a private copy of the state at tick t.  A call runs in one unit throughout, sc
+// milli-units per device unit of each key: the node's alloc is alloc * sc (an absent key stays -1),
+// the state is rebuilt times sc, the requests are held in that unit, the pods capacity and the
+// running count are plain counts.  sc is the engine's scale — the call runs in milli-units, any
+// request is representable — unless every request is a whole multiple of the engine's unit: then
+// sc = 1 and the call runs in device units (place_whole_units, below).  Either way every quantity
+// is < 2^59, so the wide evaluator eval_total1 is exact (its BalancedAllocation goes to 128 bits
+// when Ac * Am needs it), and every fit / score result is unit-free: both routes place alike.
+//
+// Exactness of a round.  Keys are make_key(total + 1, node); keys of different nodes differ.  A round
+// starts from a committed state with an empty changed set and, per distinct shape, the exact global
+// top-L keys of that state, descending (the snapshot list; fewer than L non-zero entries: the list
+// is complete, every other node's key is 0).  A node joins the changed set when a preview pod is
+// placed on it; its list entries (in every shape's list) are flagged (one bit each) once the pod is
+// decided.  For pod i of shape s:
+//   S = the first unflagged entry of list s; D = the largest exact key of shape s over the changed
+//   nodes on their current state (0: none is a candidate).
+//   - S exists: every unchanged node still has its snapshot key; those above S in the list are all
+//     changed, those below it or outside the list are smaller.  The argmax is max(S, D).
+//   - no S, list complete: every unchanged node has key 0.  The argmax is D, or there is none.
+//   - no S, all L entries changed, D > the list's last key: every unchanged node is outside the
+//     list, so below its last key.  The argmax is D.
+//   - otherwise an unchanged node outside the list may win: the round ends before pod i, the
+//     changed nodes' states are committed and the next round scans again.
+// The changed set grows by at most one node per pod, so a pod that finds a full list entirely
+// flagged has at least L pods before it in its round: a round decides at least min(L, pods left)
+// pods, and the first pod of a round is always decided (nothing is flagged yet).
+// ---------------------------------------------------------------------------------------------
+#ifndef KS_PLACE_L
+#define KS_PLACE_L 32  // (A/B: make variant DEFS=-DKS_PLACE_L=16; 8, 16, 32 measured: DESIGN.md §3.4)
+#endif
+constexpr int kPlaceL = KS_PLACE_L;
+static_assert(kPlaceL == 8 || kPlaceL == 16 || kPlaceL == 32, "snapshot list length");
+constexpr int kPlaceMaxPods = 1024;  // KS_PLACE_MAX_PODS (= the changed set's capacity)
+constexpr int kPlaceMaxShapes = 64;  // KS_PLACE_MAX_SHAPES
+enum : int32_t { kPlaceOk = 0, kPlaceOverCapacity = 1, kPlaceNotFound = -1 };
+enum : int { kPlaceWin = 0, kPlaceNone = 1, kPlaceStop = 2 };
+
+struct Placement {  // = ks_placement
+    int32_t node, status;
+    int64_t score, candidates;
+};
+static_assert(sizeof(Placement) == 24, "ks_placement layout");
+
+// a node's constants in milli-units (in place)
+__host__ __device__ __forceinline__ void place_scale_alloc(NodeV& v, const QScale& sc) {
+    v.ac = v.ac < 0 ? -1 : v.ac * sc.f[0];
+    v.am = v.am < 0 ? -1 : v.am * sc.f[1];
+    v.ag = v.ag < 0 ? -1 : v.ag * sc.f[2];
+}
+
+// Whether every masked request of the shapes is a whole multiple of the engine's unit sc.  Then the
+// call runs in device units instead (scale 1, requests divided by sc, `after` multiplied back):
+// every fit / LeastRequested / BalancedAllocation result is unit-free, so the placements are the
+// same, and the smaller numbers keep BalancedAllocation's products in 64 bits.
+__host__ __device__ __forceinline__ bool place_whole_units(const PodRec* shapes, int n_shapes, const QScale& sc) {
+    bool whole = true;
+    for (int j = 0; j < n_shapes; ++j)
+        for (int c = 0; c < 3; ++c)
+            if ((shapes[j].keymask >> c & 1) && shapes[j].req[c] % sc.f[c] != 0) whole = false;
+    return whole;
+}
+
+__host__ __device__ __forceinline__ uint32_t place_key_node(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+__host__ __device__ __forceinline__ uint64_t place_key(const Cfg& c, const PodRec& p, const NodeV& n, uint32_t node) {
+    return make_key(eval_total1(c, p, n), node);
+}
+
+// entries of a snapshot list (sorted descending, 0-padded)
+template <int L = kPlaceL>
+__host__ __device__ __forceinline__ int place_list_len(const uint64_t* list) {
+    int len = 0;
+    for (int e = 0; e < L; ++e) len += list[e] != 0;
+    return len;
+}
+
+// index of the first of a snapshot list's `len` entries whose bit in `flagged` is clear, L if none
+template <int L = kPlaceL>
+__host__ __device__ __forceinline__ int place_first_unchanged(int len, uint32_t flagged) {
+    static_assert(L <= 32, "one flag word per list");
+    const uint32_t open = ~flagged & (len >= 32 ? 0xFFFFFFFFu : (1u << len) - 1u);
+    return open ? __builtin_ctz(open) : L;
+}
+
+// The decision of one pod (above).  S: its list's first unflagged key or 0; last: the list's L-th
+// key (0: the list is complete); D: the best key over the changed nodes.  kPlaceWin: *win is the
+// argmax key; kPlaceNone: no node has an entry in the score map; kPlaceStop: the round ends here.
+__host__ __device__ __forceinline__ int place_decide(uint64_t S, uint64_t last, uint64_t D, uint64_t* win) {
+    *win = 0;
+    if (S) {
+        *win = S > D ? S : D;
+        return kPlaceWin;
+    }
+    if (!last || D > last) {
+        *win = D;
+        return D ? kPlaceWin : kPlaceNone;
+    }
+    return kPlaceStop;
+}
+
+// CreatePod on the chosen node (kubesim/node/node.go:44-58): the admission test, and on Ok the
+// pod's masked requests and one running pod join the node's state.
+__host__ __device__ __forceinline__ int32_t place_bind(const PodRec& p, NodeV& n) {
+    if (!fits(p, n)) return kPlaceOverCapacity;
+    if (p.keymask & 1) n.rc += p.req[0];
+    if (p.keymask & 2) n.rm += p.req[1];
+    if (p.keymask & 4) n.rg += p.req[2];
+    n.nr += 1;
+    return kPlaceOk;
+}
+
+// whether the node has an entry in the pod's score map: eval_total1(c, p, n) != 0 without the scores
+__host__ __device__ __forceinline__ bool place_is_cand(const Cfg& c, const PodRec& p, const NodeV& n) {
+    if (!c.has_scorers) return false;
+    if (!c.filter_feeds) return true;
+    bool ok = true;
+    if (c.filters & kFilterFit) ok &= fits(p, n);
+    if (c.filters & kFilterTaint) ok &= (n.taint & ~p.tol) == 0;
+    if (c.filters & kFilterSelector) ok &= (n.label & p.sel) == p.sel;
+    return ok;
+}
+
+// what a bind changes in shape j's candidate count: cand(after) - cand(before) on the bound node
+__host__ __device__ __forceinline__ int32_t place_cand_delta(const Cfg& c, const PodRec& shape, const NodeV& before,
+                                                             const NodeV& after) {
+    return (int32_t)place_is_cand(c, shape, after) - (int32_t)place_is_cand(c, shape, before);
+}
+
+struct PlaceCfg {
+    Cfg c;
+    QScale sc;
+    int32_t n_nodes, k, n_shapes, nblk;
+};
+// Scratch of one call (device): state [4][n_pad] rc rm rg nr at t in the units of PlaceCfg::sc
+// (launch_requested with that scale, strides (1, n_pad)): milli-units per state unit — the engine's
+// scale when the call runs in milli-units, 1 when it runs in device units (place_whole_units);
+// shapes [n_shapes]; shape_of [k]; lists [64][nblk][kPlaceL], cnt [64][nblk] (nblk = ceil(n / 256));
+// top [64][kPlaceL], ccount [64]; out [k] (read once, after the last round); rb [4], the 16 bytes the
+// host reads after every round: the first undecided pod, 1 if the round decided none, the changed
+// nodes it committed, 0.
+struct PlaceBufs {
+    int64_t* state;
+    int64_t n_pad;
+    const PodRec* shapes;
+    const int32_t* shape_of;
+    uint64_t* lists;
+    int32_t* cnt;
+    uint64_t* top;
+    long long* ccount;
+    Placement* out;
+    int32_t* rb;
+};
+// one round from pod `first`: scan + merge for the shapes in `active` (bit j: a pod >= first has
+// shape j), then the resolver
+hipError_t launch_place_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, int32_t first, uint64_t active,
+                              hipStream_t st);
+// after[n][4] from state [4][n_pad], the three quantities times sc
+hipError_t launch_place_after(const int64_t* state, int64_t n_pad, int32_t n_nodes, const QScale& sc, long long* after,
+                              hipStream_t st);
+
 }  // namespace ks

@@ -2156,17 +2156,17 @@ static_assert(KS_HEADROOM_COLS == ks::kHeadCols && KS_HEADROOM_MAX_SHAPES == ks:
 constexpr int64_t kMaxHeadSeries = 1LL << 22;  // k * (t_hi - t_lo) at the most
 
 static ks_status head_shapes(ks_engine* e, int32_t k, const int64_t* req, const uint8_t* keymask, const uint64_t* tol,
-                             const uint64_t* sel) {
+                             const uint64_t* sel, const char* what = "headroom") {
     if (k < 1 || k > KS_HEADROOM_MAX_SHAPES)
-        return fail(e, KS_EINVAL, "headroom: %d shapes outside [1, %d]", (int)k, KS_HEADROOM_MAX_SHAPES);
+        return fail(e, KS_EINVAL, "%s: %d shapes outside [1, %d]", what, (int)k, KS_HEADROOM_MAX_SHAPES);
     e->h_shapes.assign(k, ks::PodRec{});
     for (int32_t j = 0; j < k; j++) {
-        if (keymask[j] & ~7u) return fail(e, KS_EINVAL, "headroom shape %d: keymask %u has bits above 4", (int)j, (unsigned)keymask[j]);
+        if (keymask[j] & ~7u) return fail(e, KS_EINVAL, "%s shape %d: keymask %u has bits above 4", what, (int)j, (unsigned)keymask[j]);
         ks::PodRec& r = e->h_shapes[j];
         for (int c = 0; c < 3; c++) {
             if (!(keymask[j] >> c & 1)) continue;  // unmasked keys are ignored
             const int64_t q = req[j * 3 + c];
-            if (q < 0 || q >= ks::kHeadReqMax) return fail(e, KS_EINVAL, "headroom shape %d: request %d out of range", (int)j, c);
+            if (q < 0 || q >= ks::kHeadReqMax) return fail(e, KS_EINVAL, "%s shape %d: request %d out of range", what, (int)j, c);
             r.req[c] = q;
         }
         r.tol = tol[j];
@@ -2254,6 +2254,111 @@ ks_status ks_headroom_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int32_t k
                                          e->st));
     HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C2 * T, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// ---- placement preview (ks_place.hip) ----------------------------------------------------------
+// scheduleOne for k preview pods on a private copy of the state at tick t: the rebuilt rc rm rg nr in
+// milli-units (the shapes' own units; nothing of the engine is rescaled) in the query scratch — or in
+// device units when every request is a whole multiple of the engine's unit — decided in rounds:
+// scan + merge give the exact top-kPlaceL snapshot list of every shape still to be placed, one
+// workgroup decides pods in order until one needs a node outside its list (ks_device.h), and the
+// host reads back 16 bytes per round: the first undecided pod.
+static_assert(KS_PLACE_MAX_PODS == ks::kPlaceMaxPods && KS_PLACE_MAX_SHAPES == ks::kPlaceMaxShapes &&
+              KS_PLACE_MAX_SHAPES == KS_HEADROOM_MAX_SHAPES && KS_PLACE_NOT_FOUND == ks::kPlaceNotFound &&
+              KS_POD_OK == ks::kPlaceOk && KS_POD_OVER_CAPACITY == ks::kPlaceOverCapacity && KS_PLACE_INFO == 4 &&
+              sizeof(ks_placement) == sizeof(ks::Placement) && offsetof(ks_placement, score) == offsetof(ks::Placement, score) &&
+              offsetof(ks_placement, candidates) == offsetof(ks::Placement, candidates),
+              "ks_place_at constants and record");
+
+ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* req, const uint8_t* keymask,
+                      const uint64_t* tol, const uint64_t* sel, int32_t k, const int32_t* shape_of, ks_placement* out,
+                      int64_t* after_out, int64_t* info_out) {
+    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "place"); r != KS_OK) return r;
+    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "place: %d pods outside [1, %d]", (int)k, KS_PLACE_MAX_PODS);
+    if (!shape_of && k != n_shapes)
+        return fail(e, KS_EINVAL, "place: %d pods without shape_of need %d shapes, not %d", (int)k, (int)k, (int)n_shapes);
+    std::vector<int32_t> so(k);
+    for (int32_t j = 0; j < k; j++) {
+        so[j] = shape_of ? shape_of[j] : j;
+        if (so[j] < 0 || so[j] >= n_shapes)
+            return fail(e, KS_EINVAL, "place: pod %d has shape %d outside [0, %d)", (int)j, (int)so[j], (int)n_shapes);
+    }
+    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
+    int64_t info[KS_PLACE_INFO] = {0, 0, 0, 0};
+    if (e->n == 0) {
+        for (int32_t j = 0; j < k; j++) out[j] = ks_placement{-1, KS_PLACE_NOT_FOUND, -1, 0};
+        info[3] = k;
+        if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
+        return KS_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t q_hi = bound_by(e, t);
+    const int64_t nb = usage_blocks(e, t, q_hi);
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long), L = ks::kPlaceL, S = KS_PLACE_MAX_SHAPES;
+    constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
+    const int64_t up_words = W * S + (k + 1) / 2;  // one upload: the shape records, then shape_of
+    const int64_t rb_words = 2 + PW * k;           // rb[4] (read back every round), then out[k] (read once)
+    HIPCHK(e, e->d_qs.reserve(4 * np + up_words + S * nblk * L + S * L + S + rb_words + 4 * n, e->st));
+    HIPCHK(e, e->d_qi.reserve(S * nblk, e->st));
+    ks::PlaceBufs b{};
+    unsigned long long* w = e->d_qs.p;
+    b.state = (int64_t*)w;                 w += 4 * np;    // [4][np]: rc rm rg nr at t, milli-units
+    b.n_pad = np;
+    unsigned long long* up = w;            w += up_words;
+    b.shapes = (const ks::PodRec*)up;                      // [n_shapes] (of S)
+    b.shape_of = (const int32_t*)(up + W * S);             // [k]
+    b.lists = (uint64_t*)w;                w += S * nblk * L;
+    b.top = (uint64_t*)w;                  w += S * L;
+    b.ccount = (long long*)w;              w += S;
+    unsigned long long* down = w;          w += rb_words;
+    b.rb = (int32_t*)down;
+    b.out = (ks::Placement*)(down + 2);
+    long long* after = (long long*)w;                      // [n][4]
+    b.cnt = e->d_qi.p;
+    std::vector<unsigned long long> h_up(up_words, 0ull), h_down(rb_words, 0ull);
+    // whole-unit requests: the call runs in device units (same placements, 64-bit BalancedAllocation)
+    const ks::QScale milli = milli_scale(e), one{{1, 1, 1}};
+    const bool whole = ks::place_whole_units(e->h_shapes.data(), n_shapes, milli);
+    const ks::QScale sc = whole ? one : milli;
+    if (whole)
+        for (ks::PodRec& r : e->h_shapes)
+            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
+    std::memcpy(h_up.data(), e->h_shapes.data(), sizeof(ks::PodRec) * n_shapes);
+    std::memcpy(h_up.data() + W * S, so.data(), sizeof(int32_t) * k);
+    HIPCHK(e, hipMemsetAsync(b.state, 0, sizeof(unsigned long long) * 4 * np, e->st));
+    HIPCHK(e, hipMemcpyAsync(up, h_up.data(), sizeof(unsigned long long) * up_words, hipMemcpyHostToDevice, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
+                                   e->pods.p, sc, 1, np, (unsigned long long*)b.state, e->st));
+    const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, k, n_shapes, (int32_t)nblk};
+    int32_t first = 0;
+    while (first < k) {
+        uint64_t active = 0;
+        for (int32_t j = first; j < k; j++) active |= 1ull << so[j];
+        HIPCHK(e, ks::launch_place_round(e->s, pc, b, first, active, e->st));
+        int32_t rb[4] = {0, 1, 0, 0};
+        HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        // a round decides its first pod at the least (nothing is changed yet): anything else is a fault
+        if (rb[1] != 0 || rb[0] <= first || rb[0] > k || ++info[0] > k)
+            return fail(e, KS_EDEVICE, "place: the round from pod %d decided no pod", (int)first);
+        first = rb[0];
+    }
+    static_assert(sizeof(ks_placement) == sizeof(ks::Placement), "ks_placement");
+    HIPCHK(e, hipMemcpyAsync(h_down.data(), down, sizeof(unsigned long long) * rb_words, hipMemcpyDeviceToHost, e->st));
+    if (after_out) {
+        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, whole ? milli : one, after, e->st));
+        HIPCHK(e, hipMemcpyAsync(after_out, after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    std::memcpy(out, h_down.data() + 2, sizeof(ks_placement) * k);
+    for (int32_t j = 0; j < k; j++) info[out[j].status == KS_POD_OK ? 1 : out[j].status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
+    if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
     return KS_OK;
 }
 

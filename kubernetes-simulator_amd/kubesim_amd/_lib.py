@@ -46,6 +46,12 @@ KS_SERIES_COLS = 7  # ks_cluster_series: running, requested cpu / memory / gpu, 
 KS_HEADROOM_COLS = 9
 KS_HEADROOM_MAX_SHAPES = 64
 KS_HEADROOM_NODE_MAX = 2147483647
+# ks_place_at: pods and shapes per call, the status of a pod no node was selected for, the info words
+# (rounds, placed Ok, placed OverCapacity, not found)
+KS_PLACE_MAX_PODS = 1024
+KS_PLACE_MAX_SHAPES = 64
+KS_PLACE_NOT_FOUND = -1
+KS_PLACE_INFO = 4
 
 STATUS_NAMES = {KS_OK: "OK", KS_EINVAL: "InvalidArgument", KS_ENOTFOUND: "NotFound",
                 KS_EDEVICE: "DeviceError", KS_ENOMEM: "OutOfMemory", KS_ERANGE: "OutOfDomain"}
@@ -59,7 +65,7 @@ EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods"
                     "ks_usage_at", "ks_usage_digest", "ks_node_mix", "ks_pod_lookup", "ks_node_pods",
                     "ks_shard_layout", "ks_merge_candidates",
                     "ks_requested_at", "ks_filter_at", "ks_score_at", "ks_cluster_series", "ks_node_peaks",
-                    "ks_headroom_at", "ks_headroom_series",
+                    "ks_headroom_at", "ks_headroom_series", "ks_place_at",
                     # include/ks_ingest.h
                     "ks_parse_quantity", "ks_parse_simspec", "ks_cluster_parse", "ks_cluster_free",
                     "ks_cluster_nodes", "ks_cluster_tick", "ks_cluster_start_clock", "ks_cluster_arrays",
@@ -223,9 +229,10 @@ def load():
     L.ks_node_peaks.argtypes = [p, C.c_int64, C.c_int64, p]
     L.ks_headroom_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, p, p]
     L.ks_headroom_series.argtypes = [p, C.c_int64, C.c_int64, C.c_int32, p, p, p, p, p]
+    L.ks_place_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, p, p, p]
     for f in ("ks_load_nodes", "ks_submit_pods", "ks_step", "ks_filter", "ks_score", "ks_usage", "ks_usage_at",
               "ks_usage_digest", "ks_pod_lookup", "ks_node_pods", "ks_requested_at", "ks_filter_at", "ks_score_at",
-              "ks_cluster_series", "ks_node_peaks", "ks_headroom_at", "ks_headroom_series"):
+              "ks_cluster_series", "ks_node_peaks", "ks_headroom_at", "ks_headroom_series", "ks_place_at"):
         getattr(L, f).restype = C.c_int
     L.ks_current_tick.argtypes = [p]
     L.ks_current_tick.restype = C.c_int64

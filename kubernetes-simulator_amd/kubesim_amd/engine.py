@@ -16,6 +16,8 @@ scheduleOne's trace    ``filter_at(pod)`` / ``score_at(pod)`` for bound pods; no
                        past tick: ``requested_at``, ``cluster_series``, ``node_peaks``
 Node.CreatePod's test  ``headroom_at`` / ``headroom_series``: how many more pods of a shape
                        each node would admit at a past tick (kubesim/node/node.go:44-47)
+scheduleOne, what-if   ``place_at``: where k more pods would be bound at a past tick, on a
+                       private copy of the state (kubesim/kubesim.go:143-225)
 =====================  ==============================================================
 
 Errors come back as :class:`KsError` with the reference's kind (``InvalidArgument`` /
@@ -45,6 +47,11 @@ def _p(a):
 
 def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
+
+
+# ks_placement (include/ks_engine.h)
+PLACEMENT_DTYPE = np.dtype([("node", np.int32), ("status", np.int32), ("score", np.int64), ("candidates", np.int64)])
+assert PLACEMENT_DTYPE.itemsize == 24
 
 
 def _config(tick_seconds, filter_mode, filters, scorers, device, batch_pods, engine_flags):
@@ -268,6 +275,28 @@ class Engine:
         out = np.zeros((max(t_hi - t_lo, 0), k, 2), np.int64)
         self._check(self._L.ks_headroom_series(self.h, t_lo, t_hi, k, _p(req), _p(km), _p(tol), _p(sel), _p(out)))
         return out
+
+    # -- placement preview (include/ks_engine.h, ks_place_at) -----------------------------------
+    def place_at(self, t: int, shapes: dict, shape_of=None, after: bool = False):
+        """Where k more pods would be bound at tick t: scheduleOne (kubesim/kubesim.go:143-225) for
+        the pods one after another on a private copy of the state at t — no engine state changes.
+        ``shapes`` as for ``headroom_at``; pod j has shape ``shape_of[j]`` (None: one pod per shape,
+        in order).  Returns a dict of arrays over the pods — ``node`` (-1: none), ``status``
+        (KS_POD_OK, KS_POD_OVER_CAPACITY, KS_PLACE_NOT_FOUND), ``score`` (-1: none), ``candidates``
+        — plus ``info`` (rounds, placed Ok, placed OverCapacity, not found) and ``after``: with
+        ``after=True`` the [n][4] requested state at t plus every Ok placement, else None."""
+        ns, req, km, tol, sel = self._shapes(shapes)
+        so = None if shape_of is None else _c(shape_of, np.int32)
+        k = ns if so is None else len(so)
+        rec = np.zeros(max(k, 1), PLACEMENT_DTYPE)
+        aft = np.zeros((self.n, 4), np.int64) if after else None
+        info = np.zeros(_lib.KS_PLACE_INFO, np.int64)
+        self._check(self._L.ks_place_at(self.h, t, ns, _p(req), _p(km), _p(tol), _p(sel), k,
+                                        None if so is None else _p(so), _p(rec), _p(aft) if after else None,
+                                        _p(info)))
+        rec = rec[:k]
+        return dict(node=rec["node"].copy(), status=rec["status"].copy(), score=rec["score"].copy(),
+                    candidates=rec["candidates"].copy(), after=aft, info=info)
 
     def pod_lookup(self, node: int, key_id: int):
         """Node.GetPod: FIFO index of the pod stored on ``node`` under ``key_id`` (KsError NotFound)."""

@@ -1,0 +1,288 @@
+"""The placement preview's decision and bookkeeping functions of ks_device.h (place_decide,
+place_first_unchanged, place_bind, place_cand_delta, place_key, topl_insert), compiled for the host
+(tests/native/place_host.cpp).  A serial driver runs the whole rounds algorithm of ks_place.hip — per
+256-node block lists, the topl_insert merge, the resolver's pod loop, the commit, the rescan — and
+must equal the plain sequential argmax over all nodes on every field and on the final state; a
+subset is also checked against the Python integers of tests/place_ref.py.  Exact integer equality;
+no device is needed."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import place_ref as pr
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "native", "place_host.cpp")
+DEV_H = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc", "ks_device.h")
+REC = np.dtype([("node", np.int32), ("status", np.int32), ("score", np.int64), ("candidates", np.int64)])
+TOP = (1 << 59) - 1
+N_FUZZ = 2400
+
+
+@functools.lru_cache(maxsize=None)
+def host_lib(L=None):
+    """ks_device.h's placement functions compiled for the host (rebuilt when a source is newer);
+    L: another snapshot list length than the product's."""
+    lib = os.path.join(HERE, "native", "libks_hostplace%s.so" % ("" if L is None else "_l%d" % L))
+    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(SRC), os.path.getmtime(DEV_H)):
+        defs = [] if L is None else ["-DKS_PLACE_L=%d" % L]
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", *defs, "-o", lib, SRC], check=True)
+    lb = C.CDLL(lib)
+    p = C.c_void_p
+    case = [C.c_int32, p, p, p, p, p, p, C.c_int32, p, p, p, p, C.c_int32, p]
+    lb.ks_host_place_brute.argtypes = case + [p, p, p]
+    lb.ks_host_place.argtypes = lb.ks_host_place_units.argtypes = case + [p, p, p, p]
+    lb.ks_host_place_brute.restype = lb.ks_host_place.restype = lb.ks_host_place_l.restype = C.c_int
+    lb.ks_host_place_units.restype = C.c_int
+    return lb
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def make(alloc_dev, scale, state, taint, label, cfg, req, keymask, tol, sel, shape_of):
+    """A case in the driver's arrays.  cfg: (filter_feeds, filters, has_scorers, w_lr, w_ba, const_total)."""
+    c = dict(alloc=np.ascontiguousarray(alloc_dev, np.int64).reshape(-1, 4), scale=np.array(scale, np.int64),
+             state=np.ascontiguousarray(state, np.int64).reshape(-1, 4), taint=np.ascontiguousarray(taint, np.uint64),
+             label=np.ascontiguousarray(label, np.uint64), cfg=np.array(cfg, np.int32),
+             req=np.ascontiguousarray(req, np.int64).reshape(-1, 3), keymask=np.ascontiguousarray(keymask, np.uint32),
+             tol=np.ascontiguousarray(tol, np.uint64), sel=np.ascontiguousarray(sel, np.uint64),
+             shape_of=np.ascontiguousarray(shape_of, np.int32))
+    n = len(c["alloc"])
+    assert len(c["state"]) == len(c["taint"]) == len(c["label"]) == n
+    assert len(c["req"]) == len(c["keymask"]) == len(c["tol"]) == len(c["sel"]) <= 64
+    assert 1 <= len(c["shape_of"]) <= 1024 and c["shape_of"].max() < len(c["req"])
+    return c
+
+
+def run(c, brute, L=None, units=False):
+    lb = host_lib(L)
+    n, k = len(c["alloc"]), len(c["shape_of"])
+    out = np.zeros(k, REC)
+    after = np.zeros((n, 4), np.int64)
+    info = np.zeros(4, np.int64)
+    stats = np.zeros(3, np.int64)
+    args = [n, _p(c["alloc"]), _p(c["scale"]), _p(c["state"]), _p(c["taint"]), _p(c["label"]), _p(c["cfg"]),
+            len(c["req"]), _p(c["req"]), _p(c["keymask"]), _p(c["tol"]), _p(c["sel"]), k, _p(c["shape_of"])]
+    if brute:
+        rc = lb.ks_host_place_brute(*args, _p(out), _p(after), _p(info))
+    else:
+        rc = (lb.ks_host_place_units if units else lb.ks_host_place)(*args, _p(out), _p(after), _p(info), _p(stats))
+    assert rc == 0, f"the driver stopped with {rc}"
+    return dict(node=out["node"], status=out["status"], score=out["score"], candidates=out["candidates"], after=after,
+                info=info, stats=stats)
+
+
+def check(c, L=None, what=""):
+    got, want = run(c, False, L), run(c, True, L)
+    pr.assert_same(got, want, what)
+    assert 1 <= got["info"][0] <= len(c["shape_of"])
+    return got
+
+
+def python_ref(c):
+    """tests/place_ref.py fast_place on the same case (milli-units)."""
+    alloc = c["alloc"].astype(object)
+    for col in range(3):
+        alloc[:, col] = [int(a) * int(c["scale"][col]) if a >= 0 else -1 for a in c["alloc"][:, col]]
+    ff, fl, has, w_lr, w_ba, const = (int(x) for x in c["cfg"])
+    scorers = ()
+    if has:
+        scorers = ((0, 1, const),) + (((1, w_lr, 0),) if w_lr else ()) + (((2, w_ba, 0),) if w_ba else ())
+    cfg = dict(filter_mode=ff, filters=fl, scorers=scorers, taint=c["taint"], label=c["label"])
+    shapes = dict(req=c["req"], keymask=c["keymask"], tol=c["tol"], sel=c["sel"])
+    return pr.fast_place(alloc, c["state"], cfg, shapes, c["shape_of"])
+
+
+# ---- fuzz ------------------------------------------------------------------------------------
+SCALES = [(1, 1, 1), (1000, 1 << 20, 1000), (250, 1000 << 20, 1), (1, 268435456000, 1000)]
+
+
+def fuzz_case(rng):
+    u = rng.random()
+    n = int(rng.integers(1, 40)) if u < 0.35 else int(rng.integers(17, 300)) if u < 0.88 else int(rng.integers(300, 701))
+    u = rng.random()
+    k = int(rng.integers(1, 40)) if u < 0.3 else int(rng.integers(40, 300)) if u < 0.92 else int(rng.integers(300, 1025))
+    ns = int(rng.integers(1, 7)) if rng.random() < 0.9 else int(rng.integers(7, 65))
+    scale = SCALES[int(rng.integers(len(SCALES)))]
+    huge = rng.random() < 0.05            # quantities near 2^59: the 128-bit BalancedAllocation path
+    if huge:
+        scale = (1, 1, 1)
+    classes = int(rng.integers(1, 4))     # few node sizes: many equal scores
+    top_dev = [(TOP // s) if huge else int(rng.integers(8, 1 << 14)) for s in scale]
+    size = np.array([[max(top_dev[c] // int(rng.integers(1, 5)), 1) for c in range(3)] for _ in range(classes)], np.int64)
+    alloc = np.zeros((n, 4), np.int64)
+    cls = rng.integers(classes, size=n)
+    alloc[:, :3] = size[cls]
+    alloc[:, 3] = rng.choice([110, 110, 110, 3, 1, 0], size=n)
+    for col in range(3):                  # absent and empty keys
+        alloc[rng.random(n) < 0.03, col] = -1
+        alloc[rng.random(n) < 0.02, col] = 0
+    alloc_m = np.where(alloc[:, :3] >= 0, alloc[:, :3].astype(object) * np.array(scale, object), 0)
+    state = np.zeros((n, 4), np.int64)
+    busy = rng.random(n) < rng.choice([0.0, 0.3, 0.9])
+    for col in range(3):
+        state[:, col] = [int(a) * int(f) // 1000 if b else 0 for a, f, b in zip(alloc_m[:, col], rng.integers(0, 1000, n), busy)]
+    state[:, 3] = np.where(busy, rng.integers(0, 4, n), 0)
+    taint = np.where(rng.random(n) < 0.25, rng.integers(1, 8, n), 0).astype(np.uint64)
+    label = rng.integers(0, 8, n).astype(np.uint64)
+    typ = [int(size[0][c]) * scale[c] for c in range(3)]
+    req = np.zeros((ns, 3), np.int64)
+    for j in range(ns):
+        for c in range(3):
+            div = int(rng.choice([3, 6, 6, 7, 20, 1000]))
+            req[j, c] = min(typ[c] // div + int(rng.integers(0, 3)), TOP)
+    if rng.random() < 0.1:
+        req[rng.integers(ns), rng.integers(3)] = 0
+    keymask = rng.choice([3, 3, 3, 7, 1, 2, 0, 4], size=ns).astype(np.uint32)
+    tol = np.where(rng.random(ns) < 0.7, 7, rng.integers(0, 8, ns)).astype(np.uint64)
+    sel = np.where(rng.random(ns) < 0.75, 0, rng.integers(0, 16, ns)).astype(np.uint64)
+    how = rng.integers(3)
+    if how == 0:
+        shape_of = rng.integers(ns, size=k)
+    elif how == 1:
+        shape_of = np.arange(k) % ns
+    else:
+        shape_of = (np.arange(k) // max(k // (2 * ns), 1)) % ns    # runs
+    feeds = int(rng.random() < 0.7)
+    filters = int(rng.choice([7, 7, 1, 6, 3, 0]))
+    has = int(rng.random() < 0.96)
+    w_lr, w_ba = int(rng.integers(0, 4)), int(rng.integers(0, 4))
+    const = int(rng.integers(0, 6))
+    return make(alloc, scale, state, taint, label, (feeds, filters, has, w_lr, w_ba, const), req, keymask, tol, sel, shape_of)
+
+
+def test_fuzzed_clusters_rounds_equal_the_sequential_argmax():
+    rng = np.random.default_rng(20261019)
+    L = host_lib().ks_host_place_l()
+    rounds, from_d, statuses, sizes = [], 0, set(), []
+    for i in range(N_FUZZ):
+        c = fuzz_case(rng)
+        got = check(c, what=f"fuzz case {i}")
+        rounds.append(int(got["info"][0]))
+        from_d += int(got["stats"][0])
+        statuses |= set(got["status"].tolist())
+        sizes.append(len(c["alloc"]))
+        # at least L pods, or all that remain, per round
+        assert got["info"][0] <= (len(c["shape_of"]) + L - 1) // L, f"fuzz case {i}: {got['info'][0]} rounds"
+        if i < 150 and len(c["alloc"]) <= 120:
+            pr.assert_same(got, python_ref(c), f"fuzz case {i} against Python integers")
+    rounds = np.array(rounds)
+    assert N_FUZZ >= 2000 and min(sizes) == 1 and max(sizes) >= 650
+    assert (rounds >= 2).mean() >= 0.10, f"only {(rounds >= 2).mean():.1%} of the cases took two rounds or more"
+    assert (rounds >= 4).any(), "no case took four rounds"
+    assert from_d > 1000 and statuses == {pr.OK, pr.OVER, pr.NOT_FOUND}
+
+
+def test_whole_unit_requests_run_in_device_units_with_the_same_result():
+    """ks_place_at runs in device units when every masked request is a whole multiple of the unit
+    (place_whole_units): the same placements and final state as the milli-unit brute force."""
+    rng = np.random.default_rng(5150)
+    took = {0: 0, 1: 0}
+    for i in range(400):
+        c = fuzz_case(rng)
+        sc = c["scale"]
+        c["state"][:, :3] = c["state"][:, :3] // sc * sc                    # the engine's state holds whole units
+        if i % 4:                                                          # three in four: whole-unit requests
+            c["req"][:] = np.maximum(c["req"] // sc, (c["req"] > 0)) * sc
+        got, want = run(c, False, units=True), run(c, True)
+        pr.assert_same(got, want, f"case {i}")
+        whole = all(int(c["req"][j, k]) % int(sc[k]) == 0 for j in range(len(c["req"])) for k in range(3)
+                    if (int(c["keymask"][j]) >> k) & 1)
+        assert bool(got["stats"][2]) == whole, f"case {i}"
+        took[int(got["stats"][2])] += 1
+    assert took[1] >= 250 and took[0] >= 40, took
+
+
+@pytest.mark.parametrize("L", [8, 16])
+def test_other_list_lengths(L):
+    """The candidate values of kPlaceL: the same algorithm, fewer cases."""
+    assert host_lib(L).ks_host_place_l() == L
+    rng = np.random.default_rng(77 + L)
+    rounds = [int(check(fuzz_case(rng), L, f"L = {L}, case {i}")["info"][0]) for i in range(300)]
+    assert max(rounds) >= 2
+
+
+# ---- edges -----------------------------------------------------------------------------------
+def uniform(n, k, cfg, ap=110, cpu=16000, mem=64000, req=(1000, 4000, 0), shape_of=None, **over):
+    alloc = np.tile(np.array([cpu, mem, 8000, ap], np.int64), (n, 1))
+    c = dict(alloc_dev=alloc, scale=(1, 1, 1), state=np.zeros((n, 4), np.int64), taint=np.zeros(n, np.uint64),
+             label=np.zeros(n, np.uint64), cfg=cfg, req=[req], keymask=[3], tol=[0], sel=[0],
+             shape_of=np.zeros(k, np.int32) if shape_of is None else shape_of)
+    c.update(over)
+    return make(**c)
+
+
+FEEDS_CONST = (1, 7, 1, 0, 0, 3)
+FEEDS_LRBA = (1, 7, 1, 1, 1, 0)
+LITERAL_CONST = (0, 7, 1, 0, 0, 3)
+
+
+def test_ties_across_block_boundaries():
+    """600 equal nodes and a constant score: every key ties, the lowest index wins; two pods fill a
+    node, so 1,024 pods walk across both block boundaries."""
+    got = check(uniform(600, 1024, FEEDS_CONST, ap=2))
+    np.testing.assert_array_equal(got["node"], np.arange(1024) // 2)
+    assert (got["status"] == pr.OK).all() and got["info"][0] >= 1024 // (2 * host_lib().ks_host_place_l())
+    np.testing.assert_array_equal(got["candidates"], 600 - np.arange(1024) // 2)
+
+
+def test_lists_shorter_than_l_and_exactly_l_and_l_plus_one_candidates():
+    L = host_lib().ks_host_place_l()
+    for n in (1, 5, L - 1, L, L + 1):
+        got = check(uniform(n, 3 * L, FEEDS_CONST, ap=1), what=f"{n} nodes")
+        assert (got["status"][:n] == pr.OK).all() and (got["status"][n:] == pr.NOT_FOUND).all()
+        # a list shorter than L is complete and never ends a round; a full one does once all its
+        # entries are changed (with exactly L candidates the next round's list is empty, with L + 1
+        # it holds the one node that was outside)
+        assert got["info"][0] == (2 if n >= L else 1), (n, got["info"])
+    # L + 1 candidates among more nodes (the others are full)
+    c = uniform(3 * L, 2 * L, FEEDS_CONST, ap=1)
+    c["state"][L + 1:, 3] = 1
+    got = check(c)
+    assert (got["status"] == pr.OK).sum() == L + 1 and got["info"][0] == 2
+
+
+def test_winner_is_a_changed_node():
+    """BalancedAllocation prefers the node the first pod made more balanced: the second pod's winner
+    comes from the changed set, not from the list."""
+    # a cpu-only pod scores 7 everywhere and takes node 0; the memory-only pod after it scores 10 on
+    # node 0 (30 % / 30 %) and 7 on every unchanged node
+    c = uniform(40, 6, (1, 7, 1, 0, 1, 0), cpu=10000, mem=10000, req=[(3000, 0, 0), (0, 3000, 0)], keymask=[3, 3],
+                tol=[0, 0], sel=[0, 0], shape_of=np.arange(6, dtype=np.int32) % 2)
+    got = check(c)
+    assert got["stats"][0] >= 1 and got["node"][:2].tolist() == [0, 0] and got["score"][:2].tolist() == [7, 10]
+    # tiny requests: the score does not move, the same node wins again and again
+    got = check(uniform(40, 50, FEEDS_LRBA, req=(1, 1, 0)))
+    assert (got["node"] == 0).all() and got["stats"][0] == 49 and got["info"][0] == 1
+
+
+def test_not_found_between_placeable_pods():
+    c = uniform(30, 40, FEEDS_LRBA, req=[(1000, 4000, 0), (1000, 4000, 0)], keymask=[3, 3], tol=[0, 0], sel=[0, 1 << 63],
+                shape_of=np.arange(40, dtype=np.int32) % 2)
+    got = check(c)
+    assert (got["status"][0::2] == pr.OK).all() and (got["status"][1::2] == pr.NOT_FOUND).all()
+    assert (got["candidates"][1::2] == 0).all() and (got["node"][1::2] == -1).all() and (got["score"][1::2] == -1).all()
+    assert got["info"].tolist()[1:] == [20, 0, 20]
+
+
+def test_over_capacity_repeats_on_one_node_in_literal_mode():
+    c = uniform(20, 30, LITERAL_CONST, ap=2)
+    got = check(c)
+    assert (got["node"] == 0).all() and (got["candidates"] == 20).all()
+    assert got["status"].tolist() == [pr.OK] * 2 + [pr.OVER] * 28
+    assert got["after"][0].tolist() == [2000, 8000, 0, 2] and not got["after"][1:].any()
+
+
+def test_no_scorers_and_quantities_at_the_top_of_the_domain():
+    got = check(uniform(10, 5, (1, 7, 0, 1, 1, 0)))
+    assert (got["status"] == pr.NOT_FOUND).all() and (got["candidates"] == 0).all() and got["info"][0] == 1
+    c = uniform(40, 60, FEEDS_LRBA, cpu=TOP, mem=TOP - 1, req=((TOP - 1) // 7, TOP // 5 + 1, 0))
+    got = check(c)
+    pr.assert_same(got, python_ref(c), "2^59 - 1")
+    assert (got["status"] == pr.OK).all() and got["info"][0] >= 2
