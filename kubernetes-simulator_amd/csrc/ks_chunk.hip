@@ -156,8 +156,8 @@ struct ChShared {
     struct {
         uint64_t k[kWaves][kC][2];  // scratch: slot requests (setup), avail lists (guess), pair totals (sweeps)
     } x;
-    uint32_t brow[kC][4];         // chunk pod c0 + r: request words (saturated), key mask | run << 3 |
-                                  // own expiry's pod (kNoOwn: none) << 16
+    uint32_t brow[kB][4];         // pod j's bind row (static in the batch, filled in setup): request words
+                                  // (saturated), key mask | run << 3 | own expiry's pod (kNoOwn: none) << 16
     int16_t ceix[kCid];           // cid -> the node's index in E, -1 if not an E node
     int16_t e2c[kSlots];          // slot-E index -> cid, -1: the E node is no candidate of this batch
     int32_t nbc, cut, fc[2], fs[2];
@@ -173,17 +173,15 @@ static_assert(sizeof(ChShared) <= 160 * 1024, "LDS");
 // binds >= tb (admission known, adm[]), then — `chunk` — the current sweep's chunk binds (admission
 // evaluated, written to adm[]), with the pre-batch expiry slots of k (E cids) and each admitted
 // running bind's own expiry, in pod order.  Stores the state segments for pods [from, i_end) in
-// slot sl (sl < 0: none); returns the state before pod i_end binds (events effective < i_end);
-// *ecur_out / *hp_out (optional): the E cursor and whether own expiries remain pending after it.
+// slot sl (sl < 0: none); returns the state before pod i_end binds (events effective < i_end).
 // A bind whose own expiry cannot be tracked (more than kPend pending) makes the state unknown
-// from the next pod on: the slot's ovf, adm 2 for later binds, *lost_at.
-struct Replayed {
-    NS32 v;
-    int ecur;     // E cursor after the replay
-    bool hp;      // own expiries still pending
-    int lost_at;  // INT_MAX, or the first pod whose state is unknown
-};
-__device__ __forceinline__ Replayed replay(ChShared& sh, int k, int tb, bool chunk, int c0, int from, int sl, int i_end) {
+// from the next pod on: the slot's ovf, adm 2 for later binds, and — kCkpt — the batch's cut.
+// Every bind's data comes from its batch-wide row (brow: static in the batch); only adm[] and the
+// final lists change.  tb < from is allowed (segment starts are clamped to `from`); kCkpt — the
+// per-chunk cache's call, from = c0 — also rebases the cid to `from` on the way: one replay
+// instead of a rebase and a second replay from the new base.
+template <bool kCkpt = false>
+__device__ __forceinline__ NS32 replay(ChShared& sh, int k, int tb, bool chunk, int c0, int from, int sl, int i_end) {
     // (no lambdas: their by-reference closures kept the state in scratch memory)
     uint32_t vrc = (uint32_t)sh.rd[0][k], vrm = (uint32_t)sh.rd[1][k], vrg = (uint32_t)sh.rd[2][k];
     int32_t vnr = sh.rd[3][k];
@@ -195,7 +193,7 @@ __device__ __forceinline__ Replayed replay(ChShared& sh, int k, int tb, bool chu
     static_assert(kPend == 4, "four pending slots");
     int pe0 = INT_MAX, pe1 = INT_MAX, pe2 = INT_MAX, pe3 = INT_MAX, pj0 = 0, pj1 = 0, pj2 = 0, pj3 = 0;
     bool lost = false;
-    int ovf = kNoSeg, lost_at = INT_MAX;
+    int ovf = kNoSeg;
 #define KS_PUSH(EX, JB)                                                                              \
     do {                                                                                             \
         const int ex_ = (EX), jb_ = (JB);                                                            \
@@ -208,21 +206,25 @@ __device__ __forceinline__ Replayed replay(ChShared& sh, int k, int tb, bool chu
         if (!(s0 || s1 || s2 || s3)) { /* untracked: the state is unknown from the next pod on */   \
             lost = true;                                                                             \
             ovf = jb_ + 1 < ovf ? jb_ + 1 : ovf;                                                     \
-            lost_at = jb_ + 1 < lost_at ? jb_ + 1 : lost_at;                                         \
         }                                                                                            \
     } while (0)
     if (ec & 0x8000) {  // own expiries of binds before the base that have not fired by it
         for (int j = sh.fhead[k]; j >= 0 && j < tb; j = sh.fnext[j]) {
-            const int x = sh.own[j];
-            if (sh.adm[j] == 1 && (sh.clfl[j] & kFlRun) && x >= 0 && sh.xeff[x] >= tb) KS_PUSH(sh.xeff[x], j);
+            const uint32_t meta = sh.brow[j][3];
+            const int oe = (int)(meta >> 16);
+            if (sh.adm[j] == 1 && (meta & 8) && oe != kNoOwn && oe >= tb) KS_PUSH(oe, j);
         }
     }
+    // (kCkpt: the replay first runs to pod `from` without storing segments, writes there what a
+    // rebase to it writes — the base state, the E cursor, the final cursor, the cut of an untracked
+    // own expiry — and the row's first segment, and goes on to i_end)
+    bool ckpt = kCkpt;
     int ns = 0, last_t = -1;
 #define KS_STORE(T)                                                                                  \
     do {                                                                                             \
         int t_ = (T);                                                                                \
         t_ = t_ < from ? from : t_;                                                                  \
-        if (sl >= 0 && t_ < i_end && t_ < ovf) {                                                     \
+        if (sl >= 0 && !ckpt && t_ < i_end && t_ < ovf) {                                            \
             bool ok_ = true;                                                                         \
             if (t_ != last_t) {                                                                      \
                 if (ns == kSeg) { ovf = t_; ok_ = false; }                                           \
@@ -240,77 +242,98 @@ __device__ __forceinline__ Replayed replay(ChShared& sh, int k, int tb, bool chu
     const int64_t ac64 = cap64(ac), am64 = cap64(am), ag64 = cap64(ag);
     int j = sh.fcur[k];
     uint64_t m = chunk ? sh.cmask[k] : 0ull;
-    // one event loop: the next bind (final list, then the chunk mask) against the next expiry
+    // One event loop: the next bind (final list, then the chunk mask) against the next expiry.
+    // Both are held in registers — the expiry row er (reloaded only when one is consumed) and the
+    // next bind jb's row br with, for a final bind, its admission ad and list successor jn — and
+    // the reads that replace them are issued before the consumed event's arithmetic: an iteration
+    // waits for one LDS round trip.
+#define KS_EROW() (e_u < e_end ? sh.erow[e_u] : make_int4(INT_MAX, 0, 0, 0))
+#define KS_BIND()                                                                                    \
+    do {                                                                                             \
+        jb = j >= 0 ? j : (m ? c0 + __builtin_ctzll(m) : INT_MAX);                                   \
+        const int jx_ = jb != INT_MAX ? jb : 0;                                                      \
+        br = *reinterpret_cast<const uint4*>(&sh.brow[jx_][0]);                                      \
+        ad = sh.adm[jx_];                                                                            \
+        jn = sh.fnext[jx_];                                                                          \
+    } while (0)
+    int4 er = KS_EROW();
+    int jb, ad, jn;
+    uint4 br;
+    KS_BIND();
+    int iend = kCkpt ? from : i_end;
     for (;;) {
-        int jb = j >= 0 ? j : (m ? c0 + __builtin_ctzll(m) : INT_MAX);
-        if (jb >= i_end) jb = INT_MAX;
-        const int4 er = e_u < e_end ? sh.erow[e_u] : make_int4(INT_MAX, 0, 0, 0);
+        const int jc = jb < iend ? jb : INT_MAX;
         const int ne = er.x;
         const int pm01 = pe0 < pe1 ? pe0 : pe1, pm23 = pe2 < pe3 ? pe2 : pe3;
         const int pm = pm01 < pm23 ? pm01 : pm23;
         const int nx = ne < pm ? ne : pm;
-        const int lim = jb != INT_MAX ? jb : i_end - 1;
-        if (nx <= lim) {  // an expiry effective before the next bind (or before i_end)
+        const int lim = jc != INT_MAX ? jc : iend - 1;
+        if (nx <= lim) {  // an expiry effective before the next bind (or before the end)
             if (ne == nx) {
+                const int4 e0 = er;
                 ++e_u;
-                vrc -= (uint32_t)er.y; vrm -= (uint32_t)er.z; vrg -= (uint32_t)er.w; vnr -= 1;
+                er = KS_EROW();
+                vrc -= (uint32_t)e0.y; vrm -= (uint32_t)e0.z; vrg -= (uint32_t)e0.w; vnr -= 1;
             } else {
                 const bool h0 = pe0 == pm, h1 = !h0 && pe1 == pm, h2 = !h0 && !h1 && pe2 == pm,
                            h3 = !h0 && !h1 && !h2;
                 const int jq = h0 ? pj0 : (h1 ? pj1 : (h2 ? pj2 : pj3));
                 pe0 = h0 ? INT_MAX : pe0; pe1 = h1 ? INT_MAX : pe1;
                 pe2 = h2 ? INT_MAX : pe2; pe3 = h3 ? INT_MAX : pe3;
-                const PodRec& p = sh.pod[jq];
-                vrc -= (uint32_t)p.req[0]; vrm -= (uint32_t)p.req[1]; vrg -= (uint32_t)p.req[2]; vnr -= 1;
+                // (an admitted bind's request words are exact: below the capacities)
+                const uint4 pr = *reinterpret_cast<const uint4*>(&sh.brow[jq][0]);
+                vrc -= pr.x; vrm -= pr.y; vrg -= pr.z; vnr -= 1;
             }
             KS_STORE(nx);
             continue;
         }
-        if (jb == INT_MAX) break;
-        const bool fin = j >= 0;
-        if (fin) j = sh.fnext[j];
-        else m &= m - 1;
-        // the bind's request words, key mask, run flag and own-expiry pod: a chunk bind's from its
-        // 16-byte row (one read), a final bind's from the pod record
-        uint32_t q0, q1, q2, meta;
-        if (!fin) {
-            const uint4 br = *reinterpret_cast<const uint4*>(&sh.brow[jb - c0][0]);
-            q0 = br.x; q1 = br.y; q2 = br.z; meta = br.w;
-        } else {
-            const PodRec& p = sh.pod[jb];
-            q0 = (uint32_t)p.req[0]; q1 = (uint32_t)p.req[1]; q2 = (uint32_t)p.req[2];
-            const int x = sh.own[jb];
-            meta = (uint32_t)p.keymask | ((sh.clfl[jb] & kFlRun) ? 8u : 0u) |
-                   ((uint32_t)(x >= 0 ? (int)sh.xeff[x] : kNoOwn) << 16);
+        if (jc == INT_MAX) {
+            if (!ckpt) break;
+            ckpt = false;
+            iend = i_end;
+            if (lost) atomicMin(&sh.cut, from);
+            sh.rd[0][k] = (int32_t)vrc; sh.rd[1][k] = (int32_t)vrm; sh.rd[2][k] = (int32_t)vrg; sh.rd[3][k] = vnr;
+            // (bit 15: a pending slot holds a — non-negative — pod index)
+            sh.ecur[k] = (uint16_t)(e_u | ((pe0 & pe1 & pe2 & pe3) != INT_MAX ? 0x8000 : 0));
+            sh.fcur[k] = -1;
+            KS_STORE(from);
+            continue;
         }
+        // the bind's request words, key mask, run flag and own-expiry pod: its 16-byte row
+        const bool fin = j >= 0;
+        const int jb0 = jb;
+        const uint32_t q0 = br.x, q1 = br.y, q2 = br.z, meta = br.w;
+        const bool adok = ad == 1;
+        if (fin) j = jn;
+        else m &= m - 1;
+        KS_BIND();
         bool ok;
         if (fin) {
-            ok = sh.adm[jb] == 1;
+            ok = adok;
         } else {  // CreatePod admission (kubesim/node/node.go:44-47); saturated words: a request
                   // >= 2^32 - 1 exceeds every capacity (< 2^32 - 1) as its int64 value would
             ok = !lost && vnr < ap;
             if (meta & 1) ok &= (int64_t)vrc + q0 <= ac64;
             if (meta & 2) ok &= (int64_t)vrm + q1 <= am64;
             if (meta & 4) ok &= (int64_t)vrg + q2 <= ag64;
-            sh.adm[jb] = lost ? 2 : (ok ? 1 : 0);
+            sh.adm[jb0] = lost ? 2 : (ok ? 1 : 0);
         }
         if (ok && (meta & 8)) {
             vrc += q0; vrm += q1; vrg += q2; vnr += 1;
-            KS_STORE(jb + 1);
+            KS_STORE(jb0 + 1);
             const int oe = (int)(meta >> 16);
-            if (oe != kNoOwn) KS_PUSH(oe, jb);
+            if (oe != kNoOwn) KS_PUSH(oe, jb0);
         }
     }
+#undef KS_BIND
+#undef KS_EROW
 #undef KS_STORE
 #undef KS_PUSH
     if (sl >= 0) sh.smeta[sl][kMOvf] = (int16_t)ovf;
-    Replayed out;
-    out.v.ac = ac; out.v.am = am; out.v.ag = ag; out.v.ap = ap;
-    out.v.rc = (int32_t)vrc; out.v.rm = (int32_t)vrm; out.v.rg = (int32_t)vrg; out.v.nr = vnr;
-    out.v.taint = 0; out.v.label = 0;
-    out.ecur = e_u;
-    out.hp = (pe0 & pe1 & pe2 & pe3) != INT_MAX;  // any slot holds a (non-negative) pod index
-    out.lost_at = lost_at;
+    NS32 out;
+    out.ac = ac; out.am = am; out.ag = ag; out.ap = ap;
+    out.rc = (int32_t)vrc; out.rm = (int32_t)vrm; out.rg = (int32_t)vrg; out.nr = vnr;
+    out.taint = 0; out.label = 0;
     return out;
 }
 
@@ -653,6 +676,15 @@ __device__ __forceinline__ void chunk_body(const EngineArgs* __restrict__ A, ChS
         const int32_t* q = xtmp[esl];
         sh.erow[tid] = make_int4(sh.xeff[esl], q[0], q[1], q[2]);
     }
+    if (tid < nb) {  // the batch's bind rows
+        const PodRec& p = sh.pod[tid];
+        const int x = sh.own[tid];
+        auto word = [](int64_t q) { return (uint32_t)(q < 0xFFFFFFFFll ? q : 0xFFFFFFFFll); };
+        *reinterpret_cast<uint4*>(&sh.brow[tid][0]) =
+            make_uint4(word(p.req[0]), word(p.req[1]), word(p.req[2]),
+                       (uint32_t)p.keymask | ((sh.clfl[tid] & kFlRun) ? 8u : 0u) |
+                           ((uint32_t)(x >= 0 ? (int)sh.xeff[x] : kNoOwn) << 16));
+    }
     DG(uint64_t ts2 = dstamp(); uint64_t cs_e = 0, cs_r = 0, cs_x = 0;)
     __syncthreads();
 
@@ -665,32 +697,42 @@ __device__ __forceinline__ void chunk_body(const EngineArgs* __restrict__ A, ChS
         // (1) pre-chunk nodes: replay each over [c0, c1) into its first final binder's slot, then
         // per chunk pod the top two keys (lane = pod, waves over nodes)
         if (c0 > 0) {
-            // rebase every node with events to c0 (binds < c0, events effective < c0)
+            // every node with events is rebased to c0 (binds < c0, events effective < c0).  A node
+            // bound before the chunk: one replay, spread over the waves (pod j's thread is 2 j),
+            // from its base to c0 — the checkpoint — and on over [c0, c1) into its first binder's
+            // row.  An E node no pod has bound has expiry slots alone: its cursor moves to c0.
             for (int k = tid; k < ncid; k += kThreads) {
-                if (sh.ceix[k] >= 0 || sh.fhead[k] >= 0) {
-                    const Replayed r = replay(sh, k, tb, false, c0, c0, -1, c0);
-                    if (r.lost_at != INT_MAX) atomicMin(&sh.cut, c0);
-                    sh.rd[0][k] = r.v.rc; sh.rd[1][k] = r.v.rm; sh.rd[2][k] = r.v.rg; sh.rd[3][k] = r.v.nr;
-                    sh.ecur[k] = (uint16_t)(r.ecur | (r.hp ? 0x8000 : 0));
-                    sh.fcur[k] = -1;
+                const int ex = sh.ceix[k];
+                if (ex < 0 || sh.fhead[k] >= 0) continue;
+                const int e_end = sh.eoff[ex + 1];
+                int e_u = sh.ecur[k];  // (no binds: no pending own expiries, bit 15 clear)
+                uint32_t vrc = (uint32_t)sh.rd[0][k], vrm = (uint32_t)sh.rd[1][k], vrg = (uint32_t)sh.rd[2][k];
+                int32_t vnr = sh.rd[3][k];
+                const int e0 = e_u;
+                for (; e_u < e_end; ++e_u) {
+                    const int4 er = sh.erow[e_u];
+                    if (er.x >= c0) break;
+                    vrc -= (uint32_t)er.y; vrm -= (uint32_t)er.z; vrg -= (uint32_t)er.w; vnr -= 1;
                 }
+                if (e_u != e0) {
+                    sh.rd[0][k] = (int32_t)vrc; sh.rd[1][k] = (int32_t)vrm; sh.rd[2][k] = (int32_t)vrg; sh.rd[3][k] = vnr;
+                    sh.ecur[k] = (uint16_t)e_u;
+                }
+            }
+            if ((tid & 1) == 0 && (tid >> 1) < c0) {
+                const int j = tid >> 1;
+                const int k = sh.wf[j];
+                if (k >= 0 && sh.fhead[k] == j) (void)replay<true>(sh, k, tb, false, c0, c0, j, c1);
+                else sh.smeta[j][kMCid] = -1;  // (a pod that is no first binder has no row)
             }
             __syncthreads();
             DG(acc_rbase += dstamp() - t0;)
             tb = c0;
             if (sh.cut <= c0) {  // an own expiry could not be tracked: commit the pods before c0
-                committed = c0;
+                committed = c0;  // (before any row of the chunk is used)
                 stop_code = 1;
                 break;
             }
-            // replays spread over the waves: pod j's thread is 2 j
-            if ((tid & 1) == 0 && (tid >> 1) < c0) {
-                const int j = tid >> 1;
-                const int k = sh.wf[j];
-                if (k >= 0 && sh.fhead[k] == j) (void)replay(sh, k, tb, false, c0, c0, j, c1);
-                else sh.smeta[j][kMCid] = -1;
-            }
-            __syncthreads();
             DG(uint64_t tr1 = dstamp(); acc_rb += tr1 - t0;)
             {  // eight lanes per chunk pod (pod c0 + tid / 8), lane s8 takes the rows j = s8 + 8 t
                 const int pi = tid >> 3, s8 = tid & 7;
@@ -763,16 +805,6 @@ __device__ __forceinline__ void chunk_body(const EngineArgs* __restrict__ A, ChS
 
         // (2) sweeps
         DG(uint64_t t1 = dstamp(); acc_cd += t1 - t0;)
-        if (wave == 1 && c0 + lane < c1) {  // the chunk's bind rows (beside the guess in wave 0)
-            const int i = c0 + lane;
-            const PodRec& p = sh.pod[i];
-            const int x = sh.own[i];
-            auto word = [](int64_t q) { return (uint32_t)(q < 0xFFFFFFFFll ? q : 0xFFFFFFFFll); };
-            *reinterpret_cast<uint4*>(&sh.brow[lane][0]) =
-                make_uint4(word(p.req[0]), word(p.req[1]), word(p.req[2]),
-                           (uint32_t)p.keymask | ((sh.clfl[i] & kFlRun) ? 8u : 0u) |
-                               ((uint32_t)(x >= 0 ? (int)sh.xeff[x] : kNoOwn) << 16));
-        }
         // (2a) The guess: exclusion-only rounds (w_i = the first static candidate no earlier pod
         // takes; no evaluation, no replay) to their fixed point — the sequential greedy over the
         // lists, without the piles a cold start makes (every pod on its own best node).  One wave,
@@ -1233,7 +1265,7 @@ __device__ __forceinline__ void chunk_body(const EngineArgs* __restrict__ A, ChS
     if (tid < h_end && xq >= 0) gptr(a.expired)[xq] = 1;  // (h_end <= e_cnt <= kSlots <= kThreads)
     for (int k = tid; k < ncid; k += kThreads) {
         if (sh.ceix[k] >= 0 || sh.fhead[k] >= 0) {
-            const NS32 v = replay(sh, k, tb, false, 0, 0, -1, c).v;
+            const NS32 v = replay(sh, k, tb, false, 0, 0, -1, c);
             const int32_t n = sh.cnode[k];
             a.s.rc[n] = use64(v.rc); a.s.rm[n] = use64(v.rm); a.s.rg[n] = use64(v.rg); a.s.nr[n] = v.nr;
         }
