@@ -139,9 +139,14 @@ ks_status ks_create(const ks_config* cfg, ks_engine** out);
 void ks_destroy(ks_engine* eng);
 
 /* Scenario groups (BASELINE.json configs[3]: independent what-if clusters × pod traces).  A
- * group owns a stream and up to max_scenarios engines created with ks_group_add (same device and
- * batch size; ks_load_nodes / ks_submit_pods / ks_usage / ks_filter / ks_score / ks_step work on
- * them as on any engine).  ks_group_step advances every member by `ticks` ticks with one launch
+ * group owns a stream and up to max_scenarios engines created with ks_group_add (same device;
+ * ks_load_nodes / ks_submit_pods / ks_usage / ks_filter / ks_score / ks_step work on them as on
+ * any engine).  Members may differ in everything else — node count, batch size (the default
+ * already follows the node count), filters and scorers, evaluator class: the grid is sized by the
+ * largest member, and the group runs the widest evaluator, the 32-bit key table and the role-split
+ * resolver as soon as one member needs them (each is exact on the others' domains too).  A member
+ * without nodes, or one that has stopped, sits the step out with its status.
+ * ks_group_step advances every member by `ticks` ticks with one launch
  * per kernel for all of them (scenario = a grid dimension, one resolve workgroup each) — the
  * reference would run one KubeSim.Run per scenario (kubesim/kubesim.go:90-123).  Per member i:
  * binds into out[i * cap ...] (out may be NULL), their count in n_out[i] and the member's status

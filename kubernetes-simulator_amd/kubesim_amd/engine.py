@@ -488,7 +488,14 @@ class Group:
         dt = np.dtype([("pod", "<i8"), ("node", "<i4"), ("status", "<i4"), ("tick", "<i8")])
         allb = np.frombuffer(self._out, dtype=dt, count=S * cap) if S * cap else np.zeros(0, dt)
         self._cap = cap
+        self._full_counts = n
         return allb, np.minimum(n, cap), st, dict(step_ms=stats.step_ms, launches=stats.launches, pods=stats.pods)
+
+    @property
+    def full_counts(self):
+        """The binds each member made in the last :meth:`step` as ``ks_group_step`` reported them
+        (``n_out``): not clipped to ``cap``, so a member whose count exceeds ``cap`` lost rows."""
+        return self._full_counts.copy()
 
     def split(self, binds, counts):
         """Per-member copies of the binds returned by :meth:`step`."""
