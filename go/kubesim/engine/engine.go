@@ -488,6 +488,65 @@ func (e *Engine) PlaceAt(t int64, s *Shapes, shapeOf []int32, after bool) (*Plac
 	return r, err
 }
 
+// Drain preview constants (include/ks_engine.h): the most evicted pods per DrainAt call, the words
+// of Evictions.Info.
+const (
+	DrainMaxPods = 65536
+	DrainInfo    = 6
+)
+
+// Eviction is one evicted pod's outcome (ks_eviction, 40 bytes): the pod's FIFO index, the drained
+// node it ran on, and its Placement fields on the cluster without the drained nodes.
+type Eviction struct {
+	Pod               int64
+	From, Node        int32
+	Status, _         int32
+	Score, Candidates int64
+}
+
+// Evictions is the result of DrainAt: one Eviction per evicted pod in FIFO order, After the
+// requested state (4 values per node) at t with the drained nodes' rows zero plus every Ok
+// re-placement, and Info = rounds of the device algorithm, re-placed Ok, OverCapacity, not found,
+// segments, drained nodes that had no running pod.
+type Evictions struct {
+	Pods  []Eviction
+	After []int64
+	Info  [DrainInfo]int64
+}
+
+// DrainAt is where the pods running on `nodes` at tick t <= Tick() would go if those nodes left
+// k.nodes (kubesim/kubesim.go:168-206 range over it): every pod running on them is evicted and
+// handed in FIFO order to scheduleOne (kubesim.go:143-225) on a private copy of the state at t
+// without the drained nodes (ks_drain_at).  nodes are distinct indices in [0, Nodes()).  No engine
+// state changes.  It makes the sizing call itself; more than DrainMaxPods evicted pods are
+// ErrOutOfDomain.
+func (e *Engine) DrainAt(t int64, nodes []int32, after bool) (*Evictions, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	if len(nodes) == 0 && e.n > 0 {
+		return nil, strongerrors.InvalidArgument(errors.New("drain: no nodes given"))
+	}
+	nd := nodes
+	if len(nd) == 0 {
+		nd = make([]int32, 1) // n = 0: the pointer must not be NULL, the count is 0
+	}
+	r := &Evictions{}
+	if after {
+		r.After = make([]int64, 4*e.n+1)
+	}
+	info := (*C.int64_t)(unsafe.Pointer(&r.Info[0]))
+	var k C.int64_t
+	rc := C.ks_drain_at(e.h, C.int64_t(t), C.int32_t(len(nodes)), i32p(nd), nil, 0, &k, i64p(r.After), info)
+	if rc == C.KS_ERANGE && k > 0 && k <= DrainMaxPods {
+		r.Pods = make([]Eviction, int(k))
+		rc = C.ks_drain_at(e.h, C.int64_t(t), C.int32_t(len(nodes)), i32p(nd),
+			(*C.ks_eviction)(unsafe.Pointer(&r.Pods[0])), k, &k, i64p(r.After), info)
+	}
+	if after {
+		r.After = r.After[:4*e.n]
+	}
+	return r, status(e, rc)
+}
+
 // Nodes is the node count of LoadNodes.
 func (e *Engine) Nodes() int { return e.n }
 

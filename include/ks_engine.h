@@ -29,6 +29,8 @@
  *                                 repeatedly: how many more pods of a shape each node would take
  *   ks_place_at ................. scheduleOne (kubesim/kubesim.go:143-225) for k preview pods on a
  *                                 private copy of a past tick's state: where they would be bound
+ *   ks_drain_at ................. the same for the pods running on a node set that leaves k.nodes
+ *                                 (kubesim/kubesim.go:168-206 range over it): where they would go
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
  *   ks_pod_lookup / ks_node_pods  Node.GetPod / GetPodStatus / GetPodList (kubesim/node/node.go:62-93)
  *   ks_group_* .................. one KubeSim.Run per what-if scenario, stepped together
@@ -387,6 +389,53 @@ ks_status ks_place_at(ks_engine* eng, int64_t t, int32_t n_shapes, const int64_t
                       const int32_t* shape_of /* [k], or NULL: k == n_shapes, pod j is shape j */,
                       ks_placement* out /* [k] */, int64_t* after_out /* [n][4] or NULL */,
                       int64_t* info_out /* [KS_PLACE_INFO] or NULL */);
+
+/* Drain preview: where the pods running on a set of nodes would go if those nodes were taken out, at
+ * any past tick ("at tick t" as above: after tick t's bind, 0 <= t <= the current tick).  No engine
+ * state changes.
+ *
+ * nodes[n_drain] are distinct node indices in [0, n), 1 <= n_drain <= n (with n = 0: n_drain = 0).
+ * The drained nodes leave k.nodes: from then on they are in no Filter loop and no score map
+ * (kubesim/kubesim.go:168-206 range over k.nodes).  Every pod running on a drained node at t is
+ * evicted — running as ks_requested_at counts it: bound Ok with 0 <= t - bind tick < its run length
+ * (Pod.IsRunning, kubesim/pod/pod.go:67-69); OverCapacity pods and finished pods are not evicted.
+ * The evicted pods are handed in FIFO order (ascending pod index), all at tick t with nothing
+ * finishing in between, to scheduleOne (kubesim/kubesim.go:143-225, kubesim/node/node.go:36-60) on a
+ * private copy of the state: ks_requested_at(t) with the drained nodes' rows emptied.  Each pod goes
+ * through the engine's configured filter mode, filters and scorers exactly as in ks_place_at; its own
+ * record supplies req / keymask / tol / sel, its flags are ignored.  Statuses, the rule that a
+ * KS_PLACE_NOT_FOUND pod changes nothing and the preview goes on, score and candidates are
+ * ks_place_at's; in KS_FILTER_REFERENCE_LITERAL mode with scorers candidates = n - n_drain.
+ * Keys: ks_submit_pods refuses a key reused while an earlier holder may still run, so the Store of an
+ * evicted pod on its new node (node.go:58) can only replace a finished pod, which changes no totals.
+ *
+ * *n_out = the number of evicted pods, always.  If it exceeds cap or KS_DRAIN_MAX_PODS: KS_ERANGE and
+ * nothing else is written — the caller sizes out and calls again; cap = 0 with out NULL is the sizing
+ * call (KS_OK when nothing is evicted).  out[*n_out]: the evicted pod, the node it ran on, and its
+ * ks_placement fields.  after_out (may be NULL): [n][4] milli-units and running pods, the emptied state
+ * plus every Ok re-placement; the drained nodes' rows are zero.  info_out (may be NULL):
+ * {rounds of the device algorithm, re-placed Ok, OverCapacity, not found, segments (the rounds take
+ * KS_PLACE_MAX_SHAPES distinct shapes and KS_PLACE_MAX_PODS pods at a time), drained nodes that had no
+ * running pod}.  With n = 0 or no evicted pod: KS_OK, *n_out = 0, after_out = the emptied state.
+ * KS_EINVAL: a NULL engine, nodes or n_out (before the handle is read); out NULL with cap > 0; cap < 0;
+ * a node out of range or listed twice; n_drain out of range; t out of range; no nodes loaded.  It
+ * answers after an aborted run, on sharded engines and on scenario-group members, like the state
+ * queries above: it reads the bind arrays, the pod records and the cluster's alloc / taints / labels
+ * only. */
+#define KS_DRAIN_MAX_PODS 65536
+#define KS_DRAIN_INFO 6
+typedef struct {
+    int64_t pod;        /* the evicted pod (FIFO index) */
+    int32_t from;       /* the drained node it ran on */
+    int32_t node;       /* the node it would be bound to, -1 when none */
+    int32_t status;     /* KS_POD_OK, KS_POD_OVER_CAPACITY, KS_PLACE_NOT_FOUND */
+    int32_t pad;
+    int64_t score;      /* aggregated score of the chosen node, -1 when none */
+    int64_t candidates; /* nodes with an entry in the nodeScore map at this pod's turn */
+} ks_eviction;
+ks_status ks_drain_at(ks_engine* eng, int64_t t, int32_t n_drain, const int32_t* nodes /* [n_drain] */,
+                      ks_eviction* out /* [cap] or NULL */, int64_t cap, int64_t* n_out,
+                      int64_t* after_out /* [n][4] or NULL */, int64_t* info_out /* [KS_DRAIN_INFO] or NULL */);
 
 /* Name-keyed queries over the binds made so far (Node.GetPod / GetPodStatus / GetPodList,
  * kubesim/node/node.go:62-93).  ks_pod_lookup: the FIFO index of the pod stored on `node` under

@@ -1321,11 +1321,126 @@ struct PlaceBufs {
     int32_t* rb;
 };
 // one round from pod `first`: scan + merge for the shapes in `active` (bit j: a pod >= first has
-// shape j), then the resolver
+// shape j), then the resolver.  cordon (ks_drain_at; null: none): bit nd % 32 of word nd / 32 takes
+// node nd out of the scan.
+//
+// Exactness with a cordon.  The scan writes key 0 for a cordoned node, whatever its state: to every
+// shape it is a node without an entry in the score map, which is what leaving k.nodes means
+// (kubesim/kubesim.go:168-206 never visit it).  A block list, a candidate count and the merged top-L
+// are functions of the keys alone, so they are those of the cluster without the cordoned nodes.  The
+// resolver reads nodes through list entries (non-zero keys) and through the changed set (winners,
+// which come from list entries): key 0 is never a list entry, so a cordoned node is never S, never
+// joins the changed set, never contributes to D and is never committed — place_decide's argument
+// above holds verbatim over the non-cordoned nodes.
 hipError_t launch_place_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, int32_t first, uint64_t active,
-                              hipStream_t st);
+                              hipStream_t st, const uint32_t* cordon = nullptr);
 // after[n][4] from state [4][n_pad], the three quantities times sc
 hipError_t launch_place_after(const int64_t* state, int64_t n_pad, int32_t n_nodes, const QScale& sc, long long* after,
                               hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
+// Drain preview (ks_drain_at, ks_drain.hip): the pods running at tick t on a set of nodes, in FIFO
+// order, re-placed by the rounds above on the state at t without those nodes (the cordon).
+//
+// The evicted pods are gathered by an ordered compaction without atomics over the candidate pod
+// blocks the host lists in ascending order: a count per block (wave ballots), an exclusive scan of
+// the counts, and a fill with the same predicate whose rank is
+//   the block's offset + the selected pods of the waves before it + the selected lanes below it,
+// so the output order is the pod order whatever the order of execution.  The records are the pods'
+// own (whole device units), so the rounds always run in device units (scale 1).
+//
+// A round takes at most kPlaceMaxShapes distinct shapes and kPlaceMaxPods pods: the host feeds the
+// evicted pods in segments (drain_segment) and the scratch state carries from one to the next.
+// ---------------------------------------------------------------------------------------------
+constexpr int kDrainBlk = 256;             // pods per gather workgroup (= the usage index's block)
+constexpr int64_t kDrainMaxPods = 65536;   // KS_DRAIN_MAX_PODS
+
+struct Eviction {  // = ks_eviction
+    int64_t pod;
+    int32_t from, node, status, pad;
+    int64_t score, candidates;
+};
+static_assert(sizeof(Eviction) == 40, "ks_eviction layout");
+
+// the set lanes of a wave ballot below `lane` (v_mbcnt on the device)
+__host__ __device__ __forceinline__ int32_t drain_below(uint64_t ballot, int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lane;
+    return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+#else
+    return __builtin_popcountll(ballot & ((1ull << lane) - 1ull));
+#endif
+}
+
+// rank of a selected pod: its block's offset, the counts of the waves before its own, the lanes below it
+__host__ __device__ __forceinline__ int64_t drain_rank(int64_t block_off, const int32_t* wave_cnt, int wave,
+                                                       uint64_t ballot, int lane) {
+    int64_t r = block_off;
+    for (int w = 0; w < wave; ++w) r += wave_cnt[w];
+    return r + drain_below(ballot, lane);
+}
+
+// whether a node's bit is set in a cordon bitmap
+__host__ __device__ __forceinline__ bool drain_cordoned(const uint32_t* cordon, int32_t nd) {
+    return (cordon[nd >> 5] >> (nd & 31)) & 1u;
+}
+
+// two pods have the same shape: masked requests, keymask, tol, sel (flags are ignored)
+__host__ __device__ __forceinline__ bool drain_same_shape(const PodRec& a, const PodRec& b) {
+    if (a.keymask != b.keymask || a.tol != b.tol || a.sel != b.sel) return false;
+    for (int c = 0; c < 3; ++c)
+        if ((a.keymask >> c & 1) && a.req[c] != b.req[c]) return false;
+    return true;
+}
+
+// The segment that starts at pod `start` of recs[n]: it closes before the pod that would be its
+// (kPlaceMaxShapes + 1)-th distinct shape or its (kPlaceMaxPods + 1)-th pod.  Returns its end
+// (exclusive; > start when start < n), its distinct shapes in shapes[0, *n_shapes) in order of first
+// appearance (masked requests, flags 0) and shape_of[i - start] for its pods.
+inline int64_t drain_segment(const PodRec* recs, int64_t n, int64_t start, PodRec* shapes, int32_t* n_shapes,
+                             int32_t* shape_of) {
+    int32_t ns = 0;
+    int64_t i = start;
+    for (; i < n && i - start < kPlaceMaxPods; ++i) {
+        int32_t j = 0;
+        while (j < ns && !drain_same_shape(shapes[j], recs[i])) ++j;
+        if (j == ns) {
+            if (ns == kPlaceMaxShapes) break;
+            PodRec r{};
+            for (int c = 0; c < 3; ++c) r.req[c] = (recs[i].keymask >> c & 1) ? recs[i].req[c] : 0;
+            r.tol = recs[i].tol; r.sel = recs[i].sel; r.keymask = recs[i].keymask;
+            shapes[ns++] = r;
+        }
+        shape_of[i - start] = j;
+    }
+    *n_shapes = ns;
+    return i;
+}
+
+// Scratch of the gather (device): cordon [ceil(n / 32)]; bcnt / boff [nblocks]; total [1];
+// ev_pod / ev_from / ev_rec [cap] (the fill writes ranks < cap only).
+struct DrainBufs {
+    const uint32_t* cordon;
+    int32_t* bcnt;
+    int32_t* boff;
+    long long* total;
+    long long* ev_pod;
+    int32_t* ev_from;
+    PodRec* ev_rec;
+    int64_t cap;
+};
+// bcnt, boff and *total over the candidate blocks (ascending) of the pods < q_hi
+hipError_t launch_drain_count(const int32_t* blocks, int64_t nblocks, int64_t q_hi, int64_t t, int32_t n_nodes,
+                              const int32_t* b_node, const int32_t* b_status, const int64_t* t0, const int32_t* dur,
+                              const DrainBufs& d, hipStream_t st);
+// the evicted pods' rows, in pod order (after launch_drain_count on the same arguments)
+hipError_t launch_drain_fill(const int32_t* blocks, int64_t nblocks, int64_t q_hi, int64_t t, int32_t n_nodes,
+                             const int32_t* b_node, const int32_t* b_status, const int64_t* t0, const int32_t* dur,
+                             const PodRec* pods, const DrainBufs& d, hipStream_t st);
+// zero the cordoned nodes' four words of state [4][n_pad]
+hipError_t launch_drain_clear(const uint32_t* cordon, int32_t n_nodes, int64_t* state, int64_t n_pad, hipStream_t st);
+// out[i] = {ev_pod[i], ev_from[i], placed[i]} for i < n_ev
+hipError_t launch_drain_pack(const long long* ev_pod, const int32_t* ev_from, const Placement* placed, int64_t n_ev,
+                             Eviction* out, hipStream_t st);
 
 }  // namespace ks

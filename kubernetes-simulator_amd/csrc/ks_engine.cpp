@@ -2362,6 +2362,177 @@ ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* 
     return KS_OK;
 }
 
+// ---- drain preview (ks_drain.hip) ---------------------------------------------------------------
+// The pods running at t on the cordoned nodes, gathered on the device in FIFO order (count, scan,
+// fill: the host reads the 8-byte total first and sizes the rest from it), then ks_place_at's round
+// loop over them in segments of at most KS_PLACE_MAX_SHAPES distinct shapes and KS_PLACE_MAX_PODS
+// pods (ks::drain_segment) on the state at t with the cordoned rows zeroed.  The pods' records are
+// whole device units, so the rounds run in device units throughout; a round commits its changed
+// nodes to the scratch, which carries the state from one segment to the next.
+static_assert(KS_DRAIN_MAX_PODS == ks::kDrainMaxPods && KS_DRAIN_INFO == 6 && sizeof(ks_eviction) == sizeof(ks::Eviction) &&
+              offsetof(ks_eviction, pod) == offsetof(ks::Eviction, pod) && offsetof(ks_eviction, from) == offsetof(ks::Eviction, from) &&
+              offsetof(ks_eviction, node) == offsetof(ks::Eviction, node) && offsetof(ks_eviction, status) == offsetof(ks::Eviction, status) &&
+              offsetof(ks_eviction, score) == offsetof(ks::Eviction, score) &&
+              offsetof(ks_eviction, candidates) == offsetof(ks::Eviction, candidates) && kUBlk == ks::kDrainBlk,
+              "ks_drain_at constants and record");
+
+ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* nodes, ks_eviction* out, int64_t cap,
+                      int64_t* n_out, int64_t* after_out, int64_t* info_out) {
+    if (!e || !nodes || !n_out || cap < 0 || (cap > 0 && !out)) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    if (n_drain < (n ? 1 : 0) || n_drain > n)
+        return fail(e, KS_EINVAL, "drain: %d nodes outside [%d, %lld]", (int)n_drain, n ? 1 : 0, (long long)n);
+    const int64_t CW = (n + 31) / 32;
+    std::vector<uint32_t> h_cordon(CW, 0u);
+    for (int32_t j = 0; j < n_drain; j++) {
+        const int32_t nd = nodes[j];
+        if (nd < 0 || nd >= n) return fail(e, KS_EINVAL, "drain: node %d outside [0, %lld)", (int)nd, (long long)n);
+        if (h_cordon[nd >> 5] >> (nd & 31) & 1u) return fail(e, KS_EINVAL, "drain: node %d is listed twice", (int)nd);
+        h_cordon[nd >> 5] |= 1u << (nd & 31);
+    }
+    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
+    int64_t info[KS_DRAIN_INFO] = {0, 0, 0, 0, 0, 0};
+    if (n == 0) {
+        *n_out = 0;
+        if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
+        return KS_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    const int64_t q_hi = bound_by(e, t);
+    const int64_t nb = usage_blocks(e, t, q_hi);
+    if (nb * kUBlk > INT32_MAX) return fail(e, KS_EINVAL, "drain: tick %lld holds too many candidate pods", (long long)t);
+    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long), L = ks::kPlaceL, S = KS_PLACE_MAX_SHAPES;
+    constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
+    constexpr int64_t EW = sizeof(ks::Eviction) / sizeof(unsigned long long);
+    auto even = [](int64_t x) { return (x + 1) & ~(int64_t)1; };
+    // ---- the gather's count: cordon, block counts and offsets, the total (int32 scratch) ----
+    const int64_t o_bcnt = CW, o_boff = o_bcnt + nb, o_total = even(o_boff + nb), o_cnt = o_total + 2;
+    HIPCHK(e, e->d_qi.reserve(o_cnt + S * nblk, e->st));
+    ks::DrainBufs d{};
+    d.cordon = (const uint32_t*)e->d_qi.p;
+    d.bcnt = e->d_qi.p + o_bcnt;
+    d.boff = e->d_qi.p + o_boff;
+    d.total = (long long*)(e->d_qi.p + o_total);
+    HIPCHK(e, hipMemcpyAsync(e->d_qi.p, h_cordon.data(), sizeof(uint32_t) * CW, hipMemcpyHostToDevice, e->st));
+    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_drain_count(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p, d,
+                                     e->st));
+    long long total = 0;
+    HIPCHK(e, hipMemcpyAsync(&total, d.total, sizeof(total), hipMemcpyDeviceToHost, e->st));  // 8 bytes first
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (total < 0 || total > nb * kUBlk) return fail(e, KS_EDEVICE, "drain: the gather counted %lld pods", total);
+    const int64_t n_ev = total;
+    *n_out = n_ev;
+    if (n_ev > cap || n_ev > KS_DRAIN_MAX_PODS)
+        return fail(e, KS_ERANGE, "drain: %lld evicted pods, room for %lld (at most %d per call)", (long long)n_ev,
+                    (long long)std::min<int64_t>(cap, KS_DRAIN_MAX_PODS), KS_DRAIN_MAX_PODS);
+    // ---- the rest of the scratch, sized from the total ----
+    const int64_t up_words = W * S + (KS_PLACE_MAX_PODS + 1) / 2;  // per segment: the shape records, then shape_of
+    int64_t o = 0;
+    const int64_t o_state = o;   o += 4 * np;
+    const int64_t o_up = o;      o += up_words;
+    const int64_t o_lists = o;   o += S * nblk * L;
+    const int64_t o_top = o;     o += S * L;
+    const int64_t o_cc = o;      o += S;
+    const int64_t o_rb = o;      o += 2;
+    const int64_t o_placed = o;  o += PW * n_ev;
+    const int64_t o_pod = o;     o += n_ev;
+    const int64_t o_from = o;    o = even(o + (n_ev + 1) / 2);
+    const int64_t o_rec = o;     o += W * n_ev;    // 16-byte aligned: an even word offset
+    const int64_t o_evict = o;   o += EW * n_ev;
+    const int64_t o_after = o;   o += 4 * n;
+    static_assert((W * S) % 2 == 0, "shape_of follows the shape records on a 16-byte boundary");
+    HIPCHK(e, e->d_qs.reserve(o, e->st));
+    unsigned long long* w = e->d_qs.p;
+    ks::PlaceBufs b{};
+    b.state = (int64_t*)(w + o_state);
+    b.n_pad = np;
+    unsigned long long* up = w + o_up;
+    b.shapes = (const ks::PodRec*)up;
+    b.shape_of = (const int32_t*)(up + W * S);
+    b.lists = (uint64_t*)(w + o_lists);
+    b.top = (uint64_t*)(w + o_top);
+    b.ccount = (long long*)(w + o_cc);
+    b.rb = (int32_t*)(w + o_rb);
+    b.cnt = e->d_qi.p + o_cnt;
+    ks::Placement* placed = (ks::Placement*)(w + o_placed);
+    d.ev_pod = (long long*)(w + o_pod);
+    d.ev_from = (int32_t*)(w + o_from);
+    d.ev_rec = (ks::PodRec*)(w + o_rec);
+    d.cap = n_ev;
+    ks::Eviction* evict = (ks::Eviction*)(w + o_evict);
+    long long* after = (long long*)(w + o_after);
+    const ks::QScale one{{1, 1, 1}};
+    HIPCHK(e, hipMemsetAsync(b.state, 0, sizeof(unsigned long long) * 4 * np, e->st));
+    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
+                                   e->pods.p, one, 1, np, (unsigned long long*)b.state, e->st));
+    HIPCHK(e, ks::launch_drain_clear(d.cordon, (int32_t)n, b.state, np, e->st));
+    std::vector<ks::Eviction> h_ev(n_ev);
+    if (n_ev) {
+        HIPCHK(e, ks::launch_drain_fill(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
+                                        e->pods.p, d, e->st));
+        std::vector<ks::PodRec> recs(n_ev);
+        HIPCHK(e, hipMemcpyAsync(recs.data(), d.ev_rec, sizeof(ks::PodRec) * n_ev, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        std::vector<unsigned long long> h_up(up_words, 0ull);
+        std::vector<int32_t> so(KS_PLACE_MAX_PODS);
+        ks::PodRec seg_shapes[KS_PLACE_MAX_SHAPES];
+        for (int64_t start = 0; start < n_ev;) {
+            int32_t ns = 0;
+            const int64_t end = ks::drain_segment(recs.data(), n_ev, start, seg_shapes, &ns, so.data());
+            const int32_t k = (int32_t)(end - start);
+            if (k < 1 || ns < 1) return fail(e, KS_EDEVICE, "drain: empty segment at evicted pod %lld", (long long)start);
+            std::memcpy(h_up.data(), seg_shapes, sizeof(ks::PodRec) * ns);
+            std::memcpy(h_up.data() + W * S, so.data(), sizeof(int32_t) * k);
+            HIPCHK(e, hipMemcpyAsync(up, h_up.data(), sizeof(unsigned long long) * (W * S + (k + 1) / 2),
+                                     hipMemcpyHostToDevice, e->st));
+            b.out = placed + start;
+            const ks::PlaceCfg pc{e->dc, one, (int32_t)n, k, ns, (int32_t)nblk};
+            int32_t first = 0;
+            int64_t rounds = 0;
+            while (first < k) {
+                uint64_t active = 0;
+                for (int32_t j = first; j < k; j++) active |= 1ull << so[j];
+                HIPCHK(e, ks::launch_place_round(e->s, pc, b, first, active, e->st, d.cordon));
+                int32_t rb[4] = {0, 1, 0, 0};
+                HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
+                HIPCHK(e, hipStreamSynchronize(e->st));
+                // as ks_place_at: a round decides its first pod at the least
+                if (rb[1] != 0 || rb[0] <= first || rb[0] > k || ++rounds > k)
+                    return fail(e, KS_EDEVICE, "drain: the round from evicted pod %lld decided no pod",
+                                (long long)(start + first));
+                first = rb[0];
+            }
+            info[0] += rounds;
+            info[4]++;
+            start = end;
+        }
+        HIPCHK(e, ks::launch_drain_pack(d.ev_pod, d.ev_from, placed, n_ev, evict, e->st));
+        HIPCHK(e, hipMemcpyAsync(h_ev.data(), evict, sizeof(ks::Eviction) * n_ev, hipMemcpyDeviceToHost, e->st));
+    }
+    if (after_out) {
+        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, milli_scale(e), after, e->st));
+        HIPCHK(e, hipMemcpyAsync(after_out, after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    std::vector<uint32_t> seen(CW, 0u);
+    int64_t busy = 0;
+    for (int64_t i = 0; i < n_ev; i++) {
+        const ks::Eviction& v = h_ev[i];
+        info[v.status == KS_POD_OK ? 1 : v.status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
+        if ((uint32_t)v.from < (uint32_t)n && !(seen[v.from >> 5] >> (v.from & 31) & 1u)) {
+            seen[v.from >> 5] |= 1u << (v.from & 31);
+            busy++;
+        }
+    }
+    info[5] = n_drain - busy;
+    if (n_ev) std::memcpy(out, h_ev.data(), sizeof(ks_eviction) * n_ev);
+    if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
+    return KS_OK;
+}
+
 uint64_t ks_node_mix(int64_t node) {
     uint64_t z = (uint64_t)(node + 1) * 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -48,15 +48,20 @@ __device__ __forceinline__ NodeV place_load(const NodeSoA& s, const int64_t* sta
 // takes shapes of the pass: four keys per lane, L times a wave max (DPP) whose owner drops its key —
 // keys are distinct, so exactly one lane does.  lists[(shape * nblk + block) * L ..] descending,
 // 0-padded; cnt[shape * nblk + block] the block's non-zero keys.
+// kCordon (ks_drain_at): a node whose bit is set in `cordon` gets key 0 for every shape — it is in
+// no list and no count (the argument is in ks_device.h, above launch_place_round).
 // ---------------------------------------------------------------------------------------------
+template <bool kCordon>
 __global__ __launch_bounds__(kPBlk) void place_scan_kernel(NodeSoA s, const int64_t* __restrict__ state, int64_t n_pad,
                                                           PlaceCfg pc, const PodRec* __restrict__ shapes,
                                                           uint64_t active, uint64_t* __restrict__ lists,
-                                                          int32_t* __restrict__ cnt) {
+                                                          int32_t* __restrict__ cnt,
+                                                          const uint32_t* __restrict__ cordon) {
     __shared__ uint64_t tab[kPChunk][kPBlk];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int32_t nd = blockIdx.x * kPBlk + threadIdx.x;
-    const bool real = nd < pc.n_nodes;
+    bool real = nd < pc.n_nodes;
+    if constexpr (kCordon) real = real && !drain_cordoned(cordon, nd);
     NodeV v{};
     if (real) v = place_load(s, state, n_pad, pc.sc, nd);
     for (int base = 0; base < pc.n_shapes; base += kPChunk) {
@@ -285,12 +290,17 @@ __global__ __launch_bounds__(256) void place_after_kernel(const int64_t* __restr
 }  // namespace
 
 hipError_t launch_place_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, int32_t first, uint64_t active,
-                              hipStream_t st) {
+                              hipStream_t st, const uint32_t* cordon) {
     if (pc.n_nodes <= 0 || pc.n_shapes <= 0 || pc.n_shapes > kPlaceMaxShapes || pc.k <= 0 || pc.k > kPlaceMaxPods ||
         first < 0 || first >= pc.k || pc.nblk != (pc.n_nodes + kPBlk - 1) / kPBlk)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(place_scan_kernel, dim3((unsigned)pc.nblk), dim3(kPBlk), 0, st, s, (const int64_t*)b.state,
-                       b.n_pad, pc, b.shapes, active, b.lists, b.cnt);
+    if (cordon)
+        hipLaunchKernelGGL(place_scan_kernel<true>, dim3((unsigned)pc.nblk), dim3(kPBlk), 0, st, s,
+                           (const int64_t*)b.state, b.n_pad, pc, b.shapes, active, b.lists, b.cnt, cordon);
+    else
+        hipLaunchKernelGGL(place_scan_kernel<false>, dim3((unsigned)pc.nblk), dim3(kPBlk), 0, st, s,
+                           (const int64_t*)b.state, b.n_pad, pc, b.shapes, active, b.lists, b.cnt,
+                           (const uint32_t*)nullptr);
     hipLaunchKernelGGL(place_merge_kernel, dim3((unsigned)pc.n_shapes), dim3(kWave), 0, st, (const uint64_t*)b.lists,
                        (const int32_t*)b.cnt, pc.nblk, active, b.top, b.ccount);
     hipLaunchKernelGGL(place_resolve_kernel, dim3(1), dim3(kPRes), 0, st, s, b.state, b.n_pad, pc, b.shapes, b.shape_of,

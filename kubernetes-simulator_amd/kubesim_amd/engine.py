@@ -17,7 +17,9 @@ scheduleOne's trace    ``filter_at(pod)`` / ``score_at(pod)`` for bound pods; no
 Node.CreatePod's test  ``headroom_at`` / ``headroom_series``: how many more pods of a shape
                        each node would admit at a past tick (kubesim/node/node.go:44-47)
 scheduleOne, what-if   ``place_at``: where k more pods would be bound at a past tick, on a
-                       private copy of the state (kubesim/kubesim.go:143-225)
+                       private copy of the state (kubesim/kubesim.go:143-225);
+                       ``drain_at``: where the pods running on a node set would go if the
+                       set left k.nodes (kubesim/kubesim.go:168-206)
 =====================  ==============================================================
 
 Errors come back as :class:`KsError` with the reference's kind (``InvalidArgument`` /
@@ -52,6 +54,10 @@ def _c(a, dt):
 # ks_placement (include/ks_engine.h)
 PLACEMENT_DTYPE = np.dtype([("node", np.int32), ("status", np.int32), ("score", np.int64), ("candidates", np.int64)])
 assert PLACEMENT_DTYPE.itemsize == 24
+# ks_eviction (include/ks_engine.h)
+EVICTION_DTYPE = np.dtype([("pod", np.int64), ("from", np.int32), ("node", np.int32), ("status", np.int32),
+                           ("pad", np.int32), ("score", np.int64), ("candidates", np.int64)])
+assert EVICTION_DTYPE.itemsize == 40
 
 
 def _config(tick_seconds, filter_mode, filters, scorers, device, batch_pods, engine_flags):
@@ -297,6 +303,32 @@ class Engine:
         rec = rec[:k]
         return dict(node=rec["node"].copy(), status=rec["status"].copy(), score=rec["score"].copy(),
                     candidates=rec["candidates"].copy(), after=aft, info=info)
+
+    # -- drain preview (include/ks_engine.h, ks_drain_at) ---------------------------------------
+    def drain_at(self, t: int, nodes, after: bool = False):
+        """Where the pods running on ``nodes`` at tick t would go if those nodes left the cluster:
+        the drained nodes are in no Filter loop and no score map (kubesim/kubesim.go:168-206), their
+        running pods are evicted and handed in FIFO order to scheduleOne on a private copy of the
+        state — no engine state changes.  ``nodes``: distinct node indices.  Returns a dict of arrays
+        over the evicted pods — ``pod``, ``from_node``, ``node`` (-1: none), ``status``, ``score``
+        (-1: none), ``candidates`` — plus ``info`` (rounds, re-placed Ok, OverCapacity, not found,
+        segments, drained nodes that had no running pod) and ``after``: with ``after=True`` the
+        [n][4] requested state at t without the drained nodes plus every Ok re-placement, else None.
+        It makes the sizing call itself."""
+        nd = _c(nodes, np.int32).reshape(-1)
+        n_out = C.c_int64(0)
+        aft = np.zeros((self.n, 4), np.int64) if after else None
+        info = np.zeros(_lib.KS_DRAIN_INFO, np.int64)
+        pa, pi = (_p(aft) if after else None), _p(info)
+        rc = self._L.ks_drain_at(self.h, t, len(nd), _p(nd), None, 0, C.byref(n_out), pa, pi)
+        rec = np.zeros(max(n_out.value, 1), EVICTION_DTYPE)
+        if rc == _lib.KS_ERANGE and 0 < n_out.value <= _lib.KS_DRAIN_MAX_PODS:
+            rc = self._L.ks_drain_at(self.h, t, len(nd), _p(nd), _p(rec), n_out.value, C.byref(n_out), pa, pi)
+        self._check(rc)
+        rec = rec[:n_out.value]
+        return dict(pod=rec["pod"].copy(), from_node=rec["from"].copy(), node=rec["node"].copy(),
+                    status=rec["status"].copy(), score=rec["score"].copy(), candidates=rec["candidates"].copy(),
+                    after=aft, info=info)
 
     def pod_lookup(self, node: int, key_id: int):
         """Node.GetPod: FIFO index of the pod stored on ``node`` under ``key_id`` (KsError NotFound)."""
