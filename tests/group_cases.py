@@ -10,8 +10,8 @@ neighbouring groups differ in one choice.
 
 `restate` repeats the host's per-engine choices from a trace and a configuration alone:
 ks_load_nodes (units = gcd of the capacities, default batch, block count), ks_submit_pods (units
-fall to the gcd with every submitted request), update_mode (class thresholds), key16 and
-small_resolver.  No engine is imported here.
+fall to the gcd with every submitted request), update_mode (class thresholds), key16,
+small_resolver and chunk_eligible.  No engine is imported here.
 """
 from __future__ import annotations
 
@@ -111,6 +111,14 @@ def restate(trace, mode, batch_pods=0, engine_flags=0, hi=None):
     b = default_batch(n, batch_pods)
     return dict(n=n, unit=unit, scaled_max=scaled, cls=eval_class(scaled, scorers, engine_flags), B=b,
                 blocks=block_count(n), small=small_class(b, n), k16=key16(scorers))
+
+
+def chunk_eligible(r) -> bool:
+    """chunk_eligible() from restate's choices: batches of at most kWinMaxB pods, node state in
+    32-bit words (the classes from narrow on; the wide class while every scaled capacity is below
+    2^32 - 1) and totals in 16 bits."""
+    words = r["cls"] >= NARROW or max(r["scaled_max"]) < 0xFFFFFFFF
+    return r["B"] <= _lib.KS_WIN_MAX_B and words and r["k16"]
 
 
 def group_choices(restated):

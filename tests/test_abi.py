@@ -64,6 +64,41 @@ def test_bad_configs_rejected_without_device():
     assert create(batch_pods=100000) == _lib.KS_EINVAL
 
 
+def test_scorer_bounds_rejected_without_device():
+    """The largest configured total const + 10 * (w_lr + w_ba) ks_create accepts is 2^30 - 3 (the
+    resolvers' 30-bit key of total + 1); weights and constant values are non-negative; eight scorers
+    at the most.  (The accepted side needs a device: tests/test_weight_paths_gpu.py.)"""
+    L = _lib.load()
+
+    def create(scorers, n=None):
+        cfg = _lib.KsConfig()
+        cfg.abi_version = _lib.KS_ABI_VERSION
+        cfg.tick_seconds = 10
+        cfg.filter_mode, cfg.filters = 1, 7
+        cfg.n_scorers = len(scorers) if n is None else n
+        for i, (k, w, v) in enumerate(scorers):
+            cfg.scorers[i].kind, cfg.scorers[i].weight, cfg.scorers[i].value = k, w, v
+        h = C.c_void_p()
+        rc = L.ks_create(C.byref(cfg), C.byref(h))
+        if rc == _lib.KS_OK:
+            L.ks_destroy(h)
+        return rc
+    wmax = ((1, 53687090, 0), (2, 53687090, 0), (0, 3, 7))
+    assert 21 + 10 * 2 * 53687090 == (1 << 30) - 3
+    assert create(wmax) != _lib.KS_EINVAL                       # validation passes; only the device may be missing
+    assert create(wmax + ((0, 1, 1),)) == _lib.KS_EINVAL        # 2^30 - 2
+    assert create(((1, 53687090, 0), (2, 53687090, 0), (0, 11, 2))) == _lib.KS_EINVAL   # 2^30 - 2 again
+    assert create(((1, 1 << 30, 0),)) == _lib.KS_EINVAL         # the sum past int32
+    assert create(((0, 1 << 16, 1 << 16),)) == _lib.KS_EINVAL   # the product past int32
+    assert create(((1, -1, 0),)) == _lib.KS_EINVAL
+    assert create(((2, -1, 0),)) == _lib.KS_EINVAL
+    assert create(((0, 1, -1),)) == _lib.KS_EINVAL
+    assert create(((0, -1, -1),)) == _lib.KS_EINVAL             # a product that would be positive
+    assert create(((3, 1, 0),)) == _lib.KS_EINVAL               # no such kind
+    assert create(((0, 1, 1),) * 8, n=9) == _lib.KS_EINVAL
+    assert create(((0, 1, 1),) * 8) != _lib.KS_EINVAL
+
+
 def test_engine_refuses_without_library(monkeypatch, tmp_path):
     import importlib
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "missing.so"))
