@@ -1,0 +1,110 @@
+// ks_carve.h — the query scratch (ks_engine::d_qs, d_qi) carved into typed ranges; host only.
+//
+// A layout is written once, as a sequence of Carve::take() calls, and run twice: with a null base
+// the cursor only counts and `at` is the size to reserve; with the real base the same calls give
+// the pointers.  The reserved size and the ranges therefore cannot disagree.  The layouts of the
+// placement and drain previews live here too, so a stand-alone host program can check them.
+#pragma once
+#include <cstdint>
+
+#include "ks_device.h"
+
+namespace ks_host {
+
+struct Carve {
+    int64_t word;          // bytes per scratch word (8: d_qs, 4: d_qi)
+    char* base = nullptr;  // null: the sizing pass
+    int64_t at = 0;        // words taken so far
+    explicit Carve(int64_t word_bytes, void* base_ = nullptr) : word(word_bytes), base((char*)base_) {}
+    // count elements of T from the next multiple of align_words (2 words of d_qs: PodRec's 16 bytes)
+    template <typename T>
+    T* take(int64_t count, int64_t align_words = 1) {
+        at = (at + align_words - 1) / align_words * align_words;
+        T* p = base ? (T*)(base + at * word) : nullptr;
+        at += (count * (int64_t)sizeof(T) + word - 1) / word;
+        return p;
+    }
+};
+
+// the shape records of one upload (shape_of follows them on a 16-byte boundary)
+constexpr int64_t kShapeWords = (int64_t)sizeof(ks::PodRec) / 8 * ks::kPlaceMaxShapes;
+static_assert(kShapeWords % 2 == 0, "shape_of follows the shape records on a 16-byte boundary");
+
+// The rounds' buffers in d_qs (ks_device.h PlaceBufs; cnt is the caller's, in d_qi): a round set
+// uploads up to so_cap pods' shape_of, the call places n_placed pods in all.  ks_place_at: both k;
+// ks_drain_at: a segment's KS_PLACE_MAX_PODS and every evicted pod.
+inline ks::PlaceBufs carve_place(Carve& qs, int64_t np, int64_t nblk, int64_t so_cap, int64_t n_placed) {
+    constexpr int64_t S = ks::kPlaceMaxShapes, L = ks::kPlaceL;
+    ks::PlaceBufs b{};
+    b.state = qs.take<int64_t>(4 * np);  // [4][np]: rc rm rg nr at t
+    b.n_pad = np;
+    b.shapes = qs.take<ks::PodRec>(S, 2);  // one upload: the shape records, then shape_of
+    b.shape_of = qs.take<int32_t>(so_cap);
+    b.lists = qs.take<uint64_t>(S * nblk * L);
+    b.top = qs.take<uint64_t>(S * L);
+    b.ccount = qs.take<long long>(S);
+    b.rb = qs.take<int32_t>(4);                // read back every round
+    b.out = qs.take<ks::Placement>(n_placed);  // (ks_place_at reads rb and out back as one range)
+    return b;
+}
+
+struct PlaceScratch {
+    ks::PlaceBufs b;
+    long long* after;  // [n][4]
+};
+inline PlaceScratch carve_place_at(Carve& qs, Carve& qi, int64_t n, int64_t np, int64_t nblk, int64_t k) {
+    PlaceScratch s{};
+    s.b = carve_place(qs, np, nblk, k, k);
+    s.after = qs.take<long long>(4 * n);
+    s.b.cnt = qi.take<int32_t>(ks::kPlaceMaxShapes * nblk);
+    return s;
+}
+
+// ks_drain_at, before the evicted pods are counted: the gather's int32 scratch (cordon [cw], block
+// counts and offsets [nb], the 8-byte total) and the rounds' cnt
+struct DrainGather {
+    ks::DrainBufs d;
+    int32_t* cnt;
+};
+inline DrainGather carve_drain_gather(Carve& qi, int64_t cw, int64_t nb, int64_t nblk) {
+    DrainGather g{};
+    g.d.cordon = qi.take<uint32_t>(cw);
+    g.d.bcnt = qi.take<int32_t>(nb);
+    g.d.boff = qi.take<int32_t>(nb);
+    g.d.total = qi.take<long long>(1, 2);
+    g.cnt = qi.take<int32_t>(ks::kPlaceMaxShapes * nblk);
+    return g;
+}
+
+// ... and once n_ev is known: the rounds' buffers, the gathered rows (into d), the packed records
+struct DrainScratch {
+    ks::PlaceBufs b;  // b.out: every evicted pod's placement, a segment's at its first pod
+    ks::Eviction* evict;
+    long long* after;  // [n][4]
+};
+inline DrainScratch carve_drain(Carve& qs, int64_t n, int64_t np, int64_t nblk, int64_t n_ev, ks::DrainBufs* d) {
+    DrainScratch s{};
+    s.b = carve_place(qs, np, nblk, ks::kPlaceMaxPods, n_ev);
+    d->ev_pod = qs.take<long long>(n_ev);
+    d->ev_from = qs.take<int32_t>(n_ev);
+    d->ev_rec = qs.take<ks::PodRec>(n_ev, 2);
+    d->cap = n_ev;
+    s.evict = qs.take<ks::Eviction>(n_ev);
+    s.after = qs.take<long long>(4 * n);
+    return s;
+}
+
+// ks_node_peaks / ks_headroom_series: per node the offset, cursor and count of its pods in list[cap]
+struct NodeLists {
+    int32_t *off, *cur, *cnt, *list;
+};
+inline NodeLists carve_node_lists(Carve& qi, int64_t n, int64_t cap) {
+    NodeLists l{};
+    l.off = qi.take<int32_t>(n + 1);
+    l.cur = qi.take<int32_t>(n);
+    l.cnt = qi.take<int32_t>(n);
+    l.list = qi.take<int32_t>(cap);
+    return l;
+}
+
+}  // namespace ks_host

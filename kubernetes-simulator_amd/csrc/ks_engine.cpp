@@ -1,4 +1,8 @@
-// ks_engine.cpp — host side of the C-ABI declared in include/ks_engine.h.
+// ks_engine.cpp — host side of the C-ABI declared in include/ks_engine.h: create / destroy, load,
+// submit, step, scenario groups, node sharding, debug and statistics.  The engine record is in
+// ks_host.h; the entry points that answer about a run after the fact (filter / score, usage,
+// past-tick state, headroom, placement and drain previews, name-keyed lookups) are in
+// ks_queries.cpp, the device self-tests in ks_selftest.cpp.
 //
 // Host responsibilities (everything that is independent of placements):
 //  * FIFO + one-pod-per-tick: the bind tick of pod j is max(bind_tick[j-1] + 1, arrival_j)
@@ -24,10 +28,6 @@
 //    contains the global top-L).  Binds are then identical on every rank with no further
 //    exchange.  Virtual shards (several parts per rank) run the same merge path on one GPU.
 // Placements themselves are decided on the device only.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
 #include <cmath>
 #include <numeric>
 #include <cstdarg>
@@ -35,22 +35,26 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <queue>
-#include <string>
 #include <thread>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/ks_engine.h"
-#include "ks_device.h"
+#include "ks_host.h"
 
+using namespace ks_host;
+
+ks_status ks_host::fail(ks_engine* e, ks_status code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (e) e->errmsg = buf;
+    return code;
+}
 
 namespace {
 
 constexpr int64_t kMaxNodes = 1LL << 24;  // node ids fit the packed key; lists stay < 2^31 entries
-constexpr int64_t kMaxValue = 1LL << 59;
 constexpr int kMaxBatch = 256;
-constexpr int kDefaultBatch = 256;
 constexpr int kChunkBatch = 192;  // default batch of engines on the chunk resolver (ks_load_nodes)
 constexpr int64_t kStageMaxPods = 4096;  // submits of up to this many pods are host-staged
 #ifndef KS_PG_MIN_WG
@@ -60,212 +64,11 @@ constexpr int kProfEv = 11;  // per launch: prep | scan | part merges | exchange
                              // pipelined chain's second stream)
 constexpr int kRescanWgs = 1024;  // the pipelined chain's conditional local rescan: workgroups
 constexpr int64_t kNever = std::numeric_limits<int64_t>::max();
-constexpr int64_t kUBlk = 256;   // usage index: pods per block (= the usage kernels' workgroup)
-constexpr int64_t kUSup = 64;    // blocks per super block
-constexpr int64_t kMaxDigestTicks = 1 << 20;
 // the overlap's limit on a rank's scan blocks (step_body)
 #ifndef KS_OVERLAP_MAX_BLOCKS
 #define KS_OVERLAP_MAX_BLOCKS 256
 #endif
 constexpr int kOverlapMaxBlocks = KS_OVERLAP_MAX_BLOCKS;
-
-// Growable device array (stream-ordered copies on growth).
-template <typename T>
-struct DVec {
-    T* p = nullptr;
-    int64_t n = 0, cap = 0;
-    hipError_t reserve(int64_t want, hipStream_t st) {
-        if (want <= cap) return hipSuccess;
-        int64_t nc = std::max<int64_t>(want, std::max<int64_t>(cap * 2, 1024));
-        T* q = nullptr;
-        hipError_t e = hipMalloc(&q, sizeof(T) * nc);
-        if (e != hipSuccess) return e;
-        if (n) {
-            e = hipMemcpyAsync(q, p, sizeof(T) * n, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return e;
-            e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return e;
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = nc;
-        return hipSuccess;
-    }
-    hipError_t append(const T* h, int64_t k, hipStream_t st) {
-        hipError_t e = reserve(n + k, st);
-        if (e != hipSuccess) return e;
-        if (k) e = hipMemcpyAsync(p + n, h, sizeof(T) * k, hipMemcpyHostToDevice, st);
-        n += k;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = cap = 0;
-    }
-};
-
-// (finish tick, pod) min-heap whose array can be walked: the entries due by a tick are the heap's
-// top subtree (flush_expiries visits them without copying or popping the heap)
-struct PendingHeap : std::priority_queue<std::pair<int64_t, int64_t>, std::vector<std::pair<int64_t, int64_t>>,
-                                         std::greater<std::pair<int64_t, int64_t>>> {
-    template <class F>
-    void for_each_due(int64_t t, F&& f) const {
-        std::vector<size_t> st;
-        if (!c.empty() && c[0].first <= t) st.push_back(0);
-        while (!st.empty()) {
-            const size_t i = st.back();
-            st.pop_back();
-            f(c[i].second);
-            for (size_t k = 2 * i + 1; k <= 2 * i + 2 && k < c.size(); k++)
-                if (c[k].first <= t) st.push_back(k);
-        }
-    }
-};
-
-}  // namespace
-
-struct ks_engine {
-    ks_config cfg{};
-    ks::Cfg dc{};
-    hipStream_t st = nullptr;
-    int device = 0;
-    bool profiling = false;
-
-    // nodes
-    int64_t n = 0, n_pad = 0;
-    int nwb = 0;
-    bool nodes_loaded = false;
-    void* node_mem = nullptr;
-    uint4* d_ncst = nullptr;  // the node constants table (ks::EngineArgs::ncst), [n_pad][2]
-    ks::NodeSoA s{};
-
-    // pods (device)
-    DVec<ks::PodRec> pods;
-    DVec<int32_t> dur, b_node, b_status, phase_off, cum_sec, exp_pod;
-    DVec<int64_t> exp_off, t0, fin, use, exp_pos;
-    DVec<uint8_t> expired;
-    DVec<ks::ScanRec> srec;  // the pods' scan records (ks_device.h scan_rec_micro), rebuilt on a rescale
-    // pods (host mirror of placement-independent facts)
-    std::vector<int64_t> h_bind_tick, h_fin;
-    std::vector<int64_t> h_exp_off{0};
-    std::vector<int32_t> h_dur;
-    std::vector<int32_t> h_total_sec;  // Σ phase seconds, int32 wrapping (Pod.totalSeconds)
-    PendingHeap pending;  // (finish tick, pod) not yet attached to a later pod
-    int64_t P = 0, F = 0;
-    int64_t last_arrival = 0;
-    int64_t scale[3] = {1, 1, 1};   // device unit of cpu / memory / gpu, in milli-units
-    int64_t max_alloc[3] = {0, 0, 0};  // largest capacity per resource, milli-units
-    int mode = ks::kEvalWide;  // evaluator variant (ks_device.h)
-    uint32_t flags = 0;        // KS_ENGINE_*
-    std::vector<int64_t> h_exp_pos;  // global exp_pod index holding pod q's own expiry, or -1
-    // pod keys (Node.CreatePod's pods.Store(key, pod), kubesim/node/node.go:58)
-    std::vector<int64_t> h_key;
-    std::unordered_map<int64_t, int64_t> key_end;  // key -> latest run end among pods with it
-    // host mirror of the binds (name-keyed queries): node (-1 = not bound) and status
-    std::vector<int32_t> h_node;
-    std::vector<int8_t> h_status;
-    // host mirrors the per-tick path passes by value: device-unit pod records, the expiry CSR's
-    // pods, the device's expired flags (exact while err == KS_OK: every expiry attached to a pod
-    // < done has been applied, plus the ones a flush applied)
-    std::vector<ks::PodRec> h_pods;
-    std::vector<int32_t> h_exp_pod;
-    std::vector<uint8_t> h_expired;
-    // host-staged submits: rows for the device arrays in a pinned, device-visible arena, applied by
-    // one scatter (or by the per-tick kernel) before any device work reads them
-    uint8_t* stage = nullptr;           // pinned host arena
-    uint8_t* stage_dev = nullptr;       // its device address
-    int64_t stage_cap = 0, stage_used = 0;
-    ks::CopySeg* segs = nullptr;        // pinned segment table
-    ks::CopySeg* segs_dev = nullptr;
-    int seg_cap = 0, nseg = 0, seg_done = 0;
-    int64_t xpos_lo = INT64_MAX;        // exp_pos rows [xpos_lo, P) changed since the last flush
-    hipEvent_t stage_ev = nullptr;      // recorded after the launch that consumed the last segments
-    // per-tick path (ks_tick.hip)
-    ks::TickScratch* d_tick = nullptr;
-    ks::TickOut* h_tick = nullptr;      // pinned, device-visible
-    ks::TickOut* h_tick_dev = nullptr;
-    // name-keyed index over binds [0, idx_upto), extended on each query
-    int64_t idx_upto = 0;
-    std::vector<std::vector<int64_t>> node_pods;      // per node: every pod bound there, FIFO
-    // run-interval index for the usage queries: pod q may run only in [t0, end) (end = t0 when
-    // it never runs); per block of kUBlk pods and per super block of kUSup blocks the max end
-    std::vector<int64_t> h_end, blk_end, sup_end;
-    DVec<uint8_t> preg;  // 1: phases non-negative and no int32 wrap (digest by segments)
-
-    // progress
-    int64_t tick = 0, done = 0;
-    int err = KS_OK;
-    std::string errmsg;
-
-    // batch machinery
-    int B = kDefaultBatch, PG = 32;
-    uint64_t* lists = nullptr;
-    uint64_t* cand = nullptr;
-    int nblk = 0;
-    // node sharding
-    int world = 1, rank = 0, vsh = 1;
-    ncclComm_t comm = nullptr;
-    ks_allgather_fn xfn = nullptr;  // host exchange (ks_shard_host) instead of RCCL
-    void* xuser = nullptr;
-    uint64_t* h_xbuf = nullptr;     // pinned [world][vsh][B][L]
-    std::vector<int> part_lo;  // [world * vsh + 1] block boundaries of the parts
-    int blk_lo = 0, blk_n = 0;  // this rank's scan range
-    uint64_t* cand_all = nullptr;  // [world * vsh][B][L]
-    // pruned block lists (ks_scan.h): per-pod bitmaps of the blocks that wrote a list and thresholds
-    bool prune = false;
-    int L = ks::kTopL;  // the block lists' length (kTopLOverlap: the overlap's single-shard engines)
-    uint64_t* lbit = nullptr;  // [B][nwl]
-    uint64_t* lthr = nullptr;  // [2][kThrCopies][B]
-    int nwl = 0;
-    int64_t* d_ctr = nullptr;
-    int64_t* h_ctr = nullptr;  // pinned
-    ks::EngineArgs* d_args = nullptr;  // the kernels' argument record (device)
-    ks::EngineArgs* h_args = nullptr;  // its pinned host staging
-    // overlap of the next batch's scan with the chunk resolver (chunk class, one shard): the
-    // speculative scan's argument records (ctr = d_spec + parity) and counters, its workgroups
-    bool overlap = true;
-    int scan_workers = 0;
-    int64_t* d_spec = nullptr;
-    ks::EngineArgs* d_args_spec = nullptr;  // [2]: ctr = d_spec + kSpecStride * parity
-    ks::EngineArgs* h_args_spec = nullptr;
-    // the pipelined sharded chain (round 6, step_body): the next batch's speculative scan, per-part
-    // merges and exchange on a second stream beside the resolve; a rescan scans every block locally
-    // (d_args_full: the whole block range, the engine's own list set)
-    hipStream_t st2 = nullptr;
-    hipEvent_t pev_m = nullptr, pev_x = nullptr;
-    ks::EngineArgs* d_args_full = nullptr;
-    ks::EngineArgs* h_args_full = nullptr;
-    // group membership (ks_group_add): stream, counters and argument slots belong to the group
-    ks_group* group = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> prof_ev;
-    ks_step_stats stats{};
-    ks_kernel_stats kstats{};
-
-    // scratch for queries
-    uint8_t* d_mask = nullptr;
-    int64_t* d_score = nullptr;
-    ks::WinWS* d_sweep = nullptr;    // batch window workspace and node -> E index (n_pad, -1)
-    int32_t* d_eidx = nullptr;
-    int32_t* d_nslot = nullptr;      // node -> candidate slot of the batch (ks_cand.hip), -1
-    int32_t* d_first = nullptr;      // node -> its first kept entry of the batch, kNoFirst
-    unsigned long long* d_usage = nullptr;
-    DVec<int32_t> d_blk;                  // usage query: candidate pod blocks
-    std::vector<int32_t> h_blk;
-    DVec<unsigned long long> d_digest;    // [6][T + 1] difference arrays, then the prefix sums
-    // past-tick state queries (ks_requested_at ... ks_node_peaks): the arrival tick the bind-tick
-    // recurrence used per pod (non-decreasing), prefix counts of Ok / OverCapacity binds over the
-    // pods [0, cum_upto) (extended on each query), 64-bit and 32-bit device scratch
-    std::vector<int64_t> h_arr;
-    std::vector<int64_t> cum_ok{0}, cum_over{0};
-    int64_t cum_upto = 0;
-    DVec<unsigned long long> d_qs;
-    DVec<int32_t> d_qi;
-    std::vector<ks::PodRec> h_shapes;  // ks_headroom_*: the call's shape records (requests in milli-units)
-};
-
-namespace {
 
 void engine_free(ks_engine* e);  // ks_destroy's body; a group frees its members with it
 
@@ -277,22 +80,6 @@ void engine_free(ks_engine* e);  // ks_destroy's body; a group frees its members
 bool in_passed_domain(const ks_engine* e, int64_t first_bind, int64_t t) {
     return t - first_bind <= (int64_t)INT32_MAX / e->cfg.tick_seconds;
 }
-ks_status fail(ks_engine* e, ks_status code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (e) e->errmsg = buf;
-    return code;
-}
-
-#define HIPCHK(e, expr)                                                                     \
-    do {                                                                                    \
-        hipError_t _r = (expr);                                                             \
-        if (_r != hipSuccess)                                                               \
-            return fail((e), KS_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(_r));    \
-    } while (0)
 
 ks::EngineArgs make_args(ks_engine* e) {
     ks::EngineArgs a{};
@@ -345,7 +132,9 @@ hipError_t stage_xpos(ks_engine* e) {
     return stage_copy(e, e->exp_pos.p + lo, e->h_exp_pos.data() + lo, sizeof(int64_t) * (e->P - lo));
 }
 
-hipError_t stage_flush(ks_engine* e) {
+}  // namespace
+
+hipError_t ks_host::stage_flush(ks_engine* e) {
     if (hipError_t r = stage_xpos(e); r != hipSuccess) return r;
     if (e->seg_done >= e->nseg) return hipSuccess;
     hipError_t r = ks::launch_scatter(e->segs_dev + e->seg_done, e->nseg - e->seg_done, e->st);
@@ -353,6 +142,8 @@ hipError_t stage_flush(ks_engine* e) {
     e->seg_done = e->nseg;
     return r;
 }
+
+namespace {
 
 // room for `bytes` more in the arena and one more segment
 hipError_t stage_room(ks_engine* e, int64_t bytes) {
@@ -466,14 +257,6 @@ void update_mode(ks_engine* e) {
             : (tiny && !no_tiny) ? ks::kEvalTiny
             : narrow ? ks::kEvalNarrow : ks::kEvalWide;
 }
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 
 // Validation and host-side construction shared by ks_create and ks_group_add (no HIP calls).
 ks_status engine_init(const ks_config* cfg, ks_engine** out) {
@@ -1075,6 +858,44 @@ ks_status step_finish(ks_engine* e, int64_t t_end, int64_t new_done, const int32
 }
 
 }  // namespace
+
+// Apply every not-yet-applied expiry with finish tick <= the current tick (ks_filter / ks_score
+// see the state Run's next scheduleOne would).  While the run is live the host knows them
+// exactly: every expiry attached to a pod < done has been applied (mirror_expired), an expiry
+// attached to a later pod j > done finishes after bind_tick[j - 1] >= bind_tick[done] > tick, so
+// only the next pod's attached expiries and the unattached ones (pending, when every submitted pod
+// is bound) can be due — usually none, and no launch is made.
+ks_status ks_host::flush_expiries(ks_engine* e) {
+    if (e->err == KS_OK) {
+        std::vector<int32_t> qs;
+        auto add = [&](int64_t q) {
+            if (e->h_status[q] == KS_POD_OK && !e->h_expired[q] && e->h_fin[q] <= e->tick) qs.push_back((int32_t)q);
+        };
+        if (e->done < e->P)
+            for (int64_t u = e->h_exp_off[e->done]; u < e->h_exp_off[e->done + 1]; u++) add(e->h_exp_pod[u]);
+        e->pending.for_each_due(e->tick, add);
+        if ((int)qs.size() <= ks::kTickMaxExp) {
+            if (!qs.empty()) {
+                ks::ExpList L{};
+                for (int32_t q : qs) {
+                    ks::TickExp& x = L.x[L.n++];
+                    x.node = e->h_node[q];
+                    x.q = q;
+                    for (int k = 0; k < 3; k++) x.req[k] = e->h_pods[q].req[k];
+                }
+                HIPCHK(e, ks::launch_apply_exp(e->s, e->expired.p, L, e->st));
+            }
+        } else {
+            HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
+                                       e->expired.p, e->st));
+        }
+        for (int32_t q : qs) e->h_expired[q] = 1;
+        return KS_OK;
+    }
+    HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
+                               e->expired.p, e->st));
+    return KS_OK;
+}
 
 extern "C" {
 
@@ -1835,789 +1656,6 @@ ks_status ks_group_step(ks_group* g, int64_t ticks, ks_bind* out, int64_t cap, i
     return KS_OK;
 }
 
-// Apply every not-yet-applied expiry with finish tick <= the current tick (ks_filter / ks_score
-// see the state Run's next scheduleOne would).  While the run is live the host knows them
-// exactly: every expiry attached to a pod < done has been applied (mirror_expired), an expiry
-// attached to a later pod j > done finishes after bind_tick[j - 1] >= bind_tick[done] > tick, so
-// only the next pod's attached expiries and the unattached ones (pending, when every submitted pod
-// is bound) can be due — usually none, and no launch is made.
-static ks_status flush_expiries(ks_engine* e) {
-    if (e->err == KS_OK) {
-        std::vector<int32_t> qs;
-        auto add = [&](int64_t q) {
-            if (e->h_status[q] == KS_POD_OK && !e->h_expired[q] && e->h_fin[q] <= e->tick) qs.push_back((int32_t)q);
-        };
-        if (e->done < e->P)
-            for (int64_t u = e->h_exp_off[e->done]; u < e->h_exp_off[e->done + 1]; u++) add(e->h_exp_pod[u]);
-        e->pending.for_each_due(e->tick, add);
-        if ((int)qs.size() <= ks::kTickMaxExp) {
-            if (!qs.empty()) {
-                ks::ExpList L{};
-                for (int32_t q : qs) {
-                    ks::TickExp& x = L.x[L.n++];
-                    x.node = e->h_node[q];
-                    x.q = q;
-                    for (int k = 0; k < 3; k++) x.req[k] = e->h_pods[q].req[k];
-                }
-                HIPCHK(e, ks::launch_apply_exp(e->s, e->expired.p, L, e->st));
-            }
-        } else {
-            HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
-                                       e->expired.p, e->st));
-        }
-        for (int32_t q : qs) e->h_expired[q] = 1;
-        return KS_OK;
-    }
-    HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
-                               e->expired.p, e->st));
-    return KS_OK;
-}
-
-static ks_status eval_pod(ks_engine* e, int64_t pod) {
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (pod < 0 || pod >= e->P) return fail(e, KS_EINVAL, "pod %lld out of range", (long long)pod);
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    ks_status r = flush_expiries(e);
-    if (r != KS_OK) return r;
-    if (e->n == 0) return KS_OK;
-    HIPCHK(e, ks::launch_eval_pod(e->dc, e->s, e->pods.p + pod, e->cfg.filters, e->d_mask, e->d_score, e->mode, e->st));
-    return KS_OK;
-}
-
-ks_status ks_filter(ks_engine* e, int64_t pod, uint8_t* mask_out) {
-    if (!e || !mask_out) return KS_EINVAL;
-    ks_status r = eval_pod(e, pod);
-    if (r != KS_OK) return r;
-    if (e->n) HIPCHK(e, hipMemcpyAsync(mask_out, e->d_mask, e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-ks_status ks_score(ks_engine* e, int64_t pod, int64_t* score_out) {
-    if (!e || !score_out) return KS_EINVAL;
-    ks_status r = eval_pod(e, pod);
-    if (r != KS_OK) return r;
-    if (e->n)
-        HIPCHK(e, hipMemcpyAsync(score_out, e->d_score, sizeof(int64_t) * e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-// Candidate pod blocks of a usage query over ticks >= t_lo: blocks of the pods [0, q_hi) (bind
-// ticks are FIFO-monotone, so q_hi bounds the start side) holding a pod whose run end is > t_lo;
-// super blocks whose every pod ended by t_lo are skipped whole.
-static int64_t usage_blocks(ks_engine* e, int64_t t_lo, int64_t q_hi) {
-    e->h_blk.clear();
-    const int64_t nblk = (q_hi + kUBlk - 1) / kUBlk;
-    for (int64_t s = 0; s * kUSup < nblk; s++) {
-        if (e->sup_end[s] <= t_lo) continue;
-        const int64_t b1 = std::min(nblk, (s + 1) * kUSup);
-        for (int64_t b = s * kUSup; b < b1; b++)
-            if (e->blk_end[b] > t_lo) e->h_blk.push_back((int32_t)b);
-    }
-    return (int64_t)e->h_blk.size();
-}
-
-// pods bound at ticks <= t (a FIFO prefix of the binds made so far)
-static int64_t bound_by(const ks_engine* e, int64_t t) {
-    return std::upper_bound(e->h_bind_tick.begin(), e->h_bind_tick.begin() + e->done, t) - e->h_bind_tick.begin();
-}
-
-static_assert(kUBlk == 256, "usage index block = the usage kernels' workgroup");
-
-ks_status ks_usage_at(ks_engine* e, int64_t t, int64_t* usage_out) {
-    if (!e || !usage_out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "usage tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
-    if (e->n == 0) return KS_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t);
-    const int64_t nb = usage_blocks(e, t, q_hi);
-    HIPCHK(e, hipMemsetAsync(e->d_usage, 0, sizeof(unsigned long long) * 3 * e->n, e->st));
-    if (nb) {
-        HIPCHK(e, e->d_blk.reserve(nb, e->st));
-        HIPCHK(e, hipMemcpyAsync(e->d_blk.p, e->h_blk.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, e->st));
-        // (profiling: HIP events around the usage kernel alone — its roofline in bench.py)
-        if (e->profiling && e->ev[2]) HIPCHK(e, hipEventRecord(e->ev[2], e->st));
-        HIPCHK(e, ks::launch_usage(e->d_blk.p, nb, q_hi, t, e->cfg.tick_seconds, e->b_node.p, e->b_status.p, e->t0.p,
-                                   e->dur.p, e->phase_off.p, e->cum_sec.p, e->use.p, e->d_usage, e->st));
-        if (e->profiling && e->ev[3]) HIPCHK(e, hipEventRecord(e->ev[3], e->st));
-    }
-    HIPCHK(e, hipMemcpyAsync(usage_out, e->d_usage, sizeof(int64_t) * 3 * e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    if (e->profiling && nb && e->ev[2]) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
-        e->kstats.usage_ms += ms;
-        e->kstats.usage_n += 1;
-        e->kstats.usage_pods += (int64_t)nb * ks::usage_block_pods();
-    }
-    return KS_OK;
-}
-
-ks_status ks_usage(ks_engine* e, int64_t* usage_out) {
-    if (!e) return KS_EINVAL;
-    return ks_usage_at(e, e->tick, usage_out);
-}
-
-ks_status ks_usage_digest(ks_engine* e, int64_t t_lo, int64_t t_hi, uint64_t* out) {
-    if (!e || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (t_lo < 0 || t_hi <= t_lo || t_hi - 1 > e->tick || t_hi - t_lo > kMaxDigestTicks)
-        return fail(e, KS_EINVAL, "digest window [%lld, %lld) outside [0, %lld] or longer than %lld ticks",
-                    (long long)t_lo, (long long)t_hi, (long long)e->tick + 1, (long long)kMaxDigestTicks);
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t T = t_hi - t_lo;
-    const int64_t q_hi = bound_by(e, t_hi - 1);
-    const int64_t nb = usage_blocks(e, t_lo, q_hi);
-    HIPCHK(e, e->d_digest.reserve(6 * (T + 1) + 6 * T, e->st));
-    unsigned long long* diff = e->d_digest.p;
-    unsigned long long* res = diff + 6 * (T + 1);
-    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * 6 * (T + 1), e->st));
-    if (nb) {
-        HIPCHK(e, e->d_blk.reserve(nb, e->st));
-        HIPCHK(e, hipMemcpyAsync(e->d_blk.p, e->h_blk.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, e->st));
-    }
-    HIPCHK(e, ks::launch_usage_digest(e->d_blk.p, nb, q_hi, t_lo, t_hi, e->cfg.tick_seconds, e->b_node.p, e->b_status.p,
-                                      e->t0.p, e->dur.p, e->preg.p, e->phase_off.p, e->cum_sec.p, e->use.p, diff, res,
-                                      e->st));
-    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(uint64_t) * 6 * T, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-// ---- past-tick state queries (ks_query.hip) ----------------------------------------------------
-// The node table's rc rm rg nr at any past tick, rebuilt from the binds: the pods q < q_hi that
-// were bound Ok and run at t.  They share the usage queries' run-interval index, read only the
-// bind arrays and the pod records, and leave the live table and the expiry state alone — so they
-// answer after an aborted run too (on the binds made before it).
-
-// upload the candidate blocks usage_blocks() left in h_blk
-static ks_status upload_blocks(ks_engine* e, int64_t nb) {
-    if (!nb) return KS_OK;
-    HIPCHK(e, e->d_blk.reserve(nb, e->st));
-    HIPCHK(e, hipMemcpyAsync(e->d_blk.p, e->h_blk.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, e->st));
-    return KS_OK;
-}
-
-static ks::QScale milli_scale(const ks_engine* e) { return ks::QScale{{e->scale[0], e->scale[1], e->scale[2]}}; }
-
-static ks_status check_window(ks_engine* e, const char* what, int64_t t_lo, int64_t t_hi) {
-    if (t_lo < 0 || t_hi <= t_lo || t_hi - 1 > e->tick || t_hi - t_lo > kMaxDigestTicks)
-        return fail(e, KS_EINVAL, "%s window [%lld, %lld) outside [0, %lld] or longer than %lld ticks", what,
-                    (long long)t_lo, (long long)t_hi, (long long)e->tick + 1, (long long)kMaxDigestTicks);
-    return KS_OK;
-}
-
-ks_status ks_requested_at(ks_engine* e, int64_t t, int64_t* out) {
-    if (!e || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
-    if (e->n == 0) return KS_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t);
-    const int64_t nb = usage_blocks(e, t, q_hi);
-    HIPCHK(e, e->d_qs.reserve(4 * e->n, e->st));
-    HIPCHK(e, hipMemsetAsync(e->d_qs.p, 0, sizeof(unsigned long long) * 4 * e->n, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)e->n, e->b_node.p, e->b_status.p, e->t0.p,
-                                   e->dur.p, e->pods.p, milli_scale(e), 4, 1, e->d_qs.p, e->st));
-    HIPCHK(e, hipMemcpyAsync(out, e->d_qs.p, sizeof(int64_t) * 4 * e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-// Filter mask and score of an already-bound pod as scheduleOne saw them: the evaluator of
-// ks_filter / ks_score on a copy of the node table whose rc rm rg nr are the state rebuilt from the
-// pods q < pod running at the pod's bind tick (every one of them was bound at an earlier tick).
-static ks_status eval_pod_at(ks_engine* e, int64_t pod) {
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (pod < 0 || pod >= e->done || e->h_node[pod] < 0)
-        return fail(e, KS_EINVAL, "pod %lld is not bound (queued pods: ks_filter / ks_score)", (long long)pod);
-    if (e->n == 0) return KS_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t t = e->h_bind_tick[pod];
-    const int64_t nb = usage_blocks(e, t, pod);
-    const int64_t np = e->n_pad;
-    HIPCHK(e, e->d_qs.reserve(4 * np, e->st));
-    HIPCHK(e, hipMemsetAsync(e->d_qs.p, 0, sizeof(unsigned long long) * 4 * np, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, pod, t, (int32_t)e->n, e->b_node.p, e->b_status.p, e->t0.p,
-                                   e->dur.p, e->pods.p, ks::QScale{{1, 1, 1}}, 1, np, e->d_qs.p, e->st));
-    ks::NodeSoA s = e->s;
-    int64_t* b = (int64_t*)e->d_qs.p;
-    s.rc = b; s.rm = b + np; s.rg = b + 2 * np; s.nr = b + 3 * np;
-    HIPCHK(e, ks::launch_eval_pod(e->dc, s, e->pods.p + pod, e->cfg.filters, e->d_mask, e->d_score, e->mode, e->st));
-    return KS_OK;
-}
-
-ks_status ks_filter_at(ks_engine* e, int64_t pod, uint8_t* mask_out) {
-    if (!e || !mask_out) return KS_EINVAL;
-    ks_status r = eval_pod_at(e, pod);
-    if (r != KS_OK) return r;
-    if (e->n) HIPCHK(e, hipMemcpyAsync(mask_out, e->d_mask, e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-ks_status ks_score_at(ks_engine* e, int64_t pod, int64_t* score_out) {
-    if (!e || !score_out) return KS_EINVAL;
-    ks_status r = eval_pod_at(e, pod);
-    if (r != KS_OK) return r;
-    if (e->n)
-        HIPCHK(e, hipMemcpyAsync(score_out, e->d_score, sizeof(int64_t) * e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-// prefix counts of the Ok / OverCapacity binds, extended over the pods [cum_upto, done)
-static void count_binds(ks_engine* e) {
-    for (int64_t q = e->cum_upto; q < e->done; q++) {
-        e->cum_ok.push_back(e->cum_ok.back() + (e->h_status[q] == KS_POD_OK && e->h_node[q] >= 0));
-        e->cum_over.push_back(e->cum_over.back() + (e->h_status[q] == KS_POD_OVER_CAPACITY && e->h_node[q] >= 0));
-    }
-    e->cum_upto = e->done;
-}
-
-static_assert(KS_SERIES_COLS == ks::kSeriesCols, "ks_cluster_series columns");
-
-ks_status ks_cluster_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) {
-    if (!e || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (ks_status r = check_window(e, "series", t_lo, t_hi); r != KS_OK) return r;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t T = t_hi - t_lo;
-    // pods off the queue by t_lo / by the window's last tick; arrivals likewise (both FIFO prefixes)
-    const int64_t q_lo = bound_by(e, t_lo), q_hi = bound_by(e, t_hi - 1);
-    const int64_t a_lo = std::upper_bound(e->h_arr.begin(), e->h_arr.end(), t_lo) - e->h_arr.begin();
-    const int64_t a_hi = std::upper_bound(e->h_arr.begin(), e->h_arr.end(), t_hi - 1) - e->h_arr.begin();
-    const int64_t nb = usage_blocks(e, t_lo, q_hi);
-    count_binds(e);
-    ks::SeriesInit init{};
-    init.v[4] = e->cum_ok[q_lo];
-    init.v[5] = e->cum_over[q_lo];
-    init.v[6] = a_lo - q_lo;
-    const int64_t C = ks::kSeriesCols, n_arr = a_hi - a_lo;
-    HIPCHK(e, e->d_qs.reserve(C * (T + 1) + C * T + n_arr, e->st));
-    unsigned long long* diff = e->d_qs.p;
-    unsigned long long* res = diff + C * (T + 1);
-    int64_t* arr = (int64_t*)(res + C * T);
-    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * C * (T + 1), e->st));
-    if (n_arr)
-        HIPCHK(e, hipMemcpyAsync(arr, e->h_arr.data() + a_lo, sizeof(int64_t) * n_arr, hipMemcpyHostToDevice, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_series(e->d_blk.p, nb, q_lo, q_hi, t_lo, t_hi, e->b_status.p, e->t0.p, e->dur.p, e->pods.p,
-                                milli_scale(e), arr, n_arr, init, diff, res, e->st));
-    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C * T, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-ks_status ks_node_peaks(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) {
-    if (!e || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (ks_status r = check_window(e, "peaks", t_lo, t_hi); r != KS_OK) return r;
-    if (e->n == 0) return KS_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t_hi - 1);
-    const int64_t nb = usage_blocks(e, t_lo, q_hi);
-    const int64_t n = e->n, cap = nb * kUBlk;
-    if (cap > INT32_MAX) return fail(e, KS_EINVAL, "peaks window holds too many candidate pods");
-    HIPCHK(e, e->d_qs.reserve(4 * n, e->st));
-    HIPCHK(e, e->d_qi.reserve(3 * n + 1 + cap, e->st));
-    int32_t* off = e->d_qi.p;        // [n + 1]
-    int32_t* cur = off + n + 1;      // [n]
-    int32_t* cnt = cur + n;          // [n]
-    int32_t* list = cnt + n;         // [cap]
-    HIPCHK(e, hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_node_peaks(e->d_blk.p, nb, q_hi, t_lo, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p,
-                                    e->dur.p, e->pods.p, milli_scale(e), cnt, off, cur, list, (int32_t)cap,
-                                    (long long*)e->d_qs.p, e->st));
-    HIPCHK(e, hipMemcpyAsync(out, e->d_qs.p, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-// ---- headroom queries (ks_query.hip) -----------------------------------------------------------
-// How many more pods of a shape Node.CreatePod (kubesim/node/node.go:44-47) would admit per node at a
-// past tick: the rebuilt rc rm rg nr against the cluster's alloc / taints / labels.  Shapes live only
-// for the call: nothing is appended, rescaled or written back (their requests stay in milli-units,
-// the device multiplies the free amount by e->scale instead of dividing the request).
-static_assert(KS_HEADROOM_COLS == ks::kHeadCols && KS_HEADROOM_MAX_SHAPES == ks::kHeadMaxShapes &&
-              KS_HEADROOM_NODE_MAX == ks::kHeadMax, "ks_headroom_* constants");
-constexpr int64_t kMaxHeadSeries = 1LL << 22;  // k * (t_hi - t_lo) at the most
-
-static ks_status head_shapes(ks_engine* e, int32_t k, const int64_t* req, const uint8_t* keymask, const uint64_t* tol,
-                             const uint64_t* sel, const char* what = "headroom") {
-    if (k < 1 || k > KS_HEADROOM_MAX_SHAPES)
-        return fail(e, KS_EINVAL, "%s: %d shapes outside [1, %d]", what, (int)k, KS_HEADROOM_MAX_SHAPES);
-    e->h_shapes.assign(k, ks::PodRec{});
-    for (int32_t j = 0; j < k; j++) {
-        if (keymask[j] & ~7u) return fail(e, KS_EINVAL, "%s shape %d: keymask %u has bits above 4", what, (int)j, (unsigned)keymask[j]);
-        ks::PodRec& r = e->h_shapes[j];
-        for (int c = 0; c < 3; c++) {
-            if (!(keymask[j] >> c & 1)) continue;  // unmasked keys are ignored
-            const int64_t q = req[j * 3 + c];
-            if (q < 0 || q >= ks::kHeadReqMax) return fail(e, KS_EINVAL, "%s shape %d: request %d out of range", what, (int)j, c);
-            r.req[c] = q;
-        }
-        r.tol = tol[j];
-        r.sel = sel[j];
-        r.keymask = keymask[j];
-    }
-    return KS_OK;
-}
-
-ks_status ks_headroom_at(ks_engine* e, int64_t t, int32_t k, const int64_t* req, const uint8_t* keymask,
-                         const uint64_t* tol, const uint64_t* sel, int64_t* out, int32_t* per_node_out) {
-    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (ks_status r = head_shapes(e, k, req, keymask, tol, sel); r != KS_OK) return r;
-    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
-    if (e->n == 0) {
-        for (int32_t j = 0; j < k; j++)
-            for (int c = 0; c < KS_HEADROOM_COLS; c++) out[j * KS_HEADROOM_COLS + c] = c == 3 ? -1 : 0;
-        return KS_OK;
-    }
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t);
-    const int64_t nb = usage_blocks(e, t, q_hi);
-    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
-    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long);
-    HIPCHK(e, e->d_qs.reserve(4 * np + W * k + nblk * k * 3 + (int64_t)k * KS_HEADROOM_COLS, e->st));
-    if (per_node_out) HIPCHK(e, e->d_qi.reserve((int64_t)k * n, e->st));
-    unsigned long long* state = e->d_qs.p;                 // [4][np]: rc rm rg nr at t, device units
-    ks::PodRec* shapes = (ks::PodRec*)(state + 4 * np);    // [k]
-    unsigned long long* part = state + 4 * np + W * k;     // [nblk][k][3]
-    long long* res = (long long*)(part + nblk * k * 3);    // [k][KS_HEADROOM_COLS]
-    HIPCHK(e, hipMemsetAsync(state, 0, sizeof(unsigned long long) * 4 * np, e->st));
-    HIPCHK(e, hipMemcpyAsync(shapes, e->h_shapes.data(), sizeof(ks::PodRec) * k, hipMemcpyHostToDevice, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
-                                   e->pods.p, ks::QScale{{1, 1, 1}}, 1, np, state, e->st));
-    HIPCHK(e, ks::launch_headroom(e->s, (const int64_t*)state, np, (int32_t)n, e->dc.filter_feeds, e->cfg.filters,
-                                  milli_scale(e), shapes, k, part, res, per_node_out ? e->d_qi.p : nullptr, e->st));
-    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * k * KS_HEADROOM_COLS, hipMemcpyDeviceToHost, e->st));
-    if (per_node_out)
-        HIPCHK(e, hipMemcpyAsync(per_node_out, e->d_qi.p, sizeof(int32_t) * k * n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-ks_status ks_headroom_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int32_t k, const int64_t* req,
-                             const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel, int64_t* out) {
-    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (ks_status r = head_shapes(e, k, req, keymask, tol, sel); r != KS_OK) return r;
-    if (ks_status r = check_window(e, "headroom", t_lo, t_hi); r != KS_OK) return r;
-    const int64_t T = t_hi - t_lo, C2 = 2 * (int64_t)k;
-    if (k * T > kMaxHeadSeries)
-        return fail(e, KS_EINVAL, "headroom series: %d shapes x %lld ticks is more than %lld", (int)k, (long long)T,
-                    (long long)kMaxHeadSeries);
-    if (e->n == 0) {
-        std::fill(out, out + C2 * T, (int64_t)0);
-        return KS_OK;
-    }
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t_hi - 1);
-    const int64_t nb = usage_blocks(e, t_lo, q_hi);
-    const int64_t n = e->n, cap = nb * kUBlk;
-    if (cap > INT32_MAX) return fail(e, KS_EINVAL, "headroom window holds too many candidate pods");
-    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long);
-    HIPCHK(e, e->d_qs.reserve(C2 * (T + 1) + C2 * T + W * k, e->st));
-    HIPCHK(e, e->d_qi.reserve(3 * n + 1 + cap, e->st));
-    unsigned long long* diff = e->d_qs.p;                            // [2 k][T + 1]
-    unsigned long long* res = diff + C2 * (T + 1);                   // [T][k][2]
-    ks::PodRec* shapes = (ks::PodRec*)(res + C2 * T);                // [k] (an even number of words before it)
-    int32_t* off = e->d_qi.p;        // [n + 1]
-    int32_t* cur = off + n + 1;      // [n]
-    int32_t* cnt = cur + n;          // [n]
-    int32_t* list = cnt + n;         // [cap]
-    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * C2 * (T + 1), e->st));
-    HIPCHK(e, hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, e->st));
-    HIPCHK(e, hipMemcpyAsync(shapes, e->h_shapes.data(), sizeof(ks::PodRec) * k, hipMemcpyHostToDevice, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    // the listed pods' requests stay in device units (QScale 1): the count takes e->scale itself
-    HIPCHK(e, ks::launch_headroom_series(e->d_blk.p, nb, q_hi, t_lo, t_hi, e->s, (int32_t)n, e->dc.filter_feeds,
-                                         e->cfg.filters, milli_scale(e), shapes, k, e->b_node.p, e->b_status.p,
-                                         e->t0.p, e->dur.p, e->pods.p, cnt, off, cur, list, (int32_t)cap, diff, res,
-                                         e->st));
-    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C2 * T, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
-}
-
-// ---- placement preview (ks_place.hip) ----------------------------------------------------------
-// scheduleOne for k preview pods on a private copy of the state at tick t: the rebuilt rc rm rg nr in
-// milli-units (the shapes' own units; nothing of the engine is rescaled) in the query scratch — or in
-// device units when every request is a whole multiple of the engine's unit — decided in rounds:
-// scan + merge give the exact top-kPlaceL snapshot list of every shape still to be placed, one
-// workgroup decides pods in order until one needs a node outside its list (ks_device.h), and the
-// host reads back 16 bytes per round: the first undecided pod.
-static_assert(KS_PLACE_MAX_PODS == ks::kPlaceMaxPods && KS_PLACE_MAX_SHAPES == ks::kPlaceMaxShapes &&
-              KS_PLACE_MAX_SHAPES == KS_HEADROOM_MAX_SHAPES && KS_PLACE_NOT_FOUND == ks::kPlaceNotFound &&
-              KS_POD_OK == ks::kPlaceOk && KS_POD_OVER_CAPACITY == ks::kPlaceOverCapacity && KS_PLACE_INFO == 4 &&
-              sizeof(ks_placement) == sizeof(ks::Placement) && offsetof(ks_placement, score) == offsetof(ks::Placement, score) &&
-              offsetof(ks_placement, candidates) == offsetof(ks::Placement, candidates),
-              "ks_place_at constants and record");
-
-ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* req, const uint8_t* keymask,
-                      const uint64_t* tol, const uint64_t* sel, int32_t k, const int32_t* shape_of, ks_placement* out,
-                      int64_t* after_out, int64_t* info_out) {
-    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "place"); r != KS_OK) return r;
-    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "place: %d pods outside [1, %d]", (int)k, KS_PLACE_MAX_PODS);
-    if (!shape_of && k != n_shapes)
-        return fail(e, KS_EINVAL, "place: %d pods without shape_of need %d shapes, not %d", (int)k, (int)k, (int)n_shapes);
-    std::vector<int32_t> so(k);
-    for (int32_t j = 0; j < k; j++) {
-        so[j] = shape_of ? shape_of[j] : j;
-        if (so[j] < 0 || so[j] >= n_shapes)
-            return fail(e, KS_EINVAL, "place: pod %d has shape %d outside [0, %d)", (int)j, (int)so[j], (int)n_shapes);
-    }
-    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
-    int64_t info[KS_PLACE_INFO] = {0, 0, 0, 0};
-    if (e->n == 0) {
-        for (int32_t j = 0; j < k; j++) out[j] = ks_placement{-1, KS_PLACE_NOT_FOUND, -1, 0};
-        info[3] = k;
-        if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
-        return KS_OK;
-    }
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t);
-    const int64_t nb = usage_blocks(e, t, q_hi);
-    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
-    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long), L = ks::kPlaceL, S = KS_PLACE_MAX_SHAPES;
-    constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
-    const int64_t up_words = W * S + (k + 1) / 2;  // one upload: the shape records, then shape_of
-    const int64_t rb_words = 2 + PW * k;           // rb[4] (read back every round), then out[k] (read once)
-    HIPCHK(e, e->d_qs.reserve(4 * np + up_words + S * nblk * L + S * L + S + rb_words + 4 * n, e->st));
-    HIPCHK(e, e->d_qi.reserve(S * nblk, e->st));
-    ks::PlaceBufs b{};
-    unsigned long long* w = e->d_qs.p;
-    b.state = (int64_t*)w;                 w += 4 * np;    // [4][np]: rc rm rg nr at t, milli-units
-    b.n_pad = np;
-    unsigned long long* up = w;            w += up_words;
-    b.shapes = (const ks::PodRec*)up;                      // [n_shapes] (of S)
-    b.shape_of = (const int32_t*)(up + W * S);             // [k]
-    b.lists = (uint64_t*)w;                w += S * nblk * L;
-    b.top = (uint64_t*)w;                  w += S * L;
-    b.ccount = (long long*)w;              w += S;
-    unsigned long long* down = w;          w += rb_words;
-    b.rb = (int32_t*)down;
-    b.out = (ks::Placement*)(down + 2);
-    long long* after = (long long*)w;                      // [n][4]
-    b.cnt = e->d_qi.p;
-    std::vector<unsigned long long> h_up(up_words, 0ull), h_down(rb_words, 0ull);
-    // whole-unit requests: the call runs in device units (same placements, 64-bit BalancedAllocation)
-    const ks::QScale milli = milli_scale(e), one{{1, 1, 1}};
-    const bool whole = ks::place_whole_units(e->h_shapes.data(), n_shapes, milli);
-    const ks::QScale sc = whole ? one : milli;
-    if (whole)
-        for (ks::PodRec& r : e->h_shapes)
-            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
-    std::memcpy(h_up.data(), e->h_shapes.data(), sizeof(ks::PodRec) * n_shapes);
-    std::memcpy(h_up.data() + W * S, so.data(), sizeof(int32_t) * k);
-    HIPCHK(e, hipMemsetAsync(b.state, 0, sizeof(unsigned long long) * 4 * np, e->st));
-    HIPCHK(e, hipMemcpyAsync(up, h_up.data(), sizeof(unsigned long long) * up_words, hipMemcpyHostToDevice, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
-                                   e->pods.p, sc, 1, np, (unsigned long long*)b.state, e->st));
-    const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, k, n_shapes, (int32_t)nblk};
-    int32_t first = 0;
-    while (first < k) {
-        uint64_t active = 0;
-        for (int32_t j = first; j < k; j++) active |= 1ull << so[j];
-        HIPCHK(e, ks::launch_place_round(e->s, pc, b, first, active, e->st));
-        int32_t rb[4] = {0, 1, 0, 0};
-        HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
-        HIPCHK(e, hipStreamSynchronize(e->st));
-        // a round decides its first pod at the least (nothing is changed yet): anything else is a fault
-        if (rb[1] != 0 || rb[0] <= first || rb[0] > k || ++info[0] > k)
-            return fail(e, KS_EDEVICE, "place: the round from pod %d decided no pod", (int)first);
-        first = rb[0];
-    }
-    static_assert(sizeof(ks_placement) == sizeof(ks::Placement), "ks_placement");
-    HIPCHK(e, hipMemcpyAsync(h_down.data(), down, sizeof(unsigned long long) * rb_words, hipMemcpyDeviceToHost, e->st));
-    if (after_out) {
-        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, whole ? milli : one, after, e->st));
-        HIPCHK(e, hipMemcpyAsync(after_out, after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
-    }
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    std::memcpy(out, h_down.data() + 2, sizeof(ks_placement) * k);
-    for (int32_t j = 0; j < k; j++) info[out[j].status == KS_POD_OK ? 1 : out[j].status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
-    if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
-    return KS_OK;
-}
-
-// ---- drain preview (ks_drain.hip) ---------------------------------------------------------------
-// The pods running at t on the cordoned nodes, gathered on the device in FIFO order (count, scan,
-// fill: the host reads the 8-byte total first and sizes the rest from it), then ks_place_at's round
-// loop over them in segments of at most KS_PLACE_MAX_SHAPES distinct shapes and KS_PLACE_MAX_PODS
-// pods (ks::drain_segment) on the state at t with the cordoned rows zeroed.  The pods' records are
-// whole device units, so the rounds run in device units throughout; a round commits its changed
-// nodes to the scratch, which carries the state from one segment to the next.
-static_assert(KS_DRAIN_MAX_PODS == ks::kDrainMaxPods && KS_DRAIN_INFO == 6 && sizeof(ks_eviction) == sizeof(ks::Eviction) &&
-              offsetof(ks_eviction, pod) == offsetof(ks::Eviction, pod) && offsetof(ks_eviction, from) == offsetof(ks::Eviction, from) &&
-              offsetof(ks_eviction, node) == offsetof(ks::Eviction, node) && offsetof(ks_eviction, status) == offsetof(ks::Eviction, status) &&
-              offsetof(ks_eviction, score) == offsetof(ks::Eviction, score) &&
-              offsetof(ks_eviction, candidates) == offsetof(ks::Eviction, candidates) && kUBlk == ks::kDrainBlk,
-              "ks_drain_at constants and record");
-
-ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* nodes, ks_eviction* out, int64_t cap,
-                      int64_t* n_out, int64_t* after_out, int64_t* info_out) {
-    if (!e || !nodes || !n_out || cap < 0 || (cap > 0 && !out)) return KS_EINVAL;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
-    if (n_drain < (n ? 1 : 0) || n_drain > n)
-        return fail(e, KS_EINVAL, "drain: %d nodes outside [%d, %lld]", (int)n_drain, n ? 1 : 0, (long long)n);
-    const int64_t CW = (n + 31) / 32;
-    std::vector<uint32_t> h_cordon(CW, 0u);
-    for (int32_t j = 0; j < n_drain; j++) {
-        const int32_t nd = nodes[j];
-        if (nd < 0 || nd >= n) return fail(e, KS_EINVAL, "drain: node %d outside [0, %lld)", (int)nd, (long long)n);
-        if (h_cordon[nd >> 5] >> (nd & 31) & 1u) return fail(e, KS_EINVAL, "drain: node %d is listed twice", (int)nd);
-        h_cordon[nd >> 5] |= 1u << (nd & 31);
-    }
-    if (t < 0 || t > e->tick) return fail(e, KS_EINVAL, "tick %lld outside [0, %lld]", (long long)t, (long long)e->tick);
-    int64_t info[KS_DRAIN_INFO] = {0, 0, 0, 0, 0, 0};
-    if (n == 0) {
-        *n_out = 0;
-        if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
-        return KS_OK;
-    }
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, stage_flush(e));
-    const int64_t q_hi = bound_by(e, t);
-    const int64_t nb = usage_blocks(e, t, q_hi);
-    if (nb * kUBlk > INT32_MAX) return fail(e, KS_EINVAL, "drain: tick %lld holds too many candidate pods", (long long)t);
-    constexpr int64_t W = sizeof(ks::PodRec) / sizeof(unsigned long long), L = ks::kPlaceL, S = KS_PLACE_MAX_SHAPES;
-    constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
-    constexpr int64_t EW = sizeof(ks::Eviction) / sizeof(unsigned long long);
-    auto even = [](int64_t x) { return (x + 1) & ~(int64_t)1; };
-    // ---- the gather's count: cordon, block counts and offsets, the total (int32 scratch) ----
-    const int64_t o_bcnt = CW, o_boff = o_bcnt + nb, o_total = even(o_boff + nb), o_cnt = o_total + 2;
-    HIPCHK(e, e->d_qi.reserve(o_cnt + S * nblk, e->st));
-    ks::DrainBufs d{};
-    d.cordon = (const uint32_t*)e->d_qi.p;
-    d.bcnt = e->d_qi.p + o_bcnt;
-    d.boff = e->d_qi.p + o_boff;
-    d.total = (long long*)(e->d_qi.p + o_total);
-    HIPCHK(e, hipMemcpyAsync(e->d_qi.p, h_cordon.data(), sizeof(uint32_t) * CW, hipMemcpyHostToDevice, e->st));
-    if (ks_status r = upload_blocks(e, nb); r != KS_OK) return r;
-    HIPCHK(e, ks::launch_drain_count(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p, d,
-                                     e->st));
-    long long total = 0;
-    HIPCHK(e, hipMemcpyAsync(&total, d.total, sizeof(total), hipMemcpyDeviceToHost, e->st));  // 8 bytes first
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    if (total < 0 || total > nb * kUBlk) return fail(e, KS_EDEVICE, "drain: the gather counted %lld pods", total);
-    const int64_t n_ev = total;
-    *n_out = n_ev;
-    if (n_ev > cap || n_ev > KS_DRAIN_MAX_PODS)
-        return fail(e, KS_ERANGE, "drain: %lld evicted pods, room for %lld (at most %d per call)", (long long)n_ev,
-                    (long long)std::min<int64_t>(cap, KS_DRAIN_MAX_PODS), KS_DRAIN_MAX_PODS);
-    // ---- the rest of the scratch, sized from the total ----
-    const int64_t up_words = W * S + (KS_PLACE_MAX_PODS + 1) / 2;  // per segment: the shape records, then shape_of
-    int64_t o = 0;
-    const int64_t o_state = o;   o += 4 * np;
-    const int64_t o_up = o;      o += up_words;
-    const int64_t o_lists = o;   o += S * nblk * L;
-    const int64_t o_top = o;     o += S * L;
-    const int64_t o_cc = o;      o += S;
-    const int64_t o_rb = o;      o += 2;
-    const int64_t o_placed = o;  o += PW * n_ev;
-    const int64_t o_pod = o;     o += n_ev;
-    const int64_t o_from = o;    o = even(o + (n_ev + 1) / 2);
-    const int64_t o_rec = o;     o += W * n_ev;    // 16-byte aligned: an even word offset
-    const int64_t o_evict = o;   o += EW * n_ev;
-    const int64_t o_after = o;   o += 4 * n;
-    static_assert((W * S) % 2 == 0, "shape_of follows the shape records on a 16-byte boundary");
-    HIPCHK(e, e->d_qs.reserve(o, e->st));
-    unsigned long long* w = e->d_qs.p;
-    ks::PlaceBufs b{};
-    b.state = (int64_t*)(w + o_state);
-    b.n_pad = np;
-    unsigned long long* up = w + o_up;
-    b.shapes = (const ks::PodRec*)up;
-    b.shape_of = (const int32_t*)(up + W * S);
-    b.lists = (uint64_t*)(w + o_lists);
-    b.top = (uint64_t*)(w + o_top);
-    b.ccount = (long long*)(w + o_cc);
-    b.rb = (int32_t*)(w + o_rb);
-    b.cnt = e->d_qi.p + o_cnt;
-    ks::Placement* placed = (ks::Placement*)(w + o_placed);
-    d.ev_pod = (long long*)(w + o_pod);
-    d.ev_from = (int32_t*)(w + o_from);
-    d.ev_rec = (ks::PodRec*)(w + o_rec);
-    d.cap = n_ev;
-    ks::Eviction* evict = (ks::Eviction*)(w + o_evict);
-    long long* after = (long long*)(w + o_after);
-    const ks::QScale one{{1, 1, 1}};
-    HIPCHK(e, hipMemsetAsync(b.state, 0, sizeof(unsigned long long) * 4 * np, e->st));
-    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
-                                   e->pods.p, one, 1, np, (unsigned long long*)b.state, e->st));
-    HIPCHK(e, ks::launch_drain_clear(d.cordon, (int32_t)n, b.state, np, e->st));
-    std::vector<ks::Eviction> h_ev(n_ev);
-    if (n_ev) {
-        HIPCHK(e, ks::launch_drain_fill(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
-                                        e->pods.p, d, e->st));
-        std::vector<ks::PodRec> recs(n_ev);
-        HIPCHK(e, hipMemcpyAsync(recs.data(), d.ev_rec, sizeof(ks::PodRec) * n_ev, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(e, hipStreamSynchronize(e->st));
-        std::vector<unsigned long long> h_up(up_words, 0ull);
-        std::vector<int32_t> so(KS_PLACE_MAX_PODS);
-        ks::PodRec seg_shapes[KS_PLACE_MAX_SHAPES];
-        for (int64_t start = 0; start < n_ev;) {
-            int32_t ns = 0;
-            const int64_t end = ks::drain_segment(recs.data(), n_ev, start, seg_shapes, &ns, so.data());
-            const int32_t k = (int32_t)(end - start);
-            if (k < 1 || ns < 1) return fail(e, KS_EDEVICE, "drain: empty segment at evicted pod %lld", (long long)start);
-            std::memcpy(h_up.data(), seg_shapes, sizeof(ks::PodRec) * ns);
-            std::memcpy(h_up.data() + W * S, so.data(), sizeof(int32_t) * k);
-            HIPCHK(e, hipMemcpyAsync(up, h_up.data(), sizeof(unsigned long long) * (W * S + (k + 1) / 2),
-                                     hipMemcpyHostToDevice, e->st));
-            b.out = placed + start;
-            const ks::PlaceCfg pc{e->dc, one, (int32_t)n, k, ns, (int32_t)nblk};
-            int32_t first = 0;
-            int64_t rounds = 0;
-            while (first < k) {
-                uint64_t active = 0;
-                for (int32_t j = first; j < k; j++) active |= 1ull << so[j];
-                HIPCHK(e, ks::launch_place_round(e->s, pc, b, first, active, e->st, d.cordon));
-                int32_t rb[4] = {0, 1, 0, 0};
-                HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
-                HIPCHK(e, hipStreamSynchronize(e->st));
-                // as ks_place_at: a round decides its first pod at the least
-                if (rb[1] != 0 || rb[0] <= first || rb[0] > k || ++rounds > k)
-                    return fail(e, KS_EDEVICE, "drain: the round from evicted pod %lld decided no pod",
-                                (long long)(start + first));
-                first = rb[0];
-            }
-            info[0] += rounds;
-            info[4]++;
-            start = end;
-        }
-        HIPCHK(e, ks::launch_drain_pack(d.ev_pod, d.ev_from, placed, n_ev, evict, e->st));
-        HIPCHK(e, hipMemcpyAsync(h_ev.data(), evict, sizeof(ks::Eviction) * n_ev, hipMemcpyDeviceToHost, e->st));
-    }
-    if (after_out) {
-        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, milli_scale(e), after, e->st));
-        HIPCHK(e, hipMemcpyAsync(after_out, after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
-    }
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    std::vector<uint32_t> seen(CW, 0u);
-    int64_t busy = 0;
-    for (int64_t i = 0; i < n_ev; i++) {
-        const ks::Eviction& v = h_ev[i];
-        info[v.status == KS_POD_OK ? 1 : v.status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
-        if ((uint32_t)v.from < (uint32_t)n && !(seen[v.from >> 5] >> (v.from & 31) & 1u)) {
-            seen[v.from >> 5] |= 1u << (v.from & 31);
-            busy++;
-        }
-    }
-    info[5] = n_drain - busy;
-    if (n_ev) std::memcpy(out, h_ev.data(), sizeof(ks_eviction) * n_ev);
-    if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
-    return KS_OK;
-}
-
-uint64_t ks_node_mix(int64_t node) {
-    uint64_t z = (uint64_t)(node + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// Name-keyed index: every pod bound per node in FIFO order, extended over the binds
-// [idx_upto, done) on each query; a key's stored pod is the last one bound there (Store
-// replaces, kubesim/node/node.go:58).
-static void index_binds(ks_engine* e) {
-    if ((int64_t)e->node_pods.size() < e->n) e->node_pods.resize(e->n);
-    for (int64_t q = e->idx_upto; q < e->done; q++) {
-        const int32_t nd = e->h_node[q];
-        if (nd < 0) continue;  // the pod an aborted run stopped at is never stored
-        e->node_pods[nd].push_back(q);
-    }
-    e->idx_upto = e->done;
-}
-
-ks_status ks_pod_lookup(ks_engine* e, int32_t node, int64_t key_id, int64_t* pod_out) {
-    if (!e || !pod_out) return KS_EINVAL;
-    *pod_out = -1;
-    if (node < 0 || node >= e->n) return fail(e, KS_EINVAL, "node %d out of range", node);
-    index_binds(e);
-    const std::vector<int64_t>& v = e->node_pods[node];
-    for (auto it = v.rbegin(); it != v.rend(); ++it)  // the last Store under the key wins
-        if (e->h_key[*it] == key_id) {
-            *pod_out = *it;
-            return KS_OK;
-        }
-    return fail(e, KS_ENOTFOUND, "pod with key %lld not found on node %d", (long long)key_id, node);
-}
-
-ks_status ks_node_pods(ks_engine* e, int32_t node, int64_t* pods_out, int64_t cap, int64_t* n_out) {
-    if (!e || !n_out || cap < 0 || (cap > 0 && !pods_out)) return KS_EINVAL;
-    *n_out = 0;
-    if (node < 0 || node >= e->n) return fail(e, KS_EINVAL, "node %d out of range", node);
-    index_binds(e);
-    const std::vector<int64_t>& v = e->node_pods[node];
-    // one pod per key: the last one bound here (a pod is listed iff no later pod on this node
-    // has its key)
-    std::unordered_map<int64_t, int64_t> last;
-    last.reserve(v.size());
-    for (int64_t q : v) last[e->h_key[q]] = q;
-    int64_t k = 0;
-    for (int64_t q : v)
-        if (last[e->h_key[q]] == q) {
-            if (k < cap) pods_out[k] = q;
-            k++;
-        }
-    *n_out = k;
-    return KS_OK;
-}
-
-ks_status ks_pod_status(ks_engine* e, int64_t pod_lo, int64_t n, ks_pod_info* out) {
-    if (!e || (n > 0 && !out) || pod_lo < 0 || n < 0 || pod_lo + n > e->P) return KS_EINVAL;
-    if (n == 0) return KS_OK;
-    const int64_t hi = std::min(pod_lo + n, e->done), nb = std::max<int64_t>(hi - pod_lo, 0);
-    std::vector<int32_t> node(nb), status(nb);
-    if (nb) {
-        HIPCHK(e, hipSetDevice(e->device));
-        HIPCHK(e, stage_flush(e));
-        HIPCHK(e, hipMemcpyAsync(node.data(), e->b_node.p + pod_lo, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(e, hipMemcpyAsync(status.data(), e->b_status.p + pod_lo, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(e, hipStreamSynchronize(e->st));
-    }
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t q = pod_lo + i;
-        ks_pod_info& o = out[i];
-        o.total_seconds = e->h_total_sec[q];
-        const bool bound = i < nb && node[i] >= 0;
-        o.node = bound ? node[i] : -1;
-        o.start_tick = bound ? e->h_bind_tick[q] : -1;
-        if (!bound) o.phase = KS_PHASE_PENDING;
-        else if (status[i] != KS_POD_OK) o.phase = KS_PHASE_FAILED;  // CapacityExceeded
-        else {
-            // IsRunning (kubesim/pod/pod.go:67-69): passed = (t - t0) * tick < Σ phase seconds
-            const int64_t dt = e->tick - e->h_bind_tick[q];
-            o.phase = (dt >= 0 && dt < e->h_dur[q]) ? KS_PHASE_RUNNING : KS_PHASE_SUCCEEDED;
-        }
-    }
-    return KS_OK;
-}
-
 int64_t ks_current_tick(const ks_engine* e) { return e ? e->tick : -1; }
 int32_t ks_tick_seconds(const ks_engine* e) { return e ? e->cfg.tick_seconds : -1; }
 int64_t ks_queued_pods(const ks_engine* e) { return e ? e->P - e->done : -1; }
@@ -2697,136 +1735,4 @@ ks_status ks_debug_watch(ks_engine* e, int64_t pod) {
 void ks_set_profiling(ks_engine* e, int enable) {
     if (e) e->profiling = enable != 0;
 }
-
-ks_status ks_selftest(int32_t device, int32_t test, int64_t* failures) {
-    if (!failures || (test != KS_SELFTEST_LR_MICRO && test != KS_SELFTEST_MICRO_STATES)) return KS_EINVAL;
-    *failures = -1;
-    if (hipSetDevice(device) != hipSuccess) return KS_EDEVICE;
-    unsigned long long* d = nullptr;
-    unsigned long long h = 0;
-    bool ok = hipMalloc(&d, sizeof h) == hipSuccess;
-    ok = ok && hipMemset(d, 0, sizeof h) == hipSuccess;
-    ok = ok && (test == KS_SELFTEST_LR_MICRO ? ks::launch_selftest_lr_micro(d, nullptr)
-                                             : ks::launch_selftest_micro_states(d, nullptr)) == hipSuccess;
-    ok = ok && hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
-    if (d) (void)hipFree(d);
-    if (!ok) return KS_EDEVICE;
-    *failures = (int64_t)h;
-    return KS_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The evaluator mode of a ks_selftest_eval column and whether the column holds the node in 32-bit words.
-struct EvColumn { int mode; bool words; };
-EvColumn ev_column(int bit) {
-    if (bit == ks::kEvScanCol) return {ks::kEvalMicro, false};
-    const int col = bit < ks::kEvPruneBit ? bit : bit - ks::kEvPruneBit;
-    const int group = col / 4;
-    // totals: NodeV, record, NS32, conv; bounds: NodeV, NS32, conv (conv's wide entry is a NodeV)
-    const bool words = bit < ks::kEvPruneBit ? (group == 1 || group == 2) : group == 1;
-    return {col % 4, words};
-}
-
-// The batch respects what ks_load_nodes / ks_submit_pods guarantee every evaluator (values in range,
-// usage within its capacity) and the domain of every requested column's evaluator (update_mode).
-bool ev_batch_valid(const ks::Cfg& c, int64_t n, const int64_t* alloc, const int64_t* run, const int64_t* req,
-                    uint32_t variants) {
-    bool need[4] = {false, false, false, false}, words = false;
-    for (int b = 0; b < ks::kEvPruneBit + ks::kEvPruneCols; b++) {
-        if (!((variants >> b) & 1u)) continue;
-        const EvColumn col = ev_column(b);
-        need[col.mode] = true;
-        words |= col.words;
-    }
-    if (need[ks::kEvalMicro] && (c.w_lr >= ks::kMicroWeight || c.w_ba >= ks::kMicroWeight)) return false;
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t* a = alloc + i * 4;
-        const int64_t* r = run + i * 4;
-        for (int k = 0; k < 3; k++) {
-            if (a[k] < -1 || a[k] >= kMaxValue) return false;
-            if (r[k] < 0 || r[k] > std::max<int64_t>(a[k], 0)) return false;
-            if (req[i * 3 + k] < 0 || req[i * 3 + k] >= kMaxValue) return false;
-        }
-        if (a[3] < 0 || a[3] >= kMaxValue || r[3] < 0 || r[3] >= INT32_MAX) return false;  // (nr < ap stays exact with ap clamped to INT_MAX)
-        const int64_t m = std::max(std::max(a[0], a[1]), a[2]);
-        const int64_t prod = m < ks::kTinyCap ? std::max<int64_t>(a[0], 0) * std::max<int64_t>(a[1], 0) : 0;
-        if (words && m >= (int64_t)0xFFFFFFFF) return false;
-        if (need[ks::kEvalNarrow] && m >= ks::kNarrowCap) return false;
-        if (need[ks::kEvalTiny] && (m >= ks::kTinyCap || prod >= ks::kTinyCap)) return false;
-        if (need[ks::kEvalMicro] && (m >= ks::kMicroCap || prod >= ks::kMicroProd)) return false;
-    }
-    return true;
-}
-
-}  // namespace
-
-extern "C" {
-
-ks_status ks_selftest_eval(int32_t device, const ks_eval_cfg* cfg, int64_t n, const int64_t* alloc,
-                           const int64_t* run, const int64_t* req, const uint32_t* keymask, const uint64_t* masks,
-                           uint32_t variants, uint32_t* total1, uint32_t* tmax, uint32_t* live) {
-    constexpr uint32_t kAll = (1u << (ks::kEvPruneBit + ks::kEvPruneCols)) - 1u;
-    constexpr uint32_t kTotals = (1u << ks::kEvPruneBit) - 1u;
-    static_assert(ks::kEvTotalCols == KS_EVAL_TOTAL_COLS && ks::kEvPruneCols == KS_EVAL_PRUNE_COLS, "column counts");
-    if (!cfg || !alloc || !run || !req || !keymask || !masks || n < 1 || n > KS_EVAL_MAX_CASES) return KS_EINVAL;
-    if (!variants || (variants & ~kAll)) return KS_EINVAL;
-    if ((variants & kTotals) && !total1) return KS_EINVAL;
-    if ((variants & ~kTotals) && (!tmax || !live)) return KS_EINVAL;
-    if ((cfg->filters & ~7u) || cfg->w_lr < 0 || cfg->w_ba < 0 || cfg->const_total < 0) return KS_EINVAL;
-    if ((int64_t)cfg->const_total + 10 * ((int64_t)cfg->w_lr + cfg->w_ba) >= (1LL << 30) - 2) return KS_EINVAL;
-    ks::EvalCases ec{};
-    ec.c.n_nodes = (int32_t)n;
-    ec.c.filter_feeds = cfg->filter_feeds != 0;
-    ec.c.filters = cfg->filters;
-    ec.c.has_scorers = cfg->has_scorers != 0;
-    ec.c.w_lr = cfg->w_lr; ec.c.w_ba = cfg->w_ba; ec.c.const_total = cfg->const_total;
-    ec.c.tick_seconds = 1;
-    ec.n = n;
-    ec.variants = variants;
-    if (!ev_batch_valid(ec.c, n, alloc, run, req, variants)) return KS_EINVAL;
-    // the scan's per-pod records, on the host as ks_submit_pods builds them
-    std::vector<ks::ScanRec> srec((size_t)n);
-    ks::EvalCases hc = ec;
-    hc.alloc = alloc; hc.run = run; hc.req = req; hc.keymask = keymask; hc.masks = masks;
-    for (int64_t i = 0; i < n; i++) srec[(size_t)i] = ks::scan_rec_micro(ec.c, ks::evcase_pod(hc, i));
-
-    if (hipSetDevice(device) != hipSuccess) return KS_EDEVICE;
-    const size_t sz_alloc = (size_t)n * 4 * 8, sz_req = (size_t)n * 3 * 8, sz_km = (size_t)n * 4;
-    const size_t sz_scan = (size_t)n * sizeof(ks::ScanRec);
-    const size_t sz_tot = (size_t)n * 4 * ks::kEvTotalCols, sz_pr = (size_t)n * 4 * ks::kEvPruneCols;
-    void* buf[9] = {};
-    const size_t size[9] = {sz_alloc, sz_alloc, sz_req, sz_km, sz_alloc, sz_scan, sz_tot, sz_pr, sz_pr};
-    const void* src[6] = {alloc, run, req, keymask, masks, srec.data()};
-    bool ok = true;
-    for (int k = 0; k < 9 && ok; k++) ok = hipMalloc(&buf[k], size[k]) == hipSuccess;
-    for (int k = 0; k < 6 && ok; k++) ok = hipMemcpy(buf[k], src[k], size[k], hipMemcpyHostToDevice) == hipSuccess;
-    for (int k = 6; k < 9 && ok; k++) ok = hipMemset(buf[k], 0, size[k]) == hipSuccess;
-    ec.alloc = (const int64_t*)buf[0]; ec.run = (const int64_t*)buf[1]; ec.req = (const int64_t*)buf[2];
-    ec.keymask = (const uint32_t*)buf[3]; ec.masks = (const uint64_t*)buf[4]; ec.scan = (const ks::ScanRec*)buf[5];
-    ec.total1 = (uint32_t*)buf[6]; ec.tmax = (uint32_t*)buf[7]; ec.live = (uint32_t*)buf[8];
-    ok = ok && ks::launch_evtest_nodev(ec, nullptr) == hipSuccess;
-    ok = ok && ks::launch_evtest_rec12(ec, nullptr) == hipSuccess;
-    ok = ok && ks::launch_evtest_ns32(ec, nullptr) == hipSuccess;
-    ok = ok && ks::launch_evtest_conv(ec, nullptr) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
-    // only the requested columns reach the caller
-    for (int b = 0; b < ks::kEvPruneBit + ks::kEvPruneCols && ok; b++) {
-        if (!((variants >> b) & 1u)) continue;
-        const size_t col = (size_t)n * 4;
-        if (b < ks::kEvPruneBit) {
-            ok = hipMemcpy(total1 + (size_t)b * n, (char*)buf[6] + b * col, col, hipMemcpyDeviceToHost) == hipSuccess;
-        } else {
-            const size_t j = (size_t)(b - ks::kEvPruneBit);
-            ok = hipMemcpy(tmax + j * n, (char*)buf[7] + j * col, col, hipMemcpyDeviceToHost) == hipSuccess;
-            ok = ok && hipMemcpy(live + j * n, (char*)buf[8] + j * col, col, hipMemcpyDeviceToHost) == hipSuccess;
-        }
-    }
-    for (int k = 0; k < 9; k++)
-        if (buf[k]) (void)hipFree(buf[k]);
-    return ok ? KS_OK : KS_EDEVICE;
-}
-
 }  // extern "C"

@@ -1,0 +1,713 @@
+// ks_queries.cpp — the entry points of include/ks_engine.h that answer about a run after the fact:
+// filter / score of a pod, usage, the past-tick state queries, headroom, the placement and drain
+// previews and the name-keyed lookups.  They read the engine (ks_host.h) and write nothing a later
+// ks_step reads; their device scratch is the grow-only d_qs / d_qi, carved by ks_carve.h.
+#include <cstring>
+
+#include "ks_carve.h"
+#include "ks_host.h"
+
+using namespace ks_host;
+
+// ---- the pieces the queries share ---------------------------------------------------------------
+
+static ks_status check_tick(ks_engine* e, const char* what, int64_t t) {
+    if (t < 0 || t > e->tick)
+        return fail(e, KS_EINVAL, "%stick %lld outside [0, %lld]", what, (long long)t, (long long)e->tick);
+    return KS_OK;
+}
+
+static ks_status check_window(ks_engine* e, const char* what, int64_t t_lo, int64_t t_hi) {
+    if (t_lo < 0 || t_hi <= t_lo || t_hi - 1 > e->tick || t_hi - t_lo > kMaxDigestTicks)
+        return fail(e, KS_EINVAL, "%s window [%lld, %lld) outside [0, %lld] or longer than %lld ticks", what,
+                    (long long)t_lo, (long long)t_hi, (long long)e->tick + 1, (long long)kMaxDigestTicks);
+    return KS_OK;
+}
+
+// Candidate pod blocks of a usage query over ticks >= t_lo: blocks of the pods [0, q_hi) (bind
+// ticks are FIFO-monotone, so q_hi bounds the start side) holding a pod whose run end is > t_lo;
+// super blocks whose every pod ended by t_lo are skipped whole.
+static int64_t usage_blocks(ks_engine* e, int64_t t_lo, int64_t q_hi) {
+    e->h_blk.clear();
+    const int64_t nblk = (q_hi + kUBlk - 1) / kUBlk;
+    for (int64_t s = 0; s * kUSup < nblk; s++) {
+        if (e->sup_end[s] <= t_lo) continue;
+        const int64_t b1 = std::min(nblk, (s + 1) * kUSup);
+        for (int64_t b = s * kUSup; b < b1; b++)
+            if (e->blk_end[b] > t_lo) e->h_blk.push_back((int32_t)b);
+    }
+    return (int64_t)e->h_blk.size();
+}
+
+// pods bound at ticks <= t (a FIFO prefix of the binds made so far)
+static int64_t bound_by(const ks_engine* e, int64_t t) {
+    return std::upper_bound(e->h_bind_tick.begin(), e->h_bind_tick.begin() + e->done, t) - e->h_bind_tick.begin();
+}
+
+static_assert(kUBlk == 256, "usage index block = the usage kernels' workgroup");
+
+// Every past-tick query opens with this: the device, the staged submits, and the candidate blocks
+// of the pods [0, q_hi) over ticks >= t_lo, uploaded to d_blk (*nb of them).
+static ks_status query_blocks(ks_engine* e, int64_t t_lo, int64_t q_hi, int64_t* nb) {
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    *nb = usage_blocks(e, t_lo, q_hi);
+    if (!*nb) return KS_OK;
+    HIPCHK(e, e->d_blk.reserve(*nb, e->st));
+    HIPCHK(e, hipMemcpyAsync(e->d_blk.p, e->h_blk.data(), sizeof(int32_t) * *nb, hipMemcpyHostToDevice, e->st));
+    return KS_OK;
+}
+
+// Reserve what the sizing pass of a layout counted and rewind the cursors onto the scratch.
+static ks_status reserve_scratch(ks_engine* e, Carve* qs, Carve* qi) {
+    HIPCHK(e, e->d_qs.reserve(qs->at, e->st));
+    HIPCHK(e, e->d_qi.reserve(qi->at, e->st));
+    *qs = Carve(sizeof(unsigned long long), e->d_qs.p);
+    *qi = Carve(sizeof(int32_t), e->d_qi.p);
+    return KS_OK;
+}
+// A call's scratch: `layout` takes its ranges from the cursors qs (over d_qs) and qi (over d_qi) and
+// runs twice (ks_carve.h) — to size the two scratches, then, once they are reserved, for the pointers.
+#define CARVE_SCRATCH(e, layout)                                                          \
+    Carve qs(sizeof(unsigned long long)), qi(sizeof(int32_t));                            \
+    layout;                                                                               \
+    if (ks_status r_ = reserve_scratch((e), &qs, &qi); r_ != KS_OK) return r_;            \
+    layout
+
+static ks::QScale milli_scale(const ks_engine* e) { return ks::QScale{{e->scale[0], e->scale[1], e->scale[2]}}; }
+static constexpr ks::QScale kDeviceUnits{{1, 1, 1}};
+
+// The node table's rc rm rg nr at tick t, rebuilt from the binds into dst: the pods q < q_hi of the
+// nb uploaded blocks that were bound Ok and run at t, times scale; word c of node nd at
+// dst[nd * stride + c * pitch] ([n][4] rows: 4, 1; [4][pitch] planes: 1, n_pad).
+static ks_status rebuild_state(ks_engine* e, int64_t nb, int64_t q_hi, int64_t t, const ks::QScale& scale, int64_t stride,
+                               int64_t pitch, unsigned long long* dst) {
+    const int64_t words = stride == 1 ? 4 * pitch : 4 * e->n;
+    HIPCHK(e, hipMemsetAsync(dst, 0, sizeof(unsigned long long) * words, e->st));
+    HIPCHK(e, ks::launch_requested(e->d_blk.p, nb, q_hi, t, (int32_t)e->n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
+                                   e->pods.p, scale, stride, pitch, dst, e->st));
+    return KS_OK;
+}
+
+// the tail of ks_filter / ks_score (_at): copy the n-node result out once the evaluation is queued
+static ks_status copy_result(ks_engine* e, ks_status rc, void* dst, const void* src, size_t bytes) {
+    if (rc != KS_OK) return rc;
+    if (e->n) HIPCHK(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+extern "C" {
+
+// ---- filter / score of a queued pod, usage ------------------------------------------------------
+
+static ks_status eval_pod(ks_engine* e, int64_t pod) {
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (pod < 0 || pod >= e->P) return fail(e, KS_EINVAL, "pod %lld out of range", (long long)pod);
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, stage_flush(e));
+    ks_status r = flush_expiries(e);
+    if (r != KS_OK) return r;
+    if (e->n == 0) return KS_OK;
+    HIPCHK(e, ks::launch_eval_pod(e->dc, e->s, e->pods.p + pod, e->cfg.filters, e->d_mask, e->d_score, e->mode, e->st));
+    return KS_OK;
+}
+
+ks_status ks_filter(ks_engine* e, int64_t pod, uint8_t* mask_out) {
+    if (!e || !mask_out) return KS_EINVAL;
+    return copy_result(e, eval_pod(e, pod), mask_out, e->d_mask, e->n);
+}
+
+ks_status ks_score(ks_engine* e, int64_t pod, int64_t* score_out) {
+    if (!e || !score_out) return KS_EINVAL;
+    return copy_result(e, eval_pod(e, pod), score_out, e->d_score, sizeof(int64_t) * e->n);
+}
+
+ks_status ks_usage_at(ks_engine* e, int64_t t, int64_t* usage_out) {
+    if (!e || !usage_out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_tick(e, "usage ", t); r != KS_OK) return r;
+    if (e->n == 0) return KS_OK;
+    const int64_t q_hi = bound_by(e, t);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+    HIPCHK(e, hipMemsetAsync(e->d_usage, 0, sizeof(unsigned long long) * 3 * e->n, e->st));
+    if (nb) {
+        // (profiling: HIP events around the usage kernel alone — its roofline in bench.py)
+        if (e->profiling && e->ev[2]) HIPCHK(e, hipEventRecord(e->ev[2], e->st));
+        HIPCHK(e, ks::launch_usage(e->d_blk.p, nb, q_hi, t, e->cfg.tick_seconds, e->b_node.p, e->b_status.p, e->t0.p,
+                                   e->dur.p, e->phase_off.p, e->cum_sec.p, e->use.p, e->d_usage, e->st));
+        if (e->profiling && e->ev[3]) HIPCHK(e, hipEventRecord(e->ev[3], e->st));
+    }
+    HIPCHK(e, hipMemcpyAsync(usage_out, e->d_usage, sizeof(int64_t) * 3 * e->n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (e->profiling && nb && e->ev[2]) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
+        e->kstats.usage_ms += ms;
+        e->kstats.usage_n += 1;
+        e->kstats.usage_pods += (int64_t)nb * ks::usage_block_pods();
+    }
+    return KS_OK;
+}
+
+ks_status ks_usage(ks_engine* e, int64_t* usage_out) {
+    if (!e) return KS_EINVAL;
+    return ks_usage_at(e, e->tick, usage_out);
+}
+
+ks_status ks_usage_digest(ks_engine* e, int64_t t_lo, int64_t t_hi, uint64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_window(e, "digest", t_lo, t_hi); r != KS_OK) return r;
+    const int64_t T = t_hi - t_lo;
+    const int64_t q_hi = bound_by(e, t_hi - 1);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t_lo, q_hi, &nb); r != KS_OK) return r;
+    HIPCHK(e, e->d_digest.reserve(6 * (T + 1) + 6 * T, e->st));
+    unsigned long long* diff = e->d_digest.p;
+    unsigned long long* res = diff + 6 * (T + 1);
+    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * 6 * (T + 1), e->st));
+    HIPCHK(e, ks::launch_usage_digest(e->d_blk.p, nb, q_hi, t_lo, t_hi, e->cfg.tick_seconds, e->b_node.p, e->b_status.p,
+                                      e->t0.p, e->dur.p, e->preg.p, e->phase_off.p, e->cum_sec.p, e->use.p, diff, res,
+                                      e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(uint64_t) * 6 * T, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// ---- past-tick state queries (ks_query.hip) ----------------------------------------------------
+// The node table's rc rm rg nr at any past tick, rebuilt from the binds: the pods q < q_hi that
+// were bound Ok and run at t.  They share the usage queries' run-interval index, read only the
+// bind arrays and the pod records, and leave the live table and the expiry state alone — so they
+// answer after an aborted run too (on the binds made before it).
+
+ks_status ks_requested_at(ks_engine* e, int64_t t, int64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    if (e->n == 0) return KS_OK;
+    const int64_t q_hi = bound_by(e, t);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+    unsigned long long* state;  // [n][4], milli-units
+    CARVE_SCRATCH(e, state = qs.take<unsigned long long>(4 * e->n));
+    if (ks_status r = rebuild_state(e, nb, q_hi, t, milli_scale(e), 4, 1, state); r != KS_OK) return r;
+    HIPCHK(e, hipMemcpyAsync(out, state, sizeof(int64_t) * 4 * e->n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// Filter mask and score of an already-bound pod as scheduleOne saw them: the evaluator of
+// ks_filter / ks_score on a copy of the node table whose rc rm rg nr are the state rebuilt from the
+// pods q < pod running at the pod's bind tick (every one of them was bound at an earlier tick).
+static ks_status eval_pod_at(ks_engine* e, int64_t pod) {
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (pod < 0 || pod >= e->done || e->h_node[pod] < 0)
+        return fail(e, KS_EINVAL, "pod %lld is not bound (queued pods: ks_filter / ks_score)", (long long)pod);
+    if (e->n == 0) return KS_OK;
+    const int64_t t = e->h_bind_tick[pod], np = e->n_pad;
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, pod, &nb); r != KS_OK) return r;
+    int64_t* b;  // [4][np], device units
+    CARVE_SCRATCH(e, b = qs.take<int64_t>(4 * np));
+    if (ks_status r = rebuild_state(e, nb, pod, t, kDeviceUnits, 1, np, (unsigned long long*)b); r != KS_OK) return r;
+    ks::NodeSoA s = e->s;
+    s.rc = b; s.rm = b + np; s.rg = b + 2 * np; s.nr = b + 3 * np;
+    HIPCHK(e, ks::launch_eval_pod(e->dc, s, e->pods.p + pod, e->cfg.filters, e->d_mask, e->d_score, e->mode, e->st));
+    return KS_OK;
+}
+
+ks_status ks_filter_at(ks_engine* e, int64_t pod, uint8_t* mask_out) {
+    if (!e || !mask_out) return KS_EINVAL;
+    return copy_result(e, eval_pod_at(e, pod), mask_out, e->d_mask, e->n);
+}
+
+ks_status ks_score_at(ks_engine* e, int64_t pod, int64_t* score_out) {
+    if (!e || !score_out) return KS_EINVAL;
+    return copy_result(e, eval_pod_at(e, pod), score_out, e->d_score, sizeof(int64_t) * e->n);
+}
+
+// prefix counts of the Ok / OverCapacity binds, extended over the pods [cum_upto, done)
+static void count_binds(ks_engine* e) {
+    for (int64_t q = e->cum_upto; q < e->done; q++) {
+        e->cum_ok.push_back(e->cum_ok.back() + (e->h_status[q] == KS_POD_OK && e->h_node[q] >= 0));
+        e->cum_over.push_back(e->cum_over.back() + (e->h_status[q] == KS_POD_OVER_CAPACITY && e->h_node[q] >= 0));
+    }
+    e->cum_upto = e->done;
+}
+
+static_assert(KS_SERIES_COLS == ks::kSeriesCols, "ks_cluster_series columns");
+
+ks_status ks_cluster_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_window(e, "series", t_lo, t_hi); r != KS_OK) return r;
+    const int64_t T = t_hi - t_lo;
+    // pods off the queue by t_lo / by the window's last tick; arrivals likewise (both FIFO prefixes)
+    const int64_t q_lo = bound_by(e, t_lo), q_hi = bound_by(e, t_hi - 1);
+    const int64_t a_lo = std::upper_bound(e->h_arr.begin(), e->h_arr.end(), t_lo) - e->h_arr.begin();
+    const int64_t a_hi = std::upper_bound(e->h_arr.begin(), e->h_arr.end(), t_hi - 1) - e->h_arr.begin();
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t_lo, q_hi, &nb); r != KS_OK) return r;
+    count_binds(e);
+    ks::SeriesInit init{};
+    init.v[4] = e->cum_ok[q_lo];
+    init.v[5] = e->cum_over[q_lo];
+    init.v[6] = a_lo - q_lo;
+    const int64_t C = ks::kSeriesCols, n_arr = a_hi - a_lo;
+    unsigned long long *diff, *res;
+    int64_t* arr;
+    CARVE_SCRATCH(e, {
+        diff = qs.take<unsigned long long>(C * (T + 1));
+        res = qs.take<unsigned long long>(C * T);
+        arr = qs.take<int64_t>(n_arr);
+    });
+    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * C * (T + 1), e->st));
+    if (n_arr)
+        HIPCHK(e, hipMemcpyAsync(arr, e->h_arr.data() + a_lo, sizeof(int64_t) * n_arr, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, ks::launch_series(e->d_blk.p, nb, q_lo, q_hi, t_lo, t_hi, e->b_status.p, e->t0.p, e->dur.p, e->pods.p,
+                                milli_scale(e), arr, n_arr, init, diff, res, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C * T, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+ks_status ks_node_peaks(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) {
+    if (!e || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = check_window(e, "peaks", t_lo, t_hi); r != KS_OK) return r;
+    if (e->n == 0) return KS_OK;
+    const int64_t q_hi = bound_by(e, t_hi - 1);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t_lo, q_hi, &nb); r != KS_OK) return r;
+    const int64_t n = e->n, cap = nb * kUBlk;
+    if (cap > INT32_MAX) return fail(e, KS_EINVAL, "peaks window holds too many candidate pods");
+    long long* peaks;
+    NodeLists l;
+    CARVE_SCRATCH(e, {
+        peaks = qs.take<long long>(4 * n);
+        l = carve_node_lists(qi, n, cap);
+    });
+    HIPCHK(e, hipMemsetAsync(l.cnt, 0, sizeof(int32_t) * n, e->st));
+    HIPCHK(e, ks::launch_node_peaks(e->d_blk.p, nb, q_hi, t_lo, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p,
+                                    e->dur.p, e->pods.p, milli_scale(e), l.cnt, l.off, l.cur, l.list, (int32_t)cap, peaks,
+                                    e->st));
+    HIPCHK(e, hipMemcpyAsync(out, peaks, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// ---- headroom queries (ks_query.hip) -----------------------------------------------------------
+// How many more pods of a shape Node.CreatePod (kubesim/node/node.go:44-47) would admit per node at a
+// past tick: the rebuilt rc rm rg nr against the cluster's alloc / taints / labels.  Shapes live only
+// for the call: nothing is appended, rescaled or written back (their requests stay in milli-units,
+// the device multiplies the free amount by e->scale instead of dividing the request).
+static_assert(KS_HEADROOM_COLS == ks::kHeadCols && KS_HEADROOM_MAX_SHAPES == ks::kHeadMaxShapes &&
+              KS_HEADROOM_NODE_MAX == ks::kHeadMax, "ks_headroom_* constants");
+constexpr int64_t kMaxHeadSeries = 1LL << 22;  // k * (t_hi - t_lo) at the most
+
+static ks_status head_shapes(ks_engine* e, int32_t k, const int64_t* req, const uint8_t* keymask, const uint64_t* tol,
+                             const uint64_t* sel, const char* what = "headroom") {
+    if (k < 1 || k > KS_HEADROOM_MAX_SHAPES)
+        return fail(e, KS_EINVAL, "%s: %d shapes outside [1, %d]", what, (int)k, KS_HEADROOM_MAX_SHAPES);
+    e->h_shapes.assign(k, ks::PodRec{});
+    for (int32_t j = 0; j < k; j++) {
+        if (keymask[j] & ~7u) return fail(e, KS_EINVAL, "%s shape %d: keymask %u has bits above 4", what, (int)j, (unsigned)keymask[j]);
+        ks::PodRec& r = e->h_shapes[j];
+        for (int c = 0; c < 3; c++) {
+            if (!(keymask[j] >> c & 1)) continue;  // unmasked keys are ignored
+            const int64_t q = req[j * 3 + c];
+            if (q < 0 || q >= ks::kHeadReqMax) return fail(e, KS_EINVAL, "%s shape %d: request %d out of range", what, (int)j, c);
+            r.req[c] = q;
+        }
+        r.tol = tol[j];
+        r.sel = sel[j];
+        r.keymask = keymask[j];
+    }
+    return KS_OK;
+}
+
+ks_status ks_headroom_at(ks_engine* e, int64_t t, int32_t k, const int64_t* req, const uint8_t* keymask,
+                         const uint64_t* tol, const uint64_t* sel, int64_t* out, int32_t* per_node_out) {
+    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, k, req, keymask, tol, sel); r != KS_OK) return r;
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    if (e->n == 0) {
+        for (int32_t j = 0; j < k; j++)
+            for (int c = 0; c < KS_HEADROOM_COLS; c++) out[j * KS_HEADROOM_COLS + c] = c == 3 ? -1 : 0;
+        return KS_OK;
+    }
+    const int64_t q_hi = bound_by(e, t);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    unsigned long long *state, *part;
+    ks::PodRec* shapes;
+    long long* res;
+    int32_t* per_node;
+    CARVE_SCRATCH(e, {
+        state = qs.take<unsigned long long>(4 * np);  // [4][np]: rc rm rg nr at t, device units
+        shapes = qs.take<ks::PodRec>(k, 2);
+        part = qs.take<unsigned long long>(nblk * k * 3);  // [nblk][k][3]
+        res = qs.take<long long>((int64_t)k * KS_HEADROOM_COLS);
+        per_node = qi.take<int32_t>(per_node_out ? (int64_t)k * n : 0);
+    });
+    if (ks_status r = rebuild_state(e, nb, q_hi, t, kDeviceUnits, 1, np, state); r != KS_OK) return r;
+    HIPCHK(e, hipMemcpyAsync(shapes, e->h_shapes.data(), sizeof(ks::PodRec) * k, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, ks::launch_headroom(e->s, (const int64_t*)state, np, (int32_t)n, e->dc.filter_feeds, e->cfg.filters,
+                                  milli_scale(e), shapes, k, part, res, per_node_out ? per_node : nullptr, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * k * KS_HEADROOM_COLS, hipMemcpyDeviceToHost, e->st));
+    if (per_node_out)
+        HIPCHK(e, hipMemcpyAsync(per_node_out, per_node, sizeof(int32_t) * k * n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+ks_status ks_headroom_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int32_t k, const int64_t* req,
+                             const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel, int64_t* out) {
+    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, k, req, keymask, tol, sel); r != KS_OK) return r;
+    if (ks_status r = check_window(e, "headroom", t_lo, t_hi); r != KS_OK) return r;
+    const int64_t T = t_hi - t_lo, C2 = 2 * (int64_t)k;
+    if (k * T > kMaxHeadSeries)
+        return fail(e, KS_EINVAL, "headroom series: %d shapes x %lld ticks is more than %lld", (int)k, (long long)T,
+                    (long long)kMaxHeadSeries);
+    if (e->n == 0) {
+        std::fill(out, out + C2 * T, (int64_t)0);
+        return KS_OK;
+    }
+    const int64_t q_hi = bound_by(e, t_hi - 1);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t_lo, q_hi, &nb); r != KS_OK) return r;
+    const int64_t n = e->n, cap = nb * kUBlk;
+    if (cap > INT32_MAX) return fail(e, KS_EINVAL, "headroom window holds too many candidate pods");
+    unsigned long long *diff, *res;
+    ks::PodRec* shapes;
+    NodeLists l;
+    CARVE_SCRATCH(e, {
+        diff = qs.take<unsigned long long>(C2 * (T + 1));  // [2 k][T + 1]
+        res = qs.take<unsigned long long>(C2 * T);         // [T][k][2]
+        shapes = qs.take<ks::PodRec>(k, 2);
+        l = carve_node_lists(qi, n, cap);
+    });
+    HIPCHK(e, hipMemsetAsync(diff, 0, sizeof(unsigned long long) * C2 * (T + 1), e->st));
+    HIPCHK(e, hipMemsetAsync(l.cnt, 0, sizeof(int32_t) * n, e->st));
+    HIPCHK(e, hipMemcpyAsync(shapes, e->h_shapes.data(), sizeof(ks::PodRec) * k, hipMemcpyHostToDevice, e->st));
+    // the listed pods' requests stay in device units (QScale 1): the count takes e->scale itself
+    HIPCHK(e, ks::launch_headroom_series(e->d_blk.p, nb, q_hi, t_lo, t_hi, e->s, (int32_t)n, e->dc.filter_feeds,
+                                         e->cfg.filters, milli_scale(e), shapes, k, e->b_node.p, e->b_status.p,
+                                         e->t0.p, e->dur.p, e->pods.p, l.cnt, l.off, l.cur, l.list, (int32_t)cap, diff,
+                                         res, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C2 * T, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
+// ---- placement preview (ks_place.hip) ----------------------------------------------------------
+// scheduleOne for k preview pods on a private copy of the state at tick t: the rebuilt rc rm rg nr in
+// milli-units (the shapes' own units; nothing of the engine is rescaled) in the query scratch — or in
+// device units when every request is a whole multiple of the engine's unit — decided in rounds:
+// scan + merge give the exact top-kPlaceL snapshot list of every shape still to be placed, one
+// workgroup decides pods in order until one needs a node outside its list (ks_device.h), and the
+// host reads back 16 bytes per round: the first undecided pod.
+static_assert(KS_PLACE_MAX_PODS == ks::kPlaceMaxPods && KS_PLACE_MAX_SHAPES == ks::kPlaceMaxShapes &&
+              KS_PLACE_MAX_SHAPES == KS_HEADROOM_MAX_SHAPES && KS_PLACE_NOT_FOUND == ks::kPlaceNotFound &&
+              KS_POD_OK == ks::kPlaceOk && KS_POD_OVER_CAPACITY == ks::kPlaceOverCapacity && KS_PLACE_INFO == 4 &&
+              sizeof(ks_placement) == sizeof(ks::Placement) && offsetof(ks_placement, score) == offsetof(ks::Placement, score) &&
+              offsetof(ks_placement, candidates) == offsetof(ks::Placement, candidates),
+              "ks_place_at constants and record");
+
+// One upload for a set of rounds: the shape records (ns of KS_PLACE_MAX_SHAPES), then shape_of[k].
+// h_up is the caller's: it outlives the copy.
+static ks_status upload_shapes(ks_engine* e, const ks::PlaceBufs& b, std::vector<unsigned long long>& h_up,
+                               const ks::PodRec* shapes, int32_t ns, const int32_t* so, int32_t k) {
+    const int64_t words = kShapeWords + (k + 1) / 2;
+    if ((int64_t)h_up.size() < words) h_up.resize(words, 0ull);
+    std::memcpy(h_up.data(), shapes, sizeof(ks::PodRec) * ns);
+    std::memcpy(h_up.data() + kShapeWords, so, sizeof(int32_t) * k);
+    HIPCHK(e, hipMemcpyAsync((void*)b.shapes, h_up.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, e->st));
+    return KS_OK;
+}
+
+// The rounds that decide pods [0, pc.k) of the uploaded shapes: each launches scan + merge + resolver
+// from the first undecided pod and reads back 16 bytes.  what and pod_base name the pod in the message
+// of a round that decided none; *rounds grows by the rounds run.
+static ks_status place_rounds(ks_engine* e, const ks::PlaceCfg& pc, const ks::PlaceBufs& b, const int32_t* so,
+                              const uint32_t* cordon, const char* what, int64_t pod_base, int64_t* rounds) {
+    int32_t first = 0;
+    for (int64_t r = 1; first < pc.k; r++) {
+        uint64_t active = 0;
+        for (int32_t j = first; j < pc.k; j++) active |= 1ull << so[j];
+        HIPCHK(e, ks::launch_place_round(e->s, pc, b, first, active, e->st, cordon));
+        int32_t rb[4] = {0, 1, 0, 0};
+        HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        // a round decides its first pod at the least (nothing is changed yet): anything else is a fault
+        if (rb[1] != 0 || rb[0] <= first || rb[0] > pc.k || r > pc.k)
+            return fail(e, KS_EDEVICE, "%s %lld decided no pod", what, (long long)(pod_base + first));
+        first = rb[0];
+        ++*rounds;
+    }
+    return KS_OK;
+}
+
+ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* req, const uint8_t* keymask,
+                      const uint64_t* tol, const uint64_t* sel, int32_t k, const int32_t* shape_of, ks_placement* out,
+                      int64_t* after_out, int64_t* info_out) {
+    if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "place"); r != KS_OK) return r;
+    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "place: %d pods outside [1, %d]", (int)k, KS_PLACE_MAX_PODS);
+    if (!shape_of && k != n_shapes)
+        return fail(e, KS_EINVAL, "place: %d pods without shape_of need %d shapes, not %d", (int)k, (int)k, (int)n_shapes);
+    std::vector<int32_t> so(k);
+    for (int32_t j = 0; j < k; j++) {
+        so[j] = shape_of ? shape_of[j] : j;
+        if (so[j] < 0 || so[j] >= n_shapes)
+            return fail(e, KS_EINVAL, "place: pod %d has shape %d outside [0, %d)", (int)j, (int)so[j], (int)n_shapes);
+    }
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    int64_t info[KS_PLACE_INFO] = {0, 0, 0, 0};
+    if (e->n == 0) {
+        for (int32_t j = 0; j < k; j++) out[j] = ks_placement{-1, KS_PLACE_NOT_FOUND, -1, 0};
+        info[3] = k;
+        if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
+        return KS_OK;
+    }
+    const int64_t q_hi = bound_by(e, t);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    PlaceScratch s;
+    CARVE_SCRATCH(e, s = carve_place_at(qs, qi, n, np, nblk, k));
+    const ks::PlaceBufs& b = s.b;  // state in milli-units, or device units (below)
+    // whole-unit requests: the call runs in device units (same placements, 64-bit BalancedAllocation)
+    const ks::QScale milli = milli_scale(e);
+    const bool whole = ks::place_whole_units(e->h_shapes.data(), n_shapes, milli);
+    const ks::QScale sc = whole ? kDeviceUnits : milli;
+    if (whole)
+        for (ks::PodRec& r : e->h_shapes)
+            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
+    if (ks_status r = rebuild_state(e, nb, q_hi, t, sc, 1, np, (unsigned long long*)b.state); r != KS_OK) return r;
+    std::vector<unsigned long long> h_up;
+    if (ks_status r = upload_shapes(e, b, h_up, e->h_shapes.data(), n_shapes, so.data(), k); r != KS_OK) return r;
+    const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, k, n_shapes, (int32_t)nblk};
+    if (ks_status r = place_rounds(e, pc, b, so.data(), nullptr, "place: the round from pod", 0, &info[0]); r != KS_OK)
+        return r;
+    // rb[4], then out[k]: one range, read once
+    constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
+    std::vector<unsigned long long> h_down(2 + PW * k, 0ull);
+    HIPCHK(e, hipMemcpyAsync(h_down.data(), b.rb, sizeof(unsigned long long) * h_down.size(), hipMemcpyDeviceToHost, e->st));
+    if (after_out) {
+        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, whole ? milli : kDeviceUnits, s.after, e->st));
+        HIPCHK(e, hipMemcpyAsync(after_out, s.after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    std::memcpy(out, h_down.data() + 2, sizeof(ks_placement) * k);
+    for (int32_t j = 0; j < k; j++) info[out[j].status == KS_POD_OK ? 1 : out[j].status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
+    if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
+    return KS_OK;
+}
+
+// ---- drain preview (ks_drain.hip) ---------------------------------------------------------------
+// The pods running at t on the cordoned nodes, gathered on the device in FIFO order (count, scan,
+// fill: the host reads the 8-byte total first and sizes the rest from it), then ks_place_at's round
+// loop over them in segments of at most KS_PLACE_MAX_SHAPES distinct shapes and KS_PLACE_MAX_PODS
+// pods (ks::drain_segment) on the state at t with the cordoned rows zeroed.  The pods' records are
+// whole device units, so the rounds run in device units throughout; a round commits its changed
+// nodes to the scratch, which carries the state from one segment to the next.
+static_assert(KS_DRAIN_MAX_PODS == ks::kDrainMaxPods && KS_DRAIN_INFO == 6 && sizeof(ks_eviction) == sizeof(ks::Eviction) &&
+              offsetof(ks_eviction, pod) == offsetof(ks::Eviction, pod) && offsetof(ks_eviction, from) == offsetof(ks::Eviction, from) &&
+              offsetof(ks_eviction, node) == offsetof(ks::Eviction, node) && offsetof(ks_eviction, status) == offsetof(ks::Eviction, status) &&
+              offsetof(ks_eviction, score) == offsetof(ks::Eviction, score) &&
+              offsetof(ks_eviction, candidates) == offsetof(ks::Eviction, candidates) && kUBlk == ks::kDrainBlk,
+              "ks_drain_at constants and record");
+
+ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* nodes, ks_eviction* out, int64_t cap,
+                      int64_t* n_out, int64_t* after_out, int64_t* info_out) {
+    if (!e || !nodes || !n_out || cap < 0 || (cap > 0 && !out)) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    if (n_drain < (n ? 1 : 0) || n_drain > n)
+        return fail(e, KS_EINVAL, "drain: %d nodes outside [%d, %lld]", (int)n_drain, n ? 1 : 0, (long long)n);
+    const int64_t CW = (n + 31) / 32;
+    std::vector<uint32_t> h_cordon(CW, 0u);
+    for (int32_t j = 0; j < n_drain; j++) {
+        const int32_t nd = nodes[j];
+        if (nd < 0 || nd >= n) return fail(e, KS_EINVAL, "drain: node %d outside [0, %lld)", (int)nd, (long long)n);
+        if (h_cordon[nd >> 5] >> (nd & 31) & 1u) return fail(e, KS_EINVAL, "drain: node %d is listed twice", (int)nd);
+        h_cordon[nd >> 5] |= 1u << (nd & 31);
+    }
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    int64_t info[KS_DRAIN_INFO] = {0, 0, 0, 0, 0, 0};
+    if (n == 0) {
+        *n_out = 0;
+        if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
+        return KS_OK;
+    }
+    const int64_t q_hi = bound_by(e, t);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+    if (nb * kUBlk > INT32_MAX) return fail(e, KS_EINVAL, "drain: tick %lld holds too many candidate pods", (long long)t);
+    // ---- the gather's count ----
+    DrainGather g;
+    { CARVE_SCRATCH(e, g = carve_drain_gather(qi, CW, nb, nblk)); }
+    ks::DrainBufs& d = g.d;
+    HIPCHK(e, hipMemcpyAsync((void*)d.cordon, h_cordon.data(), sizeof(uint32_t) * CW, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, ks::launch_drain_count(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p, d,
+                                     e->st));
+    long long total = 0;
+    HIPCHK(e, hipMemcpyAsync(&total, d.total, sizeof(total), hipMemcpyDeviceToHost, e->st));  // 8 bytes first
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (total < 0 || total > nb * kUBlk) return fail(e, KS_EDEVICE, "drain: the gather counted %lld pods", total);
+    const int64_t n_ev = total;
+    *n_out = n_ev;
+    if (n_ev > cap || n_ev > KS_DRAIN_MAX_PODS)
+        return fail(e, KS_ERANGE, "drain: %lld evicted pods, room for %lld (at most %d per call)", (long long)n_ev,
+                    (long long)std::min<int64_t>(cap, KS_DRAIN_MAX_PODS), KS_DRAIN_MAX_PODS);
+    // ---- the rest of the scratch, sized from the total ----
+    DrainScratch s;
+    CARVE_SCRATCH(e, s = carve_drain(qs, n, np, nblk, n_ev, &d));
+    ks::PlaceBufs b = s.b;
+    b.cnt = g.cnt;
+    if (ks_status r = rebuild_state(e, nb, q_hi, t, kDeviceUnits, 1, np, (unsigned long long*)b.state); r != KS_OK) return r;
+    HIPCHK(e, ks::launch_drain_clear(d.cordon, (int32_t)n, b.state, np, e->st));
+    std::vector<ks::Eviction> h_ev(n_ev);
+    if (n_ev) {
+        HIPCHK(e, ks::launch_drain_fill(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
+                                        e->pods.p, d, e->st));
+        std::vector<ks::PodRec> recs(n_ev);
+        HIPCHK(e, hipMemcpyAsync(recs.data(), d.ev_rec, sizeof(ks::PodRec) * n_ev, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        std::vector<unsigned long long> h_up;
+        std::vector<int32_t> so(KS_PLACE_MAX_PODS);
+        ks::PodRec seg_shapes[KS_PLACE_MAX_SHAPES];
+        for (int64_t start = 0; start < n_ev;) {
+            int32_t ns = 0;
+            const int64_t end = ks::drain_segment(recs.data(), n_ev, start, seg_shapes, &ns, so.data());
+            const int32_t k = (int32_t)(end - start);
+            if (k < 1 || ns < 1) return fail(e, KS_EDEVICE, "drain: empty segment at evicted pod %lld", (long long)start);
+            if (ks_status r = upload_shapes(e, b, h_up, seg_shapes, ns, so.data(), k); r != KS_OK) return r;
+            b.out = s.b.out + start;
+            const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n, k, ns, (int32_t)nblk};
+            if (ks_status r = place_rounds(e, pc, b, so.data(), d.cordon, "drain: the round from evicted pod", start, &info[0]);
+                r != KS_OK)
+                return r;
+            info[4]++;
+            start = end;
+        }
+        HIPCHK(e, ks::launch_drain_pack(d.ev_pod, d.ev_from, s.b.out, n_ev, s.evict, e->st));
+        HIPCHK(e, hipMemcpyAsync(h_ev.data(), s.evict, sizeof(ks::Eviction) * n_ev, hipMemcpyDeviceToHost, e->st));
+    }
+    if (after_out) {
+        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, milli_scale(e), s.after, e->st));
+        HIPCHK(e, hipMemcpyAsync(after_out, s.after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    std::vector<uint32_t> seen(CW, 0u);
+    int64_t busy = 0;
+    for (int64_t i = 0; i < n_ev; i++) {
+        const ks::Eviction& v = h_ev[i];
+        info[v.status == KS_POD_OK ? 1 : v.status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
+        if ((uint32_t)v.from < (uint32_t)n && !(seen[v.from >> 5] >> (v.from & 31) & 1u)) {
+            seen[v.from >> 5] |= 1u << (v.from & 31);
+            busy++;
+        }
+    }
+    info[5] = n_drain - busy;
+    if (n_ev) std::memcpy(out, h_ev.data(), sizeof(ks_eviction) * n_ev);
+    if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
+    return KS_OK;
+}
+
+// ---- name-keyed lookups --------------------------------------------------------------------------
+
+uint64_t ks_node_mix(int64_t node) {
+    uint64_t z = (uint64_t)(node + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// Name-keyed index: every pod bound per node in FIFO order, extended over the binds
+// [idx_upto, done) on each query; a key's stored pod is the last one bound there (Store
+// replaces, kubesim/node/node.go:58).
+static void index_binds(ks_engine* e) {
+    if ((int64_t)e->node_pods.size() < e->n) e->node_pods.resize(e->n);
+    for (int64_t q = e->idx_upto; q < e->done; q++) {
+        const int32_t nd = e->h_node[q];
+        if (nd < 0) continue;  // the pod an aborted run stopped at is never stored
+        e->node_pods[nd].push_back(q);
+    }
+    e->idx_upto = e->done;
+}
+
+ks_status ks_pod_lookup(ks_engine* e, int32_t node, int64_t key_id, int64_t* pod_out) {
+    if (!e || !pod_out) return KS_EINVAL;
+    *pod_out = -1;
+    if (node < 0 || node >= e->n) return fail(e, KS_EINVAL, "node %d out of range", node);
+    index_binds(e);
+    const std::vector<int64_t>& v = e->node_pods[node];
+    for (auto it = v.rbegin(); it != v.rend(); ++it)  // the last Store under the key wins
+        if (e->h_key[*it] == key_id) {
+            *pod_out = *it;
+            return KS_OK;
+        }
+    return fail(e, KS_ENOTFOUND, "pod with key %lld not found on node %d", (long long)key_id, node);
+}
+
+ks_status ks_node_pods(ks_engine* e, int32_t node, int64_t* pods_out, int64_t cap, int64_t* n_out) {
+    if (!e || !n_out || cap < 0 || (cap > 0 && !pods_out)) return KS_EINVAL;
+    *n_out = 0;
+    if (node < 0 || node >= e->n) return fail(e, KS_EINVAL, "node %d out of range", node);
+    index_binds(e);
+    const std::vector<int64_t>& v = e->node_pods[node];
+    // one pod per key: the last one bound here (a pod is listed iff no later pod on this node
+    // has its key)
+    std::unordered_map<int64_t, int64_t> last;
+    last.reserve(v.size());
+    for (int64_t q : v) last[e->h_key[q]] = q;
+    int64_t k = 0;
+    for (int64_t q : v)
+        if (last[e->h_key[q]] == q) {
+            if (k < cap) pods_out[k] = q;
+            k++;
+        }
+    *n_out = k;
+    return KS_OK;
+}
+
+ks_status ks_pod_status(ks_engine* e, int64_t pod_lo, int64_t n, ks_pod_info* out) {
+    if (!e || (n > 0 && !out) || pod_lo < 0 || n < 0 || pod_lo + n > e->P) return KS_EINVAL;
+    if (n == 0) return KS_OK;
+    const int64_t hi = std::min(pod_lo + n, e->done), nb = std::max<int64_t>(hi - pod_lo, 0);
+    std::vector<int32_t> node(nb), status(nb);
+    if (nb) {
+        HIPCHK(e, hipSetDevice(e->device));
+        HIPCHK(e, stage_flush(e));
+        HIPCHK(e, hipMemcpyAsync(node.data(), e->b_node.p + pod_lo, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipMemcpyAsync(status.data(), e->b_status.p + pod_lo, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipStreamSynchronize(e->st));
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t q = pod_lo + i;
+        ks_pod_info& o = out[i];
+        o.total_seconds = e->h_total_sec[q];
+        const bool bound = i < nb && node[i] >= 0;
+        o.node = bound ? node[i] : -1;
+        o.start_tick = bound ? e->h_bind_tick[q] : -1;
+        if (!bound) o.phase = KS_PHASE_PENDING;
+        else if (status[i] != KS_POD_OK) o.phase = KS_PHASE_FAILED;  // CapacityExceeded
+        else {
+            // IsRunning (kubesim/pod/pod.go:67-69): passed = (t - t0) * tick < Σ phase seconds
+            const int64_t dt = e->tick - e->h_bind_tick[q];
+            o.phase = (dt >= 0 && dt < e->h_dur[q]) ? KS_PHASE_RUNNING : KS_PHASE_SUCCEEDED;
+        }
+    }
+    return KS_OK;
+}
+
+}  // extern "C"

@@ -45,7 +45,7 @@ Case make_case(int32_t n, const int64_t* alloc_dev, const int64_t* scale, const 
     for (int32_t j = 0; j < n_shapes; j++) {
         ks::PodRec p{};
         for (int c = 0; c < 3; c++)
-            if (keymask[j] >> c & 1) p.req[c] = req[j * 3 + c];  // unmasked keys are ignored (ks_engine.cpp head_shapes)
+            if (keymask[j] >> c & 1) p.req[c] = req[j * 3 + c];  // unmasked keys are ignored (ks_queries.cpp head_shapes)
         p.tol = tol[j]; p.sel = sel[j]; p.keymask = keymask[j];
         s.shapes.push_back(p);
     }

@@ -1,4 +1,4 @@
-"""Past-tick queries past a super block of the run-interval index (ks_engine.cpp usage_blocks): a
+"""Past-tick queries past a super block of the run-interval index (ks_queries.cpp usage_blocks): a
 super block is 64 blocks of 256 pods, dropped whole from a query over ticks >= t_lo when its latest
 run end is <= t_lo.
 
