@@ -547,6 +547,68 @@ func (e *Engine) DrainAt(t int64, nodes []int32, after bool) (*Evictions, error)
 	return r, status(e, rc)
 }
 
+// RemovableInfo is the words of Removals.Info (include/ks_engine.h, KS_REMOVABLE_INFO).
+const RemovableInfo = 6
+
+// Removal is one candidate's summary (ks_removal, 32 bytes): the pods running on it at t, the
+// statuses of their re-placements with the candidate alone out of k.nodes, Removable = 1 iff every
+// one was re-bound Ok (also when none runs there), and the index of its first row in Removals.Rows.
+type Removal struct {
+	Node, Evicted              int32
+	Ok, OverCapacity, NotFound int32
+	Removable                  int32
+	FirstRow                   int64
+}
+
+// Removals is the result of RemovableAt: one Removal per candidate in the caller's order, Rows (when
+// asked for) the candidates' Eviction rows concatenated in that order, FIFO within a candidate, and
+// Info = segments, candidates resolved by the batched kernel, candidates answered through the
+// single-drain path, candidates with no running pod, removable candidates, evicted pods.
+type Removals struct {
+	Nodes []Removal
+	Rows  []Eviction
+	Info  [RemovableInfo]int64
+}
+
+// RemovableAt says which of `nodes` could each be taken out on its own at tick t <= Tick(): for
+// candidate c the answer of DrainAt(t, {c}) (kubesim/kubesim.go:168-206 range over k.nodes without
+// c; its running pods go in FIFO order through scheduleOne, kubesim.go:143-225) — candidates are
+// independent (ks_removable_at).  nodes are distinct indices in [0, Nodes()).  No engine state
+// changes.  With rows it sizes the row buffer itself; more than DrainMaxPods evicted pods in all
+// are ErrOutOfDomain.
+func (e *Engine) RemovableAt(t int64, nodes []int32, rows bool) (*Removals, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	if len(nodes) == 0 && e.n > 0 {
+		return nil, strongerrors.InvalidArgument(errors.New("removable: no nodes given"))
+	}
+	nd := nodes
+	if len(nd) == 0 {
+		nd = make([]int32, 1) // n = 0: the pointer must not be NULL, the count is 0
+	}
+	r := &Removals{Nodes: make([]Removal, len(nodes)+1)}
+	out := (*C.ks_removal)(unsafe.Pointer(&r.Nodes[0]))
+	info := (*C.int64_t)(unsafe.Pointer(&r.Info[0]))
+	m := C.int32_t(len(nodes))
+	var k C.int64_t
+	var rc C.ks_status
+	if !rows {
+		rc = C.ks_removable_at(e.h, C.int64_t(t), m, i32p(nd), out, nil, 0, &k, info)
+	} else {
+		// a one-row buffer first: KS_ERANGE comes back with the count as soon as the gather has it
+		r.Rows = make([]Eviction, 1)
+		rc = C.ks_removable_at(e.h, C.int64_t(t), m, i32p(nd), out, (*C.ks_eviction)(unsafe.Pointer(&r.Rows[0])), 1, &k, info)
+		if rc == C.KS_ERANGE && k > 1 && k <= DrainMaxPods {
+			r.Rows = make([]Eviction, int(k))
+			rc = C.ks_removable_at(e.h, C.int64_t(t), m, i32p(nd), out, (*C.ks_eviction)(unsafe.Pointer(&r.Rows[0])), k, &k, info)
+		}
+		if rc == C.KS_OK {
+			r.Rows = r.Rows[:int(k)]
+		}
+	}
+	r.Nodes = r.Nodes[:len(nodes)]
+	return r, status(e, rc)
+}
+
 // Nodes is the node count of LoadNodes.
 func (e *Engine) Nodes() int { return e.n }
 

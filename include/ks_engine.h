@@ -31,6 +31,8 @@
  *                                 private copy of a past tick's state: where they would be bound
  *   ks_drain_at ................. the same for the pods running on a node set that leaves k.nodes
  *                                 (kubesim/kubesim.go:168-206 range over it): where they would go
+ *   ks_removable_at ............. ks_drain_at's answer for each of m candidate nodes on its own:
+ *                                 which of them could be taken out
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
  *   ks_pod_lookup / ks_node_pods  Node.GetPod / GetPodStatus / GetPodList (kubesim/node/node.go:62-93)
  *   ks_group_* .................. one KubeSim.Run per what-if scenario, stepped together
@@ -436,6 +438,43 @@ typedef struct {
 ks_status ks_drain_at(ks_engine* eng, int64_t t, int32_t n_drain, const int32_t* nodes /* [n_drain] */,
                       ks_eviction* out /* [cap] or NULL */, int64_t cap, int64_t* n_out,
                       int64_t* after_out /* [n][4] or NULL */, int64_t* info_out /* [KS_DRAIN_INFO] or NULL */);
+
+/* Removal scan: which of m candidate nodes could each be taken out on its own, at any past tick ("at
+ * tick t" as above).  No engine state changes.
+ *
+ * nodes[m] are distinct node indices in [0, n), 1 <= m <= n (with n = 0: m = 0).  For candidate c the
+ * answer is by definition that of ks_drain_at(t, 1, {c}): c alone leaves k.nodes
+ * (kubesim/kubesim.go:168-206 range over k.nodes), the pods running on it at t (Pod.IsRunning,
+ * kubesim/pod/pod.go:67-69) are evicted and handed in FIFO order to scheduleOne
+ * (kubesim/kubesim.go:143-225, kubesim/node/node.go:36-60) on a private copy of ks_requested_at(t)
+ * with c's row emptied; each pod's node / status / score / candidates are ks_drain_at's.  Candidates
+ * are independent: none sees another's evictions or placements.
+ *
+ * out[j] answers nodes[j], in the caller's order: the pods running on it, the statuses of their
+ * re-placements, removable = 1 iff every one of them was re-bound KS_POD_OK (also when none runs
+ * there), and first_row, the index of its first row — filled whether or not rows are asked for.
+ * rows_out (may be NULL with cap = 0: summaries only): the candidates' ks_eviction rows concatenated
+ * in the caller's order, FIFO within a candidate.  *n_rows = the total of evicted pods, always.  If it
+ * exceeds KS_DRAIN_MAX_PODS, or rows_out is given and it exceeds cap: KS_ERANGE and nothing else is
+ * written.  info_out (may be NULL): {segments (the shared lists take KS_PLACE_MAX_SHAPES distinct
+ * shapes at a time), candidates resolved by the batched kernel, candidates answered through the
+ * single-drain path (more pods than one set of lists decides: KS_PLACE_L - 1), candidates with no
+ * running pod, removable candidates, evicted pods}.
+ * KS_EINVAL: a NULL engine, nodes, out or n_rows (before the handle is read); rows_out NULL with
+ * cap > 0; cap < 0; a node out of range or listed twice; m out of range; t out of range; no nodes
+ * loaded.  It answers after an aborted run, on sharded engines and on scenario-group members, like
+ * ks_drain_at. */
+#define KS_REMOVABLE_INFO 6
+typedef struct {
+    int32_t node;          /* the candidate */
+    int32_t evicted;       /* pods running on it at t */
+    int32_t ok, over_capacity, not_found;   /* statuses of their re-placements */
+    int32_t removable;     /* 1 iff ok == evicted (also when evicted == 0) */
+    int64_t first_row;     /* index of its first row in rows_out (rows of a candidate are contiguous) */
+} ks_removal;              /* 32 bytes */
+ks_status ks_removable_at(ks_engine* eng, int64_t t, int32_t m, const int32_t* nodes /* [m] */,
+                          ks_removal* out /* [m] */, ks_eviction* rows_out /* [cap] or NULL */,
+                          int64_t cap, int64_t* n_rows, int64_t* info_out /* [KS_REMOVABLE_INFO] or NULL */);
 
 /* Name-keyed queries over the binds made so far (Node.GetPod / GetPodStatus / GetPodList,
  * kubesim/node/node.go:62-93).  ks_pod_lookup: the FIFO index of the pod stored on `node` under

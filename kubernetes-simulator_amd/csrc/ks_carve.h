@@ -3,7 +3,8 @@
 // A layout is written once, as a sequence of Carve::take() calls, and run twice: with a null base
 // the cursor only counts and `at` is the size to reserve; with the real base the same calls give
 // the pointers.  The reserved size and the ranges therefore cannot disagree.  The layouts of the
-// placement and drain previews live here too, so a stand-alone host program can check them.
+// placement and drain previews and of the removal scan live here too, so a stand-alone host program
+// can check them.
 #pragma once
 #include <cstdint>
 
@@ -91,6 +92,40 @@ inline DrainScratch carve_drain(Carve& qs, int64_t n, int64_t np, int64_t nblk, 
     d->cap = n_ev;
     s.evict = qs.take<ks::Eviction>(n_ev);
     s.after = qs.take<long long>(4 * n);
+    return s;
+}
+
+// ks_removable_at, once n_ev is known (the gather's int32 scratch is carve_drain_gather's): the
+// lists' buffers on the base state (b.shape_of: a row's shape among its segment's, every row; no
+// placements: the resolver writes rows), the gathered rows (into d), and the resolver's buffers for
+// at most min(m, n_ev) batched candidates in at most removable_seg_cap(n_ev) segments
+struct RemovableScratch {
+    ks::PlaceBufs b;
+    ks::RemovableBufs r;
+    int64_t cand_cap, seg_cap;
+};
+// A segment closes only before a candidate that would bring its 65th shape; that candidate has at
+// most kRemovableMaxPods shapes, so a closed segment holds more than kPlaceMaxShapes -
+// kRemovableMaxPods shapes, each on a row of its own.
+constexpr int64_t removable_seg_cap(int64_t n_ev) {
+    return n_ev / (ks::kPlaceMaxShapes - ks::kRemovableMaxPods + 1) + 1;
+}
+inline RemovableScratch carve_removable(Carve& qs, int64_t np, int64_t nblk, int64_t n_ev, int64_t m, ks::DrainBufs* d) {
+    RemovableScratch s{};
+    s.cand_cap = m < n_ev ? m : n_ev;
+    s.seg_cap = removable_seg_cap(n_ev);
+    s.b = carve_place(qs, np, nblk, n_ev, 0);
+    d->ev_pod = qs.take<long long>(n_ev);
+    d->ev_from = qs.take<int32_t>(n_ev);
+    d->ev_rec = qs.take<ks::PodRec>(n_ev, 2);
+    d->cap = n_ev;
+    s.r.seg_shapes = qs.take<ks::PodRec>(s.seg_cap * ks::kPlaceMaxShapes, 2);
+    s.r.shape_of = s.b.shape_of;
+    s.r.ev_pod = d->ev_pod;
+    s.r.perm = qs.take<int32_t>(n_ev);
+    s.r.cands = qs.take<ks::RemovalCand>(s.cand_cap);
+    s.r.rows = qs.take<ks::Eviction>(n_ev);
+    s.r.out = qs.take<ks::Removal>(s.cand_cap);
     return s;
 }
 

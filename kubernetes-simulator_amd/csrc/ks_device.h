@@ -1218,6 +1218,17 @@ __host__ __device__ __forceinline__ void place_scale_alloc(NodeV& v, const QScal
     v.ag = v.ag < 0 ? -1 : v.ag * sc.f[2];
 }
 
+// node nd in the call's units (sc per device unit): constants from the cluster, state from the scratch
+__device__ __forceinline__ NodeV place_load(const NodeSoA& s, const int64_t* state, int64_t n_pad, const QScale& sc,
+                                            int64_t nd) {
+    NodeV v;
+    v.ac = s.ac[nd]; v.am = s.am[nd]; v.ag = s.ag[nd]; v.ap = s.ap[nd];
+    v.taint = s.taint[nd]; v.label = s.label[nd];
+    place_scale_alloc(v, sc);
+    v.rc = state[nd]; v.rm = state[n_pad + nd]; v.rg = state[2 * n_pad + nd]; v.nr = state[3 * n_pad + nd];
+    return v;
+}
+
 // Whether every masked request of the shapes is a whole multiple of the engine's unit sc.  Then the
 // call runs in device units instead (scale 1, requests divided by sc, `after` multiplied back):
 // every fit / LeastRequested / BalancedAllocation result is unit-free, so the placements are the
@@ -1334,6 +1345,9 @@ struct PlaceBufs {
 // above holds verbatim over the non-cordoned nodes.
 hipError_t launch_place_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, int32_t first, uint64_t active,
                               hipStream_t st, const uint32_t* cordon = nullptr);
+// the lists alone (ks_removable_at): scan + merge for the shapes in `active` on the state as it is,
+// without a cordon — b.top and b.ccount of pc.n_shapes shapes; no resolver, nothing is committed
+hipError_t launch_place_lists(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, uint64_t active, hipStream_t st);
 // after[n][4] from state [4][n_pad], the three quantities times sc
 hipError_t launch_place_after(const int64_t* state, int64_t n_pad, int32_t n_nodes, const QScale& sc, long long* after,
                               hipStream_t st);
@@ -1442,5 +1456,127 @@ hipError_t launch_drain_clear(const uint32_t* cordon, int32_t n_nodes, int64_t* 
 // out[i] = {ev_pod[i], ev_from[i], placed[i]} for i < n_ev
 hipError_t launch_drain_pack(const long long* ev_pod, const int32_t* ev_from, const Placement* placed, int64_t n_ev,
                              Eviction* out, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
+// Removal scan (ks_removable_at, ks_removable.hip): for each of m candidate nodes on its own, the
+// answer of the drain preview above with that node alone as the set.  Candidates are independent:
+// every one starts from the same state at t, only the cordoned node differs.
+//
+// Exactness of one shared scan.  The snapshot top-L lists and the candidate counts of a segment's
+// shapes are built once, on the base state at t with no cordon (launch_place_lists).  For
+// candidate c the resolver
+//   - starts its private flag words with every list entry whose node is c flagged, and never puts c
+//     in its changed set;
+//   - starts its running candidate counts at the base count minus place_is_cand(shape, c's base
+//     record).
+// Read "changed or removed" for "changed" in the argument above place_decide, over the nodes other
+// than c: a flagged entry is a node that is changed or removed; an unflagged entry is a node other
+// than c that no pod of this candidate was placed on, so it still has its snapshot key; those above
+// the first unflagged entry S are all changed or removed, those below it or outside the list are
+// smaller; a complete list (fewer than L entries) still means every node outside it — c included or
+// not — has key 0; with all L entries flagged and D above the list's last key every unchanged node
+// other than c lies outside the list, so below that key.  The three cases of place_decide hold
+// verbatim.  c is never S (its entries are flagged from the start), so never a winner, never in the
+// changed set and never in D; its pods' own requests stay in its base record, which nothing reads
+// but the count correction.  That c's row is not emptied (ks_drain_at zeroes it) changes nothing: a
+// cordoned node's state is never read there either.
+//
+// Progress.  A node is flagged when a pod is placed on it from the list, at most one per pod, so
+// pod i (1-based) of a candidate finds at most (i - 1) + 1 flagged entries in its list.  kPlaceStop
+// needs all L entries flagged, so a candidate with at most kRemovableMaxPods = L - 1 evicted pods is
+// decided completely from one set of lists, with no rescan and nothing committed.  A candidate with
+// more pods is answered through ks_drain_at's own path (removable_route): the same result by
+// definition.
+//
+// Segments.  A resolver launch shares the lists of at most kPlaceMaxShapes shapes, so the host walks
+// the batched candidates in the caller's order and closes a segment before the candidate that would
+// bring its (kPlaceMaxShapes + 1)-th distinct shape (removable_segment); a candidate has at most
+// L - 1 shapes, so it always fits an empty segment.  Segments are independent: all start from the
+// base state.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRemovableMaxPods = kPlaceL - 1;  // evicted pods of a candidate the batched resolver decides
+static_assert(kRemovableMaxPods < kWave && kRemovableMaxPods < kPlaceMaxShapes, "a lane per changed node; a candidate fits a segment");
+enum : int { kRemovableEmpty = 0, kRemovableBatched = 1, kRemovableDrain = 2 };
+
+struct Removal {  // = ks_removal
+    int32_t node, evicted, ok, over_capacity, not_found, removable;
+    int64_t first_row;
+};
+static_assert(sizeof(Removal) == 32, "ks_removal layout");
+
+// a batched candidate: its node, its pods' rows [first, first + count) in the caller-ordered rows
+struct RemovalCand {
+    int64_t first;
+    int32_t node, count;
+};
+static_assert(sizeof(RemovalCand) == 16, "RemovalCand layout");
+
+// who answers a candidate with `pods` running pods
+__host__ __device__ __forceinline__ int removable_route(int64_t pods) {
+    return pods <= 0 ? kRemovableEmpty : pods <= kRemovableMaxPods ? kRemovableBatched : kRemovableDrain;
+}
+
+// bit e: entry e of a snapshot list is a key of `node`
+template <int L = kPlaceL>
+__host__ __device__ __forceinline__ uint32_t removable_entries_on(const uint64_t* list, uint32_t node) {
+    uint32_t bits = 0u;
+    for (int e = 0; e < L; ++e)
+        if (list[e] && place_key_node(list[e]) == node) bits |= 1u << e;
+    return bits;
+}
+
+// The segment that starts at batched candidate `start` of cands[n_cand] (rows of recs, each
+// candidate's contiguous): it closes before the candidate that would bring its (kPlaceMaxShapes +
+// 1)-th distinct shape.  Returns its end (exclusive; > start when start < n_cand: a candidate has at
+// most kRemovableMaxPods shapes), its distinct shapes in shapes[0, *n_shapes) in order of first
+// appearance (masked requests, flags 0) and shape_of[row] for its candidates' rows.
+inline int64_t removable_segment(const PodRec* recs, const RemovalCand* cands, int64_t n_cand, int64_t start,
+                                 PodRec* shapes, int32_t* n_shapes, int32_t* shape_of) {
+    int32_t ns = 0;
+    int64_t a = start;
+    for (; a < n_cand; ++a) {
+        const int32_t before = ns;
+        bool fits_in = true;
+        for (int64_t row = cands[a].first; row < cands[a].first + cands[a].count; ++row) {
+            int32_t j = 0;
+            while (j < ns && !drain_same_shape(shapes[j], recs[row])) ++j;
+            if (j == ns) {
+                if (ns == kPlaceMaxShapes) {
+                    fits_in = false;
+                    break;
+                }
+                PodRec r{};
+                for (int c = 0; c < 3; ++c) r.req[c] = (recs[row].keymask >> c & 1) ? recs[row].req[c] : 0;
+                r.tol = recs[row].tol; r.sel = recs[row].sel; r.keymask = recs[row].keymask;
+                shapes[ns++] = r;
+            }
+            shape_of[row] = j;
+        }
+        if (!fits_in) {
+            ns = before;  // (the next segment numbers this candidate's rows again)
+            break;
+        }
+    }
+    *n_shapes = ns;
+    return a;
+}
+
+// Scratch of the resolver (device): cands [batched candidates], in the caller's order; seg_shapes
+// [segments][kPlaceMaxShapes]; shape_of [rows] (a row's shape among its segment's); ev_pod [rows] in
+// gather order and perm [rows], the gather index of each caller-ordered row; rows [rows] and out
+// [batched candidates], the results.
+struct RemovableBufs {
+    const RemovalCand* cands;
+    const PodRec* seg_shapes;
+    const int32_t* shape_of;
+    const long long* ev_pod;
+    const int32_t* perm;
+    Eviction* rows;
+    Removal* out;
+};
+// one segment: candidates [cand0, cand0 + n_cand) against the lists b.top / b.ccount of the
+// pc.n_shapes shapes at `shapes` (after launch_place_lists on the same shapes)
+hipError_t launch_removable_resolve(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, const RemovableBufs& r,
+                                    const PodRec* shapes, int64_t cand0, int64_t n_cand, hipStream_t st);
 
 }  // namespace ks

@@ -31,17 +31,6 @@ static_assert(kPBlk == 4 * kWave, "the extraction reads four keys per lane");
 
 __device__ __forceinline__ bool shape_active(uint64_t active, int sh) { return (active >> sh) & 1ull; }
 
-// node nd in the call's units (sc per device unit): constants from the cluster, state from the scratch
-__device__ __forceinline__ NodeV place_load(const NodeSoA& s, const int64_t* state, int64_t n_pad, const QScale& sc,
-                                            int64_t nd) {
-    NodeV v;
-    v.ac = s.ac[nd]; v.am = s.am[nd]; v.ag = s.ag[nd]; v.ap = s.ap[nd];
-    v.taint = s.taint[nd]; v.label = s.label[nd];
-    place_scale_alloc(v, sc);
-    v.rc = state[nd]; v.rm = state[n_pad + nd]; v.rg = state[2 * n_pad + nd]; v.nr = state[3 * n_pad + nd];
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Scan: a node's ten words are loaded once; the shape records are workgroup-uniform (scalar loads).
 // Per pass of kPChunk shapes every thread writes its key into tab[shape][thread]; then each wave
@@ -305,6 +294,17 @@ hipError_t launch_place_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceB
                        (const int32_t*)b.cnt, pc.nblk, active, b.top, b.ccount);
     hipLaunchKernelGGL(place_resolve_kernel, dim3(1), dim3(kPRes), 0, st, s, b.state, b.n_pad, pc, b.shapes, b.shape_of,
                        first, active, (const uint64_t*)b.top, (const long long*)b.ccount, b.out, b.rb);
+    return hipGetLastError();
+}
+
+hipError_t launch_place_lists(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, uint64_t active, hipStream_t st) {
+    if (pc.n_nodes <= 0 || pc.n_shapes <= 0 || pc.n_shapes > kPlaceMaxShapes ||
+        pc.nblk != (pc.n_nodes + kPBlk - 1) / kPBlk)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(place_scan_kernel<false>, dim3((unsigned)pc.nblk), dim3(kPBlk), 0, st, s, (const int64_t*)b.state,
+                       b.n_pad, pc, b.shapes, active, b.lists, b.cnt, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(place_merge_kernel, dim3((unsigned)pc.n_shapes), dim3(kWave), 0, st, (const uint64_t*)b.lists,
+                       (const int32_t*)b.cnt, pc.nblk, active, b.top, b.ccount);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // ks_queries.cpp — the entry points of include/ks_engine.h that answer about a run after the fact:
 // filter / score of a pod, usage, the past-tick state queries, headroom, the placement and drain
-// previews and the name-keyed lookups.  They read the engine (ks_host.h) and write nothing a later
+// previews, the removal scan and the name-keyed lookups.  They read the engine (ks_host.h) and write nothing a later
 // ks_step reads; their device scratch is the grow-only d_qs / d_qi, carved by ks_carve.h.
 #include <cstring>
 
@@ -526,21 +526,72 @@ static_assert(KS_DRAIN_MAX_PODS == ks::kDrainMaxPods && KS_DRAIN_INFO == 6 && si
               offsetof(ks_eviction, candidates) == offsetof(ks::Eviction, candidates) && kUBlk == ks::kDrainBlk,
               "ks_drain_at constants and record");
 
+// A query's node set as a bitmap: nodes[n_set] distinct indices in [0, n), n_set in [1, n] (n = 0: 0)
+static ks_status node_set(ks_engine* e, const char* what, int32_t n_set, const int32_t* nodes, std::vector<uint32_t>* bits) {
+    const int64_t n = e->n;
+    if (n_set < (n ? 1 : 0) || n_set > n)
+        return fail(e, KS_EINVAL, "%s: %d nodes outside [%d, %lld]", what, (int)n_set, n ? 1 : 0, (long long)n);
+    bits->assign((n + 31) / 32, 0u);
+    for (int32_t j = 0; j < n_set; j++) {
+        const int32_t nd = nodes[j];
+        if (nd < 0 || nd >= n) return fail(e, KS_EINVAL, "%s: node %d outside [0, %lld)", what, (int)nd, (long long)n);
+        if ((*bits)[nd >> 5] >> (nd & 31) & 1u) return fail(e, KS_EINVAL, "%s: node %d is listed twice", what, (int)nd);
+        (*bits)[nd >> 5] |= 1u << (nd & 31);
+    }
+    return KS_OK;
+}
+
+// The gather's count: the candidate blocks at t, the int32 scratch (carve_drain_gather), the node set
+// uploaded as the cordon, and n_ev, the pods running at t on the set (8 bytes read back first)
+struct DrainCount {
+    int64_t q_hi, nb, n_ev;
+    DrainGather g;
+};
+static ks_status drain_count(ks_engine* e, const char* what, int64_t t, const std::vector<uint32_t>& h_cordon,
+                             DrainCount* c) {
+    const int64_t n = e->n, nblk = (n + 255) / 256, CW = (int64_t)h_cordon.size();
+    c->q_hi = bound_by(e, t);
+    c->nb = 0;
+    if (ks_status r = query_blocks(e, t, c->q_hi, &c->nb); r != KS_OK) return r;
+    if (c->nb * kUBlk > INT32_MAX)
+        return fail(e, KS_EINVAL, "%s: tick %lld holds too many candidate pods", what, (long long)t);
+    { CARVE_SCRATCH(e, c->g = carve_drain_gather(qi, CW, c->nb, nblk)); }
+    const ks::DrainBufs& d = c->g.d;
+    HIPCHK(e, hipMemcpyAsync((void*)d.cordon, h_cordon.data(), sizeof(uint32_t) * CW, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, ks::launch_drain_count(e->d_blk.p, c->nb, c->q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p,
+                                     e->dur.p, d, e->st));
+    long long total = 0;
+    HIPCHK(e, hipMemcpyAsync(&total, d.total, sizeof(total), hipMemcpyDeviceToHost, e->st));  // 8 bytes first
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (total < 0 || total > c->nb * kUBlk) return fail(e, KS_EDEVICE, "%s: the gather counted %lld pods", what, total);
+    c->n_ev = total;
+    return KS_OK;
+}
+
+// ... and its rows once the scratch is carved (d: the gather's buffers with ev_* set): the n_ev
+// pods' records, and the nodes they run on when `from` is asked for, read back in FIFO order
+static ks_status drain_rows(ks_engine* e, int64_t t, const DrainCount& c, const ks::DrainBufs& d,
+                            std::vector<ks::PodRec>* recs, std::vector<int32_t>* from) {
+    HIPCHK(e, ks::launch_drain_fill(e->d_blk.p, c.nb, c.q_hi, t, (int32_t)e->n, e->b_node.p, e->b_status.p, e->t0.p,
+                                    e->dur.p, e->pods.p, d, e->st));
+    recs->resize(c.n_ev);
+    HIPCHK(e, hipMemcpyAsync(recs->data(), d.ev_rec, sizeof(ks::PodRec) * c.n_ev, hipMemcpyDeviceToHost, e->st));
+    if (from) {
+        from->resize(c.n_ev);
+        HIPCHK(e, hipMemcpyAsync(from->data(), d.ev_from, sizeof(int32_t) * c.n_ev, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KS_OK;
+}
+
 ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* nodes, ks_eviction* out, int64_t cap,
                       int64_t* n_out, int64_t* after_out, int64_t* info_out) {
     if (!e || !nodes || !n_out || cap < 0 || (cap > 0 && !out)) return KS_EINVAL;
     if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
     const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
-    if (n_drain < (n ? 1 : 0) || n_drain > n)
-        return fail(e, KS_EINVAL, "drain: %d nodes outside [%d, %lld]", (int)n_drain, n ? 1 : 0, (long long)n);
-    const int64_t CW = (n + 31) / 32;
-    std::vector<uint32_t> h_cordon(CW, 0u);
-    for (int32_t j = 0; j < n_drain; j++) {
-        const int32_t nd = nodes[j];
-        if (nd < 0 || nd >= n) return fail(e, KS_EINVAL, "drain: node %d outside [0, %lld)", (int)nd, (long long)n);
-        if (h_cordon[nd >> 5] >> (nd & 31) & 1u) return fail(e, KS_EINVAL, "drain: node %d is listed twice", (int)nd);
-        h_cordon[nd >> 5] |= 1u << (nd & 31);
-    }
+    std::vector<uint32_t> h_cordon;
+    if (ks_status r = node_set(e, "drain", n_drain, nodes, &h_cordon); r != KS_OK) return r;
+    const int64_t CW = (int64_t)h_cordon.size();
     if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
     int64_t info[KS_DRAIN_INFO] = {0, 0, 0, 0, 0, 0};
     if (n == 0) {
@@ -548,22 +599,12 @@ ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* n
         if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
         return KS_OK;
     }
-    const int64_t q_hi = bound_by(e, t);
-    int64_t nb = 0;
-    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
-    if (nb * kUBlk > INT32_MAX) return fail(e, KS_EINVAL, "drain: tick %lld holds too many candidate pods", (long long)t);
     // ---- the gather's count ----
-    DrainGather g;
-    { CARVE_SCRATCH(e, g = carve_drain_gather(qi, CW, nb, nblk)); }
+    DrainCount gc;
+    if (ks_status r = drain_count(e, "drain", t, h_cordon, &gc); r != KS_OK) return r;
+    DrainGather& g = gc.g;
     ks::DrainBufs& d = g.d;
-    HIPCHK(e, hipMemcpyAsync((void*)d.cordon, h_cordon.data(), sizeof(uint32_t) * CW, hipMemcpyHostToDevice, e->st));
-    HIPCHK(e, ks::launch_drain_count(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p, d,
-                                     e->st));
-    long long total = 0;
-    HIPCHK(e, hipMemcpyAsync(&total, d.total, sizeof(total), hipMemcpyDeviceToHost, e->st));  // 8 bytes first
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    if (total < 0 || total > nb * kUBlk) return fail(e, KS_EDEVICE, "drain: the gather counted %lld pods", total);
-    const int64_t n_ev = total;
+    const int64_t n_ev = gc.n_ev, nb = gc.nb, q_hi = gc.q_hi;
     *n_out = n_ev;
     if (n_ev > cap || n_ev > KS_DRAIN_MAX_PODS)
         return fail(e, KS_ERANGE, "drain: %lld evicted pods, room for %lld (at most %d per call)", (long long)n_ev,
@@ -577,11 +618,8 @@ ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* n
     HIPCHK(e, ks::launch_drain_clear(d.cordon, (int32_t)n, b.state, np, e->st));
     std::vector<ks::Eviction> h_ev(n_ev);
     if (n_ev) {
-        HIPCHK(e, ks::launch_drain_fill(e->d_blk.p, nb, q_hi, t, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p, e->dur.p,
-                                        e->pods.p, d, e->st));
-        std::vector<ks::PodRec> recs(n_ev);
-        HIPCHK(e, hipMemcpyAsync(recs.data(), d.ev_rec, sizeof(ks::PodRec) * n_ev, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(e, hipStreamSynchronize(e->st));
+        std::vector<ks::PodRec> recs;
+        if (ks_status r = drain_rows(e, t, gc, d, &recs, nullptr); r != KS_OK) return r;
         std::vector<unsigned long long> h_up;
         std::vector<int32_t> so(KS_PLACE_MAX_PODS);
         ks::PodRec seg_shapes[KS_PLACE_MAX_SHAPES];
@@ -620,6 +658,158 @@ ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* n
     info[5] = n_drain - busy;
     if (n_ev) std::memcpy(out, h_ev.data(), sizeof(ks_eviction) * n_ev);
     if (info_out) std::copy(info, info + KS_DRAIN_INFO, info_out);
+    return KS_OK;
+}
+
+// ---- removal scan (ks_removable.hip) -------------------------------------------------------------
+// ks_drain_at's question for each of m candidate nodes on its own.  One gather with the candidates as
+// the node set; the host groups the rows by candidate (a stable counting sort on the position in
+// nodes[]: FIFO within a candidate) and routes each candidate (ks::removable_route): no pod, the
+// batched resolver (at most kRemovableMaxPods pods), or ks_drain_at itself.  The batched candidates
+// are walked in segments of at most KS_PLACE_MAX_SHAPES distinct shapes that close at candidate
+// boundaries (ks::removable_segment); every segment's scan, merge and resolver are queued back to
+// back on the base state and the stream is synchronised once.  The single-drain candidates follow:
+// they use the same scratch.
+static_assert(KS_REMOVABLE_INFO == 6 && sizeof(ks_removal) == sizeof(ks::Removal) &&
+              offsetof(ks_removal, node) == offsetof(ks::Removal, node) && offsetof(ks_removal, evicted) == offsetof(ks::Removal, evicted) &&
+              offsetof(ks_removal, ok) == offsetof(ks::Removal, ok) && offsetof(ks_removal, over_capacity) == offsetof(ks::Removal, over_capacity) &&
+              offsetof(ks_removal, not_found) == offsetof(ks::Removal, not_found) &&
+              offsetof(ks_removal, removable) == offsetof(ks::Removal, removable) &&
+              offsetof(ks_removal, first_row) == offsetof(ks::Removal, first_row),
+              "ks_removable_at constants and record");
+
+ks_status ks_removable_at(ks_engine* e, int64_t t, int32_t m, const int32_t* nodes, ks_removal* out, ks_eviction* rows_out,
+                          int64_t cap, int64_t* n_rows, int64_t* info_out) {
+    if (!e || !nodes || !out || !n_rows || cap < 0 || (cap > 0 && !rows_out)) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    std::vector<uint32_t> h_set;
+    if (ks_status r = node_set(e, "removable", m, nodes, &h_set); r != KS_OK) return r;
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    int64_t info[KS_REMOVABLE_INFO] = {0, 0, 0, 0, 0, 0};
+    if (n == 0) {
+        *n_rows = 0;
+        if (info_out) std::copy(info, info + KS_REMOVABLE_INFO, info_out);
+        return KS_OK;
+    }
+    // ---- one gather for every candidate ----
+    DrainCount gc;
+    if (ks_status r = drain_count(e, "removable", t, h_set, &gc); r != KS_OK) return r;
+    const int64_t n_ev = gc.n_ev;
+    *n_rows = n_ev;
+    if (n_ev > KS_DRAIN_MAX_PODS || (rows_out && n_ev > cap))
+        return fail(e, KS_ERANGE, "removable: %lld evicted pods, room for %lld (at most %d per call)", (long long)n_ev,
+                    (long long)(rows_out ? std::min<int64_t>(cap, KS_DRAIN_MAX_PODS) : (int64_t)KS_DRAIN_MAX_PODS),
+                    KS_DRAIN_MAX_PODS);
+    std::vector<ks::Removal> h_out(m);
+    std::vector<ks::Eviction> h_rows(n_ev);
+    std::vector<int32_t> slow;  // positions in nodes[] of the candidates ks_drain_at answers
+    for (int32_t j = 0; j < m; j++) h_out[j] = ks::Removal{nodes[j], 0, 0, 0, 0, 1, 0};
+    if (n_ev) {
+        ks::DrainBufs d = gc.g.d;
+        RemovableScratch s;
+        CARVE_SCRATCH(e, s = carve_removable(qs, np, nblk, n_ev, m, &d));
+        ks::PlaceBufs b = s.b;
+        b.cnt = gc.g.cnt;
+        if (ks_status r = rebuild_state(e, gc.nb, gc.q_hi, t, kDeviceUnits, 1, np, (unsigned long long*)b.state); r != KS_OK)
+            return r;
+        std::vector<ks::PodRec> fifo;
+        std::vector<int32_t> from;
+        if (ks_status r = drain_rows(e, t, gc, d, &fifo, &from); r != KS_OK) return r;
+        // ---- group by candidate: rows in the caller's order, FIFO within a candidate ----
+        std::vector<int32_t> pos(n, -1), perm(n_ev), fill(m, 0);
+        for (int32_t j = 0; j < m; j++) pos[nodes[j]] = j;
+        for (int64_t i = 0; i < n_ev; i++) {
+            if ((uint32_t)from[i] >= (uint32_t)n || pos[from[i]] < 0)
+                return fail(e, KS_EDEVICE, "removable: evicted pod %lld runs on node %d, no candidate", (long long)i, (int)from[i]);
+            h_out[pos[from[i]]].evicted++;
+        }
+        for (int32_t j = 1; j < m; j++) h_out[j].first_row = h_out[j - 1].first_row + h_out[j - 1].evicted;
+        std::vector<ks::PodRec> recs(n_ev);
+        for (int64_t i = 0; i < n_ev; i++) {
+            const int32_t j = pos[from[i]];
+            const int64_t row = h_out[j].first_row + fill[j]++;
+            perm[row] = (int32_t)i;
+            recs[row] = fifo[i];
+        }
+        std::vector<ks::RemovalCand> cands;
+        std::vector<int32_t> cand_pos;
+        for (int32_t j = 0; j < m; j++) {
+            const int route = ks::removable_route(h_out[j].evicted);
+            if (route == ks::kRemovableBatched) {
+                cands.push_back(ks::RemovalCand{h_out[j].first_row, nodes[j], h_out[j].evicted});
+                cand_pos.push_back(j);
+            } else if (route == ks::kRemovableDrain) {
+                slow.push_back(j);
+            }
+        }
+        const int64_t n_cand = (int64_t)cands.size();
+        if (n_cand) {
+            // ---- the segment walk, then every segment's kernels back to back ----
+            struct Seg { int64_t cand0, n_cand; int32_t ns; };
+            std::vector<Seg> segs;
+            std::vector<ks::PodRec> seg_shapes;
+            std::vector<int32_t> so(n_ev, 0);
+            for (int64_t start = 0; start < n_cand;) {
+                seg_shapes.resize((segs.size() + 1) * KS_PLACE_MAX_SHAPES, ks::PodRec{});
+                int32_t ns = 0;
+                const int64_t end = ks::removable_segment(recs.data(), cands.data(), n_cand, start,
+                                                          seg_shapes.data() + segs.size() * KS_PLACE_MAX_SHAPES, &ns, so.data());
+                if (end <= start || ns < 1 || (int64_t)segs.size() >= s.seg_cap)
+                    return fail(e, KS_EDEVICE, "removable: empty segment at candidate %lld", (long long)start);
+                segs.push_back(Seg{start, end - start, ns});
+                start = end;
+            }
+            HIPCHK(e, hipMemcpyAsync((void*)s.r.seg_shapes, seg_shapes.data(), sizeof(ks::PodRec) * seg_shapes.size(),
+                                     hipMemcpyHostToDevice, e->st));
+            HIPCHK(e, hipMemcpyAsync((void*)s.r.shape_of, so.data(), sizeof(int32_t) * n_ev, hipMemcpyHostToDevice, e->st));
+            HIPCHK(e, hipMemcpyAsync((void*)s.r.perm, perm.data(), sizeof(int32_t) * n_ev, hipMemcpyHostToDevice, e->st));
+            HIPCHK(e, hipMemcpyAsync((void*)s.r.cands, cands.data(), sizeof(ks::RemovalCand) * n_cand, hipMemcpyHostToDevice, e->st));
+            for (size_t g = 0; g < segs.size(); g++) {
+                const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n, 0, segs[g].ns, (int32_t)nblk};
+                b.shapes = s.r.seg_shapes + g * KS_PLACE_MAX_SHAPES;
+                const uint64_t active = segs[g].ns >= 64 ? ~0ull : (1ull << segs[g].ns) - 1ull;
+                HIPCHK(e, ks::launch_place_lists(e->s, pc, b, active, e->st));
+                HIPCHK(e, ks::launch_removable_resolve(e->s, pc, b, s.r, b.shapes, segs[g].cand0, segs[g].n_cand, e->st));
+            }
+            std::vector<ks::Removal> got(n_cand);
+            HIPCHK(e, hipMemcpyAsync(got.data(), s.r.out, sizeof(ks::Removal) * n_cand, hipMemcpyDeviceToHost, e->st));
+            if (rows_out)
+                HIPCHK(e, hipMemcpyAsync(h_rows.data(), s.r.rows, sizeof(ks::Eviction) * n_ev, hipMemcpyDeviceToHost, e->st));
+            HIPCHK(e, hipStreamSynchronize(e->st));
+            for (int64_t a = 0; a < n_cand; a++) {
+                const ks::Removal& v = got[a];
+                ks::Removal& o = h_out[cand_pos[a]];
+                if (v.node != o.node || v.evicted != o.evicted || v.first_row != o.first_row || v.removable < 0 ||
+                    v.ok + v.over_capacity + v.not_found != v.evicted)
+                    return fail(e, KS_EDEVICE, "removable: candidate node %d was not decided", (int)o.node);
+                o = v;
+            }
+            info[0] = (int64_t)segs.size();
+            info[1] = n_cand;
+        }
+    }
+    // ---- the candidates with more pods than one set of lists decides: ks_drain_at, one by one ----
+    std::vector<ks_eviction> one;
+    for (int32_t j : slow) {
+        ks::Removal& o = h_out[j];
+        one.resize(o.evicted);
+        int64_t k = 0, dinfo[KS_DRAIN_INFO];
+        if (ks_status r = ks_drain_at(e, t, 1, &o.node, one.data(), o.evicted, &k, nullptr, dinfo); r != KS_OK) return r;
+        if (k != o.evicted) return fail(e, KS_EDEVICE, "removable: node %d evicts %lld pods, not %d", (int)o.node, (long long)k, (int)o.evicted);
+        o.ok = (int32_t)dinfo[1]; o.over_capacity = (int32_t)dinfo[2]; o.not_found = (int32_t)dinfo[3];
+        o.removable = o.ok == o.evicted;
+        std::memcpy(h_rows.data() + o.first_row, one.data(), sizeof(ks_eviction) * k);
+    }
+    info[2] = (int64_t)slow.size();
+    for (int32_t j = 0; j < m; j++) {
+        info[3] += h_out[j].evicted == 0;
+        info[4] += h_out[j].removable;
+    }
+    info[5] = n_ev;
+    std::memcpy(out, h_out.data(), sizeof(ks_removal) * m);
+    if (rows_out && n_ev) std::memcpy(rows_out, h_rows.data(), sizeof(ks_eviction) * n_ev);
+    if (info_out) std::copy(info, info + KS_REMOVABLE_INFO, info_out);
     return KS_OK;
 }
 

@@ -56,6 +56,12 @@ KS_PLACE_INFO = 4
 # segments, drained nodes that had no running pod)
 KS_DRAIN_MAX_PODS = 65536
 KS_DRAIN_INFO = 6
+# ks_removable_at: the info words (segments, candidates resolved by the batched kernel, candidates
+# answered through the single-drain path, candidates with no running pod, removable candidates,
+# evicted pods); KS_REMOVABLE_MAX_BATCHED: the pods of a candidate the batched kernel decides
+# (csrc/ks_device.h kRemovableMaxPods = KS_PLACE_L - 1)
+KS_REMOVABLE_INFO = 6
+KS_REMOVABLE_MAX_BATCHED = 31
 
 STATUS_NAMES = {KS_OK: "OK", KS_EINVAL: "InvalidArgument", KS_ENOTFOUND: "NotFound",
                 KS_EDEVICE: "DeviceError", KS_ENOMEM: "OutOfMemory", KS_ERANGE: "OutOfDomain"}
@@ -70,6 +76,7 @@ EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods"
                     "ks_shard_layout", "ks_merge_candidates",
                     "ks_requested_at", "ks_filter_at", "ks_score_at", "ks_cluster_series", "ks_node_peaks",
                     "ks_headroom_at", "ks_headroom_series", "ks_place_at", "ks_drain_at",
+                    "ks_removable_at",
                     # include/ks_ingest.h
                     "ks_parse_quantity", "ks_parse_simspec", "ks_cluster_parse", "ks_cluster_free",
                     "ks_cluster_nodes", "ks_cluster_tick", "ks_cluster_start_clock", "ks_cluster_arrays",
@@ -235,10 +242,11 @@ def load():
     L.ks_headroom_series.argtypes = [p, C.c_int64, C.c_int64, C.c_int32, p, p, p, p, p]
     L.ks_place_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, p, p, p]
     L.ks_drain_at.argtypes = [p, C.c_int64, C.c_int32, p, p, C.c_int64, C.POINTER(C.c_int64), p, p]
+    L.ks_removable_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, C.c_int64, C.POINTER(C.c_int64), p]
     for f in ("ks_load_nodes", "ks_submit_pods", "ks_step", "ks_filter", "ks_score", "ks_usage", "ks_usage_at",
               "ks_usage_digest", "ks_pod_lookup", "ks_node_pods", "ks_requested_at", "ks_filter_at", "ks_score_at",
               "ks_cluster_series", "ks_node_peaks", "ks_headroom_at", "ks_headroom_series", "ks_place_at",
-              "ks_drain_at"):
+              "ks_drain_at", "ks_removable_at"):
         getattr(L, f).restype = C.c_int
     L.ks_current_tick.argtypes = [p]
     L.ks_current_tick.restype = C.c_int64

@@ -19,7 +19,8 @@ Node.CreatePod's test  ``headroom_at`` / ``headroom_series``: how many more pods
 scheduleOne, what-if   ``place_at``: where k more pods would be bound at a past tick, on a
                        private copy of the state (kubesim/kubesim.go:143-225);
                        ``drain_at``: where the pods running on a node set would go if the
-                       set left k.nodes (kubesim/kubesim.go:168-206)
+                       set left k.nodes (kubesim/kubesim.go:168-206); ``removable_at``: that
+                       answer for each of m candidate nodes on its own
 =====================  ==============================================================
 
 Errors come back as :class:`KsError` with the reference's kind (``InvalidArgument`` /
@@ -58,6 +59,10 @@ assert PLACEMENT_DTYPE.itemsize == 24
 EVICTION_DTYPE = np.dtype([("pod", np.int64), ("from", np.int32), ("node", np.int32), ("status", np.int32),
                            ("pad", np.int32), ("score", np.int64), ("candidates", np.int64)])
 assert EVICTION_DTYPE.itemsize == 40
+# ks_removal (include/ks_engine.h)
+REMOVAL_DTYPE = np.dtype([("node", np.int32), ("evicted", np.int32), ("ok", np.int32), ("over_capacity", np.int32),
+                          ("not_found", np.int32), ("removable", np.int32), ("first_row", np.int64)])
+assert REMOVAL_DTYPE.itemsize == 32
 
 
 def _config(tick_seconds, filter_mode, filters, scorers, device, batch_pods, engine_flags):
@@ -329,6 +334,47 @@ class Engine:
         return dict(pod=rec["pod"].copy(), from_node=rec["from"].copy(), node=rec["node"].copy(),
                     status=rec["status"].copy(), score=rec["score"].copy(), candidates=rec["candidates"].copy(),
                     after=aft, info=info)
+
+    # -- removal scan (include/ks_engine.h, ks_removable_at) ------------------------------------
+    def removable_at(self, t: int, nodes, rows: bool = False):
+        """Which of ``nodes`` could each be taken out on its own at tick t: for candidate c the answer
+        of ``drain_at(t, [c])`` — candidates are independent, no engine state changes.  ``nodes``:
+        distinct node indices.  Returns a dict of arrays over the candidates, in the caller's order —
+        ``node``, ``evicted`` (pods running on it), ``ok`` / ``over_capacity`` / ``not_found`` (their
+        re-placements), ``removable`` (bool: every pod re-bound Ok, also when none runs there),
+        ``first_row`` — plus ``info`` (segments, candidates resolved by the batched kernel, candidates
+        answered through the single-drain path, candidates with no running pod, removable candidates,
+        evicted pods) and ``rows``: with ``rows=True`` ``drain_at``'s arrays over the evicted pods
+        (``pod``, ``from_node``, ``node``, ``status``, ``score``, ``candidates``), the candidates'
+        rows concatenated in the caller's order, candidate j's at ``first_row[j]``; else None.  It
+        makes the sizing call itself."""
+        nd = _c(nodes, np.int32).reshape(-1)
+        m = len(nd)
+        out = np.zeros(max(m, 1), REMOVAL_DTYPE)
+        n_rows = C.c_int64(0)
+        info = np.zeros(_lib.KS_REMOVABLE_INFO, np.int64)
+        if rows:
+            # a one-row buffer first: KS_ERANGE comes back with the count as soon as the gather has it
+            rec = np.zeros(1, EVICTION_DTYPE)
+            rc = self._L.ks_removable_at(self.h, t, m, _p(nd), _p(out), _p(rec), 1, C.byref(n_rows), _p(info))
+            if rc == _lib.KS_ERANGE and 1 < n_rows.value <= _lib.KS_DRAIN_MAX_PODS:
+                rec = np.zeros(n_rows.value, EVICTION_DTYPE)
+                rc = self._L.ks_removable_at(self.h, t, m, _p(nd), _p(out), _p(rec), n_rows.value, C.byref(n_rows),
+                                             _p(info))
+        else:
+            rc = self._L.ks_removable_at(self.h, t, m, _p(nd), _p(out), None, 0, C.byref(n_rows), _p(info))
+        self._check(rc)
+        out = out[:m]
+        res = {f: out[f].copy() for f in ("node", "evicted", "ok", "over_capacity", "not_found", "first_row")}
+        res["removable"] = out["removable"] != 0
+        res["info"] = info
+        res["rows"] = None
+        if rows:
+            rec = rec[:n_rows.value]
+            res["rows"] = dict(pod=rec["pod"].copy(), from_node=rec["from"].copy(), node=rec["node"].copy(),
+                               status=rec["status"].copy(), score=rec["score"].copy(),
+                               candidates=rec["candidates"].copy())
+        return res
 
     def pod_lookup(self, node: int, key_id: int):
         """Node.GetPod: FIFO index of the pod stored on ``node`` under ``key_id`` (KsError NotFound)."""
