@@ -667,6 +667,7 @@ func (e *Engine) PodStatus(lo, n int64) ([]PodInfo, error) {
 const (
 	SelftestLRMicro     = int32(C.KS_SELFTEST_LR_MICRO)     // the micro evaluator's LeastRequested floor, every (x, A)
 	SelftestMicroStates = int32(C.KS_SELFTEST_MICRO_STATES) // the micro evaluator and its scan form, every usage of 13 capacity pairs
+	SelftestListMerge   = int32(C.KS_SELFTEST_LIST_MERGE)   // merge_cl's score-class list merge against the host fold
 )
 
 // Selftest runs one device self-test and returns the number of mismatching cases (0 = pass).

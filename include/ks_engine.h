@@ -567,7 +567,12 @@ ks_status ks_debug_watch(ks_engine* eng, int64_t pod);
 /* test 1: the whole micro evaluator and its scan form on every usage (uc, um) in [0, Ac + 2] x
  * [0, Am + 2] of thirteen capacity pairs with Ac * Am < 2^24 (both domain edges, primes, multiples
  * of ten, degenerate ones), filters off, three scorer configurations, against exact 64-bit integers. */
-enum { KS_SELFTEST_LR_MICRO = 0, KS_SELFTEST_MICRO_STATES = 1 };
+/* test 2: merge_cl's score-class list merge (ks_device.h) against the host's topl_insert fold, for list
+ * lengths 8 and 12: 1 .. 600 lists at 256 threads and 1,025 / 4,096 at 1,024; one class everywhere, two
+ * classes with the boundary inside a lane's run, inside a wave and at a wave boundary, one block holding
+ * the whole top class behind blocks holding 1-3, every total distinct, fewer feasible nodes than the list
+ * length, empty lists, and threshold-prefix (pruned) lists.  *failures = mismatching output words. */
+enum { KS_SELFTEST_LR_MICRO = 0, KS_SELFTEST_MICRO_STATES = 1, KS_SELFTEST_LIST_MERGE = 2 };
 ks_status ks_selftest(int32_t device, int32_t test, int64_t* failures);
 /* Device batch of the fused Filter + Score evaluator (diagnostics / tests; no engine needed): case i is
  * one node (alloc[i][4] cpu memory gpu pods, -1 absent; run[i][4] requested cpu memory gpu of the running

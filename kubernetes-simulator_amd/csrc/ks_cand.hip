@@ -12,7 +12,7 @@
 //                        expiries due before pods 1 .. nb-1 (slots), the distinct nodes E of the
 //                        pre-batch pods among them, each pod's own slot.
 //   merge_cl_kernel      (after the scan, one workgroup per pod) the exact top-L of the pod's block
-//                        lists (the merge kernel's algorithm), then its static candidates cl_i: the
+//                        lists (the score-class merge, ks_device.h), then its static candidates cl_i: the
 //                        top-L entries outside E (their snapshot key is exact while the node is
 //                        unbound) and every E node whose exact key at pod i's tick (the pre-batch
 //                        expiries due by then applied) reaches thr_i, the list's last key — sorted,
@@ -101,22 +101,51 @@ constexpr int kEPer = kEMax / 256;
 static_assert(kTopLOverlap >= kTopL, "merged lists kept at the longest list length");
 // kDirect (the two-launch chain): a kept entry's slot record from the constants table and the usage
 // fields (load_rec12c) instead of the ten SoA fields.
+//
+// Which entries lie on an E node is decided in the workgroup: e_idx[n] >= 0 exactly for the nodes
+// ws.e_node[0 .. n_e) (the window prep marks them, the chunk kernel's commit unmarks them), and every
+// thread holds its E node ids already (en: E nodes tid and tid + nthr; any further ones from
+// ws.e_node) — each compares them with the kLL candidate nodes in LDS and ORs a bit into c_.emask, so
+// no global round trip stands between the merged list and the threshold.  The caller zeroed c_.cnt
+// and c_.emask before the barrier that published cand[].
+struct ClLDS {
+    int cnt;
+    uint32_t emask;
+};
 template <int kMode, int kLL, bool kDirect>
 __device__ __forceinline__ void cand_list(const EngineArgs& a, WinWS& ws, int i, const uint64_t* cand,
-                                          const uint64_t* ek, int n_e) {
-    static_assert(kLL >= kTopL && kLL <= kWave, "one list entry per lane");
-    const int tid = threadIdx.x;
+                                          const uint64_t* ek, int n_e, const int32_t (&en)[2], ClLDS& c_) {
+    static_assert(kLL >= kTopL && kLL <= 32, "one list entry per lane, one mask bit per entry");
+    const int tid = threadIdx.x, nthr = blockDim.x;
     PDG(uint64_t pt = pstamp();)
     __shared__ uint64_t buf[kClBuf];
-    __shared__ int cnt;
+    int& cnt = c_.cnt;
     __shared__ uint64_t s_thr;
     __shared__ int s_full;
-    if (tid == 0) cnt = 0;
+    {
+        uint32_t cn[kLL];  // the candidates' nodes (an empty entry: -1, no node)
+#pragma unroll
+        for (int k = 0; k < kLL; ++k) cn[k] = 0xFFFFFFFFu - (uint32_t)cand[k];
+        uint32_t hit = 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (tid + q * nthr >= n_e) continue;
+#pragma unroll
+            for (int k = 0; k < kLL; ++k) hit |= cn[k] == (uint32_t)en[q] ? 1u << k : 0u;
+        }
+#pragma unroll 1
+        for (int j = tid + 2 * nthr; j < n_e; j += nthr) {
+            const uint32_t n = (uint32_t)ws.e_node[j];
+#pragma unroll
+            for (int k = 0; k < kLL; ++k) hit |= cn[k] == n ? 1u << k : 0u;
+        }
+        if (hit) atomicOr(&c_.emask, hit);
+    }
     __syncthreads();
     if (tid < kWave) {  // wave 0, lane k: list entry k
         const int lane = tid;
         const uint64_t x = lane < kLL ? cand[lane] : 0ull;
-        const bool un = x != 0 && a.e_idx[key_node(x)] < 0;
+        const bool un = x != 0 && !((c_.emask >> (lane & 31)) & 1u);  // (x != 0: lane < kLL <= 32)
         const uint64_t um = __ballot(un);
         const int rank = __popcll(um & ((1ull << lane) - 1ull));
         if (un && rank < kTopL) {
@@ -213,11 +242,45 @@ __device__ __forceinline__ void cand_list(const EngineArgs& a, WinWS& ws, int i,
     }
 }
 
-// merge + candidate list of pod b in one workgroup (the merge kernel's exact top-L over nl sorted
-// lists lists[b * pod_stride + k * list_stride] of kLL keys, ks_kernels.hip, then cand_list) — one
-// launch fewer per batch.  src == nullptr: the engine's own block lists (pruned: only the blocks its
-// bitmap flags, ks_scan.h).  Every launch clears the pods' bitmaps and thresholds for the next scan.
+// The final stage of the score-class merge (ks_device.h), by one wave: the nwav wave results wl[w]
+// (kLL keys each, in wave = node order) to the pod's top kLL, 0-padded.  Up to 4 waves (256
+// threads): one candidate per lane; up to kMergeMaxWaves: kPer per lane.
 constexpr int kMergeMaxWaves = 16;
+template <int kLL>
+__device__ __forceinline__ void merge_final_stage(const uint64_t (*wl)[kLL], int nwav, uint64_t* pc, int lane) {
+    static_assert(4 * kLL <= kWave, "one candidate per lane at 4 waves");
+    const int nc = nwav * kLL;
+    if (nwav <= 4) {
+        const uint64_t v[1] = {lane < nc ? wl[lane / kLL][lane % kLL] : 0ull};
+        class_merge_final<kLL, 1>(v, pc, lane);
+    } else {
+        constexpr int kPer = (kMergeMaxWaves * kLL + kWave - 1) / kWave;
+        uint64_t v[kPer];
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) {
+            const int c = lane + q * kWave;
+            v[q] = c < nc ? wl[c / kLL][c % kLL] : 0ull;
+        }
+        class_merge_final<kLL, kPer>(v, pc, lane);
+    }
+}
+
+// merge + candidate list of pod b in one workgroup (the exact top-L over nl sorted lists
+// lists[b * pod_stride + k * list_stride] of kLL keys, then cand_list) — one launch fewer per batch.
+// src == nullptr: the engine's own block lists (pruned: only the blocks its bitmap flags, ks_scan.h).
+// Every launch clears the pods' bitmaps and thresholds for the next scan.
+//
+// The merge is the score-class merge of ks_device.h (where its exactness argument stands), not the
+// merge kernel's extraction rounds (ks_kernels.hip: kLL rounds of wave max + ballot per wave, kLL
+// more over the wave results).  Each thread folds a contiguous range of the lists
+// (merge_list_range) with topl_insert, so its sorted top[] covers a contiguous node range and
+// lane order is node order across the workgroup; a wave then ranks one whole score class per step
+// (a wave max of the high words, a run count, a prefix sum), and wave 0 does the same by ballots
+// over the wave results.  The output is what the extraction rounds give, bit for bit: the kLL
+// largest distinct non-zero keys, descending, 0-padded (pc, ws.mrg).  Every path into this kernel has
+// its lists in node order — the engine's own block lists by block index, their flagged subset in
+// block order, the sharded form's parts by part index (ascending block ranges, ks_shard_layout) —
+// so none keeps the extraction rounds.
 }  // namespace sq
 #ifdef KS_MCL_BYVAL
 thread_local const EngineArgs* ks_mcl_host_args = nullptr;  // (diagnostic build: set by step_body before each launch)
@@ -350,9 +413,11 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
     // it is in flight
     if constexpr (kDirect) e_index();
     uint64_t lv0[kLL];
-    const bool has0 = tid < nfl;
+    int j0, j1;  // this thread's lists: a contiguous range, so thread order is node order
+    merge_list_range(tid, nthr, nfl, j0, j1);
+    const bool has0 = j0 < j1;
     {
-        const int l0 = has0 ? (pruned ? scn::flagged_block(tid, 0, nl, F) : tid) : 0;
+        const int l0 = has0 ? (pruned ? scn::flagged_block(j0, 0, nl, F) : j0) : 0;
         const ulonglong2* lp = reinterpret_cast<const ulonglong2*>(lists + (int64_t)l0 * list_stride);
 #pragma unroll
         for (int k = 0; k < kLL / 2; ++k) {
@@ -373,7 +438,7 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
 #pragma unroll
         for (int k = 0; k < kLL; ++k) top[k] = lv0[k];
     }
-    for (int j = tid + nthr; j < nfl; j += nthr) {
+    for (int j = j0 + 1; j < j1; ++j) {
         const int blk = pruned ? scn::flagged_block(j, 0, nl, F) : j;
         const ulonglong2* lp = reinterpret_cast<const ulonglong2*>(lists + (int64_t)blk * list_stride);
         uint64_t lv[kLL];
@@ -387,55 +452,21 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
     }
     __shared__ uint64_t wl[kMergeMaxWaves][kLL];
     __shared__ uint64_t pc[kLL];
+    __shared__ ClLDS cl;
     PDG(MDG_AT(6, pt);)
-    int head = 0;
-    for (int r = 0; r < kLL; ++r) {
-        uint64_t h = 0;
-#pragma unroll
-        for (int k = 0; k < kLL; ++k) h = (k == head) ? top[k] : h;
-        const uint64_t m = wave_max_u64(h);
-        const uint64_t hit = __ballot(h == m && m != 0);
-        if (lane == 0) wl[wave][r] = m;
-        if (hit && lane == __ffsll((unsigned long long)hit) - 1) head++;
-    }
+    // the score-class merge (ks_device.h): each wave's top kLL of its lanes' lists, then wave 0 over
+    // the wave results in (wave, position) order.  Lane order is node order on every path that
+    // reaches this kernel — the engine's own block lists in block order (the pruned form: the
+    // flagged blocks in block order), the sharded form's parts in part order (ks_shard_layout:
+    // ascending block ranges) — so no path keeps the extraction rounds.
+    class_merge_wave<kLL>(top, wl[wave], lane);
+    if (tid == 0) { cl.cnt = 0; cl.emask = 0; }
+    // (the E keys here, not later: computed just before cand_list's E-inclusion loop they left this
+    // section 3.7k cycles shorter and that loop 7.2k longer, and the bench no faster — EXPERIMENTS.md)
     if constexpr (kDirect) e_keys();  // (cand_list reads ek after its own barriers)
     __syncthreads();
     PDG(MDG_AT(7, pt);)
-    if (wave == 0 && nthr <= 256) {  // the wave lists' top kLL: one candidate per lane (4 waves)
-        static_assert(4 * kLL <= kWave, "one candidate per lane");
-        uint64_t v = lane < nwav * kLL ? wl[lane / kLL][lane % kLL] : 0ull;
-        for (int r = 0; r < kLL; ++r) {
-            const uint64_t m = wave_max_u64(v);
-            if (lane == 0) pc[r] = m;
-            if (m == 0) continue;
-            const uint64_t h = __ballot(v == m);  // keys are distinct: one holder
-            if (lane == __ffsll((unsigned long long)h) - 1) v = 0;
-        }
-    } else if (wave == 0) {  // up to kPer candidates per lane
-        constexpr int kPer = (kMergeMaxWaves * kLL + kWave - 1) / kWave;
-        const int nc = nwav * kLL;
-        uint64_t v[kPer];
-#pragma unroll
-        for (int q = 0; q < kPer; ++q) {
-            const int c = lane + q * kWave;
-            v[q] = c < nc ? wl[c / kLL][c % kLL] : 0ull;
-        }
-        for (int r = 0; r < kLL; ++r) {
-            uint64_t lm = v[0];
-#pragma unroll
-            for (int q = 1; q < kPer; ++q) lm = lm > v[q] ? lm : v[q];
-            const uint64_t m = wave_max_u64(lm);
-            if (lane == 0) pc[r] = m;
-            if (m == 0) continue;
-            bool done = false;  // keys are distinct: exactly one holder
-#pragma unroll
-            for (int q = 0; q < kPer; ++q) {
-                const uint64_t h = __ballot(!done && v[q] == m);
-                if (h && lane == __ffsll((unsigned long long)h) - 1) v[q] = 0;
-                done = done || h != 0;
-            }
-        }
-    }
+    if (wave == 0) merge_final_stage<kLL>(wl, nwav, pc, lane);
     __syncthreads();
     // a reused pod's merged list as merge_cl kept it for the previous batch; every pod's merged list
     // kept for the next (its possible reuse)
@@ -443,7 +474,7 @@ __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __rest
     if (reuse) __syncthreads();
     if (tid < kLL) ws.mrg[mpar][b][tid] = pc[tid];
     PDG(MDG_AT(8, pt);)
-    cand_list<kMode, kLL, kDirect>(a, ws, b, pc, ek, n_e);
+    cand_list<kMode, kLL, kDirect>(a, ws, b, pc, ek, n_e, en, cl);
 }
 
 }  // namespace sq
@@ -482,6 +513,43 @@ hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t*
 #ifdef KS_MCL_BYVAL
 #undef d
 #endif
+    return hipGetLastError();
+}
+
+// ks_selftest KS_SELFTEST_LIST_MERGE: merge_cl_kernel's list merge alone — the same thread-to-list
+// assignment (merge_list_range), topl_insert folds and score-class stages — over nl sorted lists of
+// kLL keys, one workgroup; out[0 .. kLL) receives the top kLL.
+namespace sq {
+template <int kLL>
+__global__ __launch_bounds__(1024) void list_merge_test_kernel(const uint64_t* __restrict__ lists, int nl,
+                                                                uint64_t* __restrict__ out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nthr = blockDim.x, nwav = nthr / kWave;
+    uint64_t top[kLL];
+#pragma unroll
+    for (int k = 0; k < kLL; ++k) top[k] = 0;
+    int j0, j1;
+    merge_list_range(tid, nthr, nl, j0, j1);
+    for (int j = j0; j < j1; ++j) {
+        uint64_t lv[kLL];
+#pragma unroll
+        for (int k = 0; k < kLL; ++k) lv[k] = lists[(int64_t)j * kLL + k];
+        topl_insert<kLL>(top, lv);
+    }
+    __shared__ uint64_t wl[kMergeMaxWaves][kLL];
+    __shared__ uint64_t pc[kLL];
+    class_merge_wave<kLL>(top, wl[wave], lane);
+    __syncthreads();
+    if (wave == 0) merge_final_stage<kLL>(wl, nwav, pc, lane);
+    __syncthreads();
+    if (tid < kLL) out[tid] = pc[tid];
+}
+}  // namespace sq
+
+hipError_t launch_list_merge_test(const uint64_t* lists, int nl, int L, int threads, uint64_t* out, hipStream_t st) {
+    if ((L != kTopL && L != kTopLOverlap) || (threads != 256 && threads != 1024) || nl < 0) return hipErrorInvalidValue;
+    if (L == kTopL) hipLaunchKernelGGL((sq::list_merge_test_kernel<kTopL>), dim3(1), dim3(threads), 0, st, lists, nl, out);
+    else hipLaunchKernelGGL((sq::list_merge_test_kernel<kTopLOverlap>), dim3(1), dim3(threads), 0, st, lists, nl, out);
     return hipGetLastError();
 }
 

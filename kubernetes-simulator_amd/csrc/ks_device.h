@@ -667,6 +667,104 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return ((uint64_t)mh << 32) | ml;
 }
 
+// Wave-wide inclusive prefix sum in the same DPP moves: row_shr 1/2/4/8 scans each 16-lane row,
+// row_bcast 15/31 adds the rows before (a lane without a source adds 0).  Lane 63 holds the total.
+__device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Score-class merge of sorted key lists whose lane order is node order (merge_cl, ks_cand.hip).
+//
+// A key is (total + 1) << 32 | ~node, so within one score class (one high word) descending key order
+// is ascending node order.  When every lane holds a sorted (descending, 0-padded) list and each
+// lane's nodes all lie below the next lane's, the number of keys above a key x of class m at
+// position k of lane l is exact without comparing a node word:
+//     (keys of higher classes, all lanes) + (class-m keys of lanes < l) + (class-m keys before k in l).
+// Classes are taken from the top: m = the wave max of the high words at the lanes' cursors, each
+// lane's run of class-m keys starts at its cursor (its list is sorted and every higher class is
+// consumed), an exclusive prefix sum of the run lengths gives the second term.  The keys whose count
+// is < L are the wave's L largest, written at that rank; the loop ends once L keys are ranked or no
+// key is left.  The result is the exact top-L of the keys held, the same keys in the same order as L
+// rounds of (wave max, drop the holder).
+//
+// The lists held are themselves truncated (a block's top-L, a thread's top-L of several blocks, a
+// threshold prefix in the pruned form).  That loses nothing: a list cut at L entries inside a class
+// already supplies L keys at or above that class, so no key it dropped, and no later lane's key of
+// that class or below, is among the L largest — and the count above gives each of those a rank >= L
+// (the cut lane's L keys are all counted before them).  A pruned list drops only keys below a
+// threshold that L keys of the snapshot reach (ks_scan.h).
+// ---------------------------------------------------------------------------------------------
+// One wave: lane l holds top[] (sorted, 0-padded); out[0 .. L) receives the wave's top-L, 0-padded.
+template <int L>
+__device__ __forceinline__ void class_merge_wave(const uint64_t (&top)[L], uint64_t* out, int lane) {
+    uint32_t hw[L];
+#pragma unroll
+    for (int k = 0; k < L; ++k) hw[k] = (uint32_t)(top[k] >> 32);
+    int head = 0, ranked = 0;  // this lane's cursor; keys ranked so far (wave-uniform)
+    while (ranked < L) {
+        uint32_t h = 0;
+#pragma unroll
+        for (int k = 0; k < L; ++k) h = (k == head) ? hw[k] : h;
+        const uint32_t m = wave_max_u32(h);
+        if (m == 0) break;
+        int run = 0;
+#pragma unroll
+        for (int k = 0; k < L; ++k) run += hw[k] == m ? 1 : 0;
+        const uint32_t incl = wave_incl_sum_u32((uint32_t)run);
+        const int base = ranked + (int)incl - run - head;  // rank of top[k], k in the run: base + k
+#pragma unroll
+        for (int k = 0; k < L; ++k)
+            if (hw[k] == m && base + k < L) out[base + k] = top[k];
+        head += run;
+        ranked += __builtin_amdgcn_readlane((int)incl, 63);
+    }
+    if (lane >= ranked && lane < L) out[lane] = 0ull;
+}
+
+// One wave over nc <= kPer * 64 candidates in (list, position) order, lists in node order (the wave
+// results of class_merge_wave): candidate c = lane + 64 q is v[q].  The same class rule by ballots:
+// a class's keys are in candidate order, so a key's rank is the count ranked so far plus the class's
+// candidates before it.  out[0 .. L): the top-L, 0-padded.
+template <int L, int kPer>
+__device__ __forceinline__ void class_merge_final(const uint64_t (&v)[kPer], uint64_t* out, int lane) {
+    uint32_t hw[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) hw[q] = (uint32_t)(v[q] >> 32);
+    int ranked = 0;
+    while (ranked < L) {
+        uint32_t lm = hw[0];
+#pragma unroll
+        for (int q = 1; q < kPer; ++q) lm = lm > hw[q] ? lm : hw[q];
+        const uint32_t m = wave_max_u32(lm);
+        if (m == 0) break;
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) {
+            const bool in = hw[q] == m;
+            const uint64_t mask = __ballot(in);
+            const int rank = ranked + __popcll(mask & ((1ull << lane) - 1ull));
+            if (in && rank < L) out[rank] = v[q];
+            if (in) hw[q] = 0;
+            ranked += __popcll(mask);
+        }
+    }
+    if (lane >= ranked && lane < L) out[lane] = 0ull;
+}
+
+// The lists one merge thread folds: thread t of nthr takes the contiguous range [j0, j1) of nfl
+// lists, so its top-L covers a contiguous node range and thread order is node order.
+__device__ __forceinline__ void merge_list_range(int t, int nthr, int nfl, int& j0, int& j1) {
+    const int q = (nfl + nthr - 1) / nthr;
+    j0 = t * q < nfl ? t * q : nfl;
+    j1 = j0 + q < nfl ? j0 + q : nfl;
+}
+
 // ctr[] slots of a batch (EngineArgs::ctr), pod flags the resolvers stop on, error codes
 // (5, 6: cumulative counts of the window prep's rescans and list reuses — diagnostic builds use
 // ctr[5..31] for their own counters)
@@ -980,6 +1078,9 @@ hipError_t launch_selftest_lr_micro(unsigned long long* bad, hipStream_t st);
 // every state of a fixed list of micro capacity pairs, eval_total1_micro and eval_scan_micro against
 // exact 64-bit integers (ks_selftest test 1)
 hipError_t launch_selftest_micro_states(unsigned long long* bad, hipStream_t st);
+// merge_cl's list merge alone on nl sorted lists of L keys (kTopL or kTopLOverlap), one workgroup of
+// 256 or 1,024 threads; out[0 .. L): the top L (ks_selftest test 2, ks_cand.hip)
+hipError_t launch_list_merge_test(const uint64_t* lists, int nl, int L, int threads, uint64_t* out, hipStream_t st);
 
 // ks_selftest_eval: a batch of (node, pod) cases through every evaluator variant and state type.
 // Only this case layout is shared; each kernel lives in the translation unit that owns its state

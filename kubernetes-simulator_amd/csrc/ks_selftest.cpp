@@ -1,6 +1,7 @@
 // ks_selftest.cpp — the device self-tests of include/ks_engine.h (ks_selftest, ks_selftest_eval):
 // the evaluators of ks_device.h run on the device over the caller's cases.  They need no engine.
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 #include "ks_host.h"  // kMaxValue: the value range ks_load_nodes / ks_submit_pods accept
@@ -51,14 +52,135 @@ bool ev_batch_valid(const ks::Cfg& c, int64_t n, const int64_t* alloc, const int
     return true;
 }
 
+// ---- KS_SELFTEST_LIST_MERGE: merge_cl's list merge against the host fold ----------------------
+// A case: per-node totals (total + 1, 0 = infeasible) over nl 256-node blocks.  Its block lists are
+// each block's top-L keys; `prune` cuts them to a threshold prefix as the pruned scan does (ks_scan.h:
+// any key that L keys reach is a valid threshold, and blocks read different ones): none, the last key
+// of the first full list, or the exact L-th key, by block index.
+struct MergeCase { int nl, threads; bool prune; std::vector<uint32_t> tot; };
+
+template <int L>
+void merge_case_lists(const MergeCase& c, std::vector<uint64_t>& lists, uint64_t (&want)[L]) {
+    constexpr int kBlk = 256;
+    lists.assign((size_t)c.nl * L, 0ull);
+    std::vector<uint64_t> keys;
+    for (int b = 0; b < c.nl; b++) {
+        keys.clear();
+        for (int t = 0; t < kBlk; t++) {
+            const size_t n = (size_t)b * kBlk + t;
+            const uint64_t k = n < c.tot.size() ? ks::make_key(c.tot[n], (uint32_t)n) : 0ull;
+            if (k) keys.push_back(k);
+        }
+        std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+        for (size_t k = 0; k < keys.size() && k < (size_t)L; k++) lists[(size_t)b * L + k] = keys[k];
+    }
+    auto fold = [&](uint64_t (&top)[L]) {
+        for (int k = 0; k < L; k++) top[k] = 0;
+        for (int b = 0; b < c.nl; b++) {
+            uint64_t lv[L];
+            for (int k = 0; k < L; k++) lv[k] = lists[(size_t)b * L + k];
+            ks::topl_insert<L>(top, lv);
+        }
+    };
+    fold(want);
+    if (!c.prune) return;
+    uint64_t first_full = 0;
+    for (int b = 0; b < c.nl && !first_full; b++) first_full = lists[(size_t)b * L + L - 1];
+    const uint64_t thr[3] = {0ull, first_full, want[L - 1]};
+    for (int b = 0; b < c.nl; b++)
+        for (int k = 0; k < L; k++)
+            if (lists[(size_t)b * L + k] < thr[b % 3]) lists[(size_t)b * L + k] = 0ull;
+    uint64_t again[L];
+    fold(again);  // (pruning drops nothing the top L needs)
+    for (int k = 0; k < L; k++)
+        if (again[k] != want[k]) want[k] = ~0ull;  // a broken case fails the test
+}
+
+std::vector<MergeCase> merge_cases(int L) {
+    std::vector<MergeCase> cs;
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { rng = rng * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(rng >> 33); };
+    auto add = [&](int nl, bool prune, auto&& f) {
+        MergeCase c{nl, nl > 1024 ? 1024 : 256, prune, std::vector<uint32_t>((size_t)nl * 256)};
+        for (size_t n = 0; n < c.tot.size(); n++) c.tot[n] = f((int64_t)n);
+        cs.push_back(std::move(c));
+    };
+    const int sizes[] = {1, 2, 63, 64, 65, 196, 256, 257, 600, 1025, 4096};
+    for (int nl : sizes) {
+        const int64_t n = (int64_t)nl * 256;
+        add(nl, false, [](int64_t) { return 7u; });  // one class everywhere
+        // a few small classes, the top one rare: ties dominate, the top L spans one to three classes
+        add(nl, false, [&](int64_t) { const uint32_t r = rnd() % (uint32_t)(n / 3 + 2); return r == 0 ? 9u : r < 4 ? 8u : 7u - r % 3; });
+        add(nl, true, [&](int64_t) { const uint32_t r = rnd() % (uint32_t)(n / 5 + 2); return r == 0 ? 9u : r < 3 ? 8u : 7u - r % 3; });
+        // every total distinct, scattered (40507 is coprime to every n here: a bijection mod n)
+        add(nl, false, [&](int64_t i) { return (uint32_t)(1 + (i * 40507 + 17) % n); });
+        add(nl, true, [&](int64_t i) { return (uint32_t)(1 + (n - 1 - i)); });  // distinct, the top at the lowest nodes
+        add(nl, false, [&](int64_t i) { return (uint32_t)(1 + i); });  // distinct, the top at the highest nodes
+        add(nl, false, [](int64_t) { return 0u; });  // all lists empty
+        // fewer than L feasible nodes in all (every step-th node, step >= n / (L - 1)), two classes
+        const int64_t step = (n + L - 2) / (L - 1);
+        add(nl, false, [&](int64_t i) { return i % step == 5 ? 3u + (uint32_t)(i & 1) : 0u; });
+    }
+    // 256 lists at 256 threads: lane l holds block l's list.  Two classes (9 above 5):
+    auto two = [&](auto&& top_class) {
+        add(256, false, [&](int64_t i) { return top_class((int)(i / 256), (int)(i % 256)) ? 9u : 5u; });
+        add(256, true, [&](int64_t i) { return top_class((int)(i / 256), (int)(i % 256)) ? 9u : 5u; });
+    };
+    two([](int b, int t) { return b == 0 && t < 2; });                 // the class boundary inside lane 0's list, the cut inside its run
+    two([](int b, int t) { return b == 5 && t >= 253; });              // three top keys in lane 5, the cut inside lane 0's run of the second class
+    two([](int b, int t) { return (b == 3 && t < 2) || (b == 40 && t == 7); });  // boundary inside wave 0
+    two([](int b, int t) { return b >= 60 && b < 64 && t == 9; });     // the top class ends exactly at a wave boundary
+    two([&](int b, int t) { return b >= 64 - L && b < 64 && t == 0; });  // L top keys end at the wave boundary
+    two([&](int b, int t) { return b >= 64 - L + 1 && b <= 64 && t == 0; });  // ... one past it
+    two([](int b, int t) { return (b == 63 || b == 64 || b == 128) && t >= 254; });  // runs on both sides of wave boundaries
+    // one block holding >= L of the top class while lower-index blocks hold 1-3 each
+    two([&](int b, int t) { return (b == 9 && t < L + 4) || (b == 1 && t == 3) || (b == 2 && t < 2) || (b == 4 && t >= 253); });
+    two([&](int b, int t) { return (b == 200 && t < L) || (b == 66 && t == 3) || (b == 130 && t < 3); });
+    // the second class only in a few lanes: runs of different lengths, nothing below
+    add(256, false, [&](int64_t i) { const int b = (int)(i / 256), t = (int)(i % 256);
+                                      return b == 70 && t == 1 ? 9u : (b == 10 && t < 3) || (b == 50 && t < 2) || (b == 63 && t < L) ? 5u : 0u; });
+    return cs;
+}
+
+template <int L>
+bool run_merge_cases(uint64_t* d_lists, uint64_t* d_out, int64_t& bad) {
+    std::vector<uint64_t> lists;
+    for (const MergeCase& c : merge_cases(L)) {
+        uint64_t want[L], got[L];
+        merge_case_lists<L>(c, lists, want);
+        if (hipMemcpy(d_lists, lists.data(), lists.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return false;
+        if (ks::launch_list_merge_test(d_lists, c.nl, L, c.threads, d_out, nullptr) != hipSuccess) return false;
+        if (hipMemcpy(got, d_out, sizeof got, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (int k = 0; k < L; k++) bad += got[k] != want[k];
+    }
+    return true;
+}
+
+ks_status selftest_list_merge(int64_t* failures) {
+    constexpr int kMaxLists = 4096;
+    uint64_t *d_lists = nullptr, *d_out = nullptr;
+    int64_t bad = 0;
+    bool ok = hipMalloc(&d_lists, sizeof(uint64_t) * kMaxLists * ks::kTopLOverlap) == hipSuccess;
+    ok = ok && hipMalloc(&d_out, sizeof(uint64_t) * ks::kTopLOverlap) == hipSuccess;
+    ok = ok && run_merge_cases<ks::kTopL>(d_lists, d_out, bad);
+    if constexpr (ks::kTopLOverlap != ks::kTopL) ok = ok && run_merge_cases<ks::kTopLOverlap>(d_lists, d_out, bad);
+    if (d_lists) (void)hipFree(d_lists);
+    if (d_out) (void)hipFree(d_out);
+    if (!ok) return KS_EDEVICE;
+    *failures = bad;
+    return KS_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 ks_status ks_selftest(int32_t device, int32_t test, int64_t* failures) {
-    if (!failures || (test != KS_SELFTEST_LR_MICRO && test != KS_SELFTEST_MICRO_STATES)) return KS_EINVAL;
+    if (!failures || (test != KS_SELFTEST_LR_MICRO && test != KS_SELFTEST_MICRO_STATES && test != KS_SELFTEST_LIST_MERGE))
+        return KS_EINVAL;
     *failures = -1;
     if (hipSetDevice(device) != hipSuccess) return KS_EDEVICE;
+    if (test == KS_SELFTEST_LIST_MERGE) return selftest_list_merge(failures);
     unsigned long long* d = nullptr;
     unsigned long long h = 0;
     bool ok = hipMalloc(&d, sizeof h) == hipSuccess;

@@ -34,6 +34,7 @@ KS_SLOT_MAX = 1536    # csrc/ks_device.h kSlotMax: candidate slots whose record 
 KS_CHUNK_CIDS = 1024  # csrc/ks_chunk.hip kCid: candidates the chunk kernel numbers per batch
 KS_SELFTEST_LR_MICRO = 0
 KS_SELFTEST_MICRO_STATES = 1
+KS_SELFTEST_LIST_MERGE = 2
 # ks_selftest_eval (include/ks_engine.h): total1 column 4 * form + mode, tmax / live column 4 * form + mode
 KS_EVAL_TOTAL_COLS = 17
 KS_EVAL_PRUNE_COLS = 12
