@@ -558,7 +558,7 @@ ks_status ks_debug_counters(ks_engine* eng, int64_t* out32);
 ks_status ks_debug_invariants(ks_engine* eng, int64_t* out4);
 /* Diagnostics: the raw batch window workspace (ks_device.h WinWS; *size_out = its size, up to cap
  * bytes copied to out), and — in a -DKS_BATCH_LOG diagnostic build only (KS_EINVAL otherwise) — the
- * pod whose batch the chunk resolver records in it (tests/dev/byval_diag.py). */
+ * pod whose batch the chunk resolver records in it. */
 ks_status ks_debug_window(ks_engine* eng, void* out, int64_t cap, int64_t* size_out);
 ks_status ks_debug_watch(ks_engine* eng, int64_t pod);
 /* Device self-test of an evaluator identity the exactness argument rests on (no engine needed).

@@ -281,21 +281,10 @@ __device__ __forceinline__ void merge_final_stage(const uint64_t (*wl)[kLL], int
 // its lists in node order — the engine's own block lists by block index, their flagged subset in
 // block order, the sharded form's parts by part index (ascending block ranges, ks_shard_layout) —
 // so none keeps the extraction rounds.
-}  // namespace sq
-#ifdef KS_MCL_BYVAL
-thread_local const EngineArgs* ks_mcl_host_args = nullptr;  // (diagnostic build: set by step_body before each launch)
-#endif
-namespace sq {
 template <int kMode, int kLL, bool kDirect>
-#ifdef KS_MCL_BYVAL  // (diagnostic build only: the engine arguments by value, VERDICT r5 item 1's A/B)
-__global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs av, const uint64_t* src,
-                                                         int64_t pod_stride, int32_t nl, int64_t list_stride, int own_fb) {
-    const EngineArgs& a = av;
-#else
 __global__ __launch_bounds__(1024) void merge_cl_kernel(const EngineArgs* __restrict__ A, const uint64_t* src,
                                                          int64_t pod_stride, int32_t nl, int64_t list_stride, int own_fb) {
     const EngineArgs& a = A[0];
-#endif
     WinWS& ws = *a.sw;
     // (own_fb: a pipelined engine's rescan scanned every block locally — its own lists, not src)
     const bool own = src == nullptr || (own_fb && ws.rescan);
@@ -485,34 +474,26 @@ hipError_t launch_window_prep(const EngineArgs* d, bool head, bool spec, int slo
     return hipGetLastError();
 }
 
-hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t* lists, int64_t pod_stride,
-                           int32_t nl, int64_t list_stride, int nl_max, hipStream_t st, int L, bool own_fallback,
-                           bool direct) {
-    const int fb = own_fallback ? 1 : 0;
+hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const ListSet& in, hipStream_t st,
+                           const MergeClOpts& o) {
+    const int fb = o.own_fallback ? 1 : 0;
     static_assert(sq::kEPer * 256 >= kEMax, "E keys per thread at 256 threads");
-    const dim3 g(B), t(nl_max > 1024 ? 1024 : 256);
-#ifdef KS_MCL_BYVAL
-    if (!ks_mcl_host_args) return hipErrorInvalidValue;
-    const EngineArgs hv = *ks_mcl_host_args;  // (diagnostic: the host copy, as commit 63524d5 passed it)
-#define d hv
-#endif
-#define KS_MCL(LL, DR)                                                                                                   \
-    switch (mode) {                                                                                                  \
-        case kEvalMicro: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalMicro, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break; \
-        case kEvalTiny: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalTiny, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break;   \
-        case kEvalNarrow: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalNarrow, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break; \
-        default: hipLaunchKernelGGL((sq::merge_cl_kernel<kEvalWide, LL, DR>), g, t, 0, st, d, lists, pod_stride, nl, list_stride, fb); break;          \
-    }
-    if (L != kTopL && L != kTopLOverlap) return hipErrorInvalidValue;
-    if (direct) {
-        if (L == kTopL) { KS_MCL(kTopL, true) } else { KS_MCL(kTopLOverlap, true) }
+    const dim3 g(B), t(in.nl_max > 1024 ? 1024 : 256);
+    auto go = [&](auto ll, auto direct) {
+        with_eval_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL((sq::merge_cl_kernel<decltype(m)::value, decltype(ll)::value, decltype(direct)::value>), g, t, 0,
+                               st, d, in.lists, in.pod_stride, in.nl, in.list_stride, fb);
+        });
+    };
+    using std::integral_constant;
+    if (o.L != kTopL && o.L != kTopLOverlap) return hipErrorInvalidValue;
+    if (o.direct) {
+        if (o.L == kTopL) go(integral_constant<int, kTopL>{}, std::true_type{});
+        else go(integral_constant<int, kTopLOverlap>{}, std::true_type{});
     } else {
-        if (L == kTopL) { KS_MCL(kTopL, false) } else { KS_MCL(kTopLOverlap, false) }
+        if (o.L == kTopL) go(integral_constant<int, kTopL>{}, std::false_type{});
+        else go(integral_constant<int, kTopLOverlap>{}, std::false_type{});
     }
-#undef KS_MCL
-#ifdef KS_MCL_BYVAL
-#undef d
-#endif
     return hipGetLastError();
 }
 

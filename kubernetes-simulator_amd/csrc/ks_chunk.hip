@@ -1426,37 +1426,32 @@ static_assert(sizeof(ChShared) >= 2 * kMaxPGScan * scn::kNodes * sizeof(uint16_t
 
 // the chunk resolver proper (its window and candidate lists: launch_window_prep(head) and
 // launch_merge_cl, ks_cand.hip)
-template <bool kPrune, int kLL>
-static void launch_chunk_scan_t(const EngineArgs* d, const EngineArgs* ds, const dim3& g, int sl, int mode, hipStream_t st) {
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL((chk::chunk_scan_kernel<kEvalMicro, kPrune, kLL>), g, dim3(chk::kThreads), 0, st, d, ds, sl); break;
-        case kEvalTiny: hipLaunchKernelGGL((chk::chunk_scan_kernel<kEvalTiny, kPrune, kLL>), g, dim3(chk::kThreads), 0, st, d, ds, sl); break;
-        case kEvalNarrow: hipLaunchKernelGGL((chk::chunk_scan_kernel<kEvalNarrow, kPrune, kLL>), g, dim3(chk::kThreads), 0, st, d, ds, sl); break;
-        default: hipLaunchKernelGGL((chk::chunk_scan_kernel<kEvalWide, kPrune, kLL>), g, dim3(chk::kThreads), 0, st, d, ds, sl); break;
-    }
-}
-
 hipError_t launch_chunk_scan(const EngineArgs* d, const EngineArgs* ds, int workers, int next_slot, int mode,
                              bool prune, int L, hipStream_t st) {
     const dim3 g(1 + workers);
+    const int sl = next_slot & 1;
+    auto go = [&](auto pr, auto ll) {
+        with_eval_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL((chk::chunk_scan_kernel<decltype(m)::value, decltype(pr)::value, decltype(ll)::value>), g,
+                               dim3(chk::kThreads), 0, st, d, ds, sl);
+        });
+    };
+    using std::integral_constant;
     if (L != kTopL) {
         if (prune || L != kTopLOverlap) return hipErrorInvalidValue;
-        launch_chunk_scan_t<false, kTopLOverlap>(d, ds, g, next_slot & 1, mode, st);
+        go(std::false_type{}, integral_constant<int, kTopLOverlap>{});
     } else if (prune) {
-        launch_chunk_scan_t<true, kTopL>(d, ds, g, next_slot & 1, mode, st);
+        go(std::true_type{}, integral_constant<int, kTopL>{});
     } else {
-        launch_chunk_scan_t<false, kTopL>(d, ds, g, next_slot & 1, mode, st);
+        go(std::false_type{}, integral_constant<int, kTopL>{});
     }
     return hipGetLastError();
 }
 
 hipError_t launch_chunk_only(const EngineArgs* d, int mode, hipStream_t st) {
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL(chk::resolve_chunk_kernel<kEvalMicro>, dim3(1), dim3(chk::kThreads), 0, st, d); break;
-        case kEvalTiny: hipLaunchKernelGGL(chk::resolve_chunk_kernel<kEvalTiny>, dim3(1), dim3(chk::kThreads), 0, st, d); break;
-        case kEvalNarrow: hipLaunchKernelGGL(chk::resolve_chunk_kernel<kEvalNarrow>, dim3(1), dim3(chk::kThreads), 0, st, d); break;
-        default: hipLaunchKernelGGL(chk::resolve_chunk_kernel<kEvalWide>, dim3(1), dim3(chk::kThreads), 0, st, d); break;
-    }
+    with_eval_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(chk::resolve_chunk_kernel<decltype(m)::value>, dim3(1), dim3(chk::kThreads), 0, st, d);
+    });
     return hipGetLastError();
 }
 

@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace ks {
 
 constexpr int kWave = 64;
@@ -900,8 +902,8 @@ struct EngineArgs {
     int32_t lset;            // the set this argument record's scans write
     int32_t det_cids;        // chunk resolver: number the candidates by first appearance (sharded engines:
                              // every rank must cut its batches at the same pods), not by claim order
-    // The two-launch overlapped chain (single-shard engines on the fused overlap, ks_engine.cpp
-    // step_body): no conditional scan launch between the chunk kernel and merge_cl.  merge_cl
+    // The two-launch overlapped chain (single-shard engines on the fused overlap, ks_step.cpp
+    // batch_two_launch): no conditional scan launch between the chunk kernel and merge_cl.  merge_cl
     // computes its E keys from the node table (no staged WinWS::e_rec), and a window prep that must
     // rescan publishes an empty batch instead of flagging one (ks_prep.h).
     int32_t two_launch;
@@ -947,27 +949,58 @@ int max_pods_per_scan_wg();
 int block_nodes();
 // expiries due before each scenario's batch head
 hipError_t launch_expire_head(const EngineArgs* d, int S, hipStream_t st);
+// The evaluator variant as a compile-time constant: f(std::integral_constant<int, kEval*>) for the
+// run-time mode, so a launcher instantiates its kernel once per evaluator in one place:
+//   with_eval_mode(mode, [&](auto m) { hipLaunchKernelGGL(kernel<decltype(m)::value>, ...); });
+template <class F>
+inline void with_eval_mode(int mode, F&& f) {
+    switch (mode) {
+        case kEvalMicro: f(std::integral_constant<int, kEvalMicro>{}); break;
+        case kEvalTiny: f(std::integral_constant<int, kEvalTiny>{}); break;
+        case kEvalNarrow: f(std::integral_constant<int, kEvalNarrow>{}); break;
+        default: f(std::integral_constant<int, kEvalWide>{}); break;
+    }
+}
 // scan of each scenario's blocks [blk_lo, blk_lo + blk_n); grid x = the largest blk_n
 // key16: every total + 1 < 2^16 (scan_kernel's 16-bit key table)
-// cond: only when the window workspace's rescan flag is set (the overlap's fallback)
-// prune: the pruned-list form (the engine's lbit / lthr set, ks_scan.h)
-// L: the block lists' length (kTopL; kTopLOverlap for the overlap's single-shard engines: key16, not
-// pruned)
-// pw > 0 (one engine): a grid of at most pw workgroups, each looping over its XCD's items (the
-// pipelined engines' conditional rescan: cheap to launch when nothing is flagged)
+struct ScanOpts {
+    bool cond = false;   // only when the window workspace's rescan flag is set (the overlap's fallback)
+    bool prune = false;  // the pruned-list form (the engine's lbit / lthr set, ks_scan.h)
+    int L = kTopL;       // the block lists' length (kTopL; kTopLOverlap for the two-launch chain's engines —
+                         // key16, not pruned — and the pipelined sharded engines')
+    bool stage = false;  // (chunk class, one engine) also stage the batch's E records for merge_cl
+    int pw = 0;          // > 0 (one engine): a grid of at most pw workgroups, each looping over its XCD's items
+                         // (the pipelined engines' conditional rescan: cheap to launch when nothing is flagged)
+};
 hipError_t launch_scan(const EngineArgs* d, int S, int blk_n, int B, int PG, int mode, bool key16, hipStream_t st,
-                       bool cond = false, bool prune = false, int L = kTopL, bool stage = false, int pw = 0);
-// per scenario and pod b < batch size: exact top-L over nl sorted lists
-// lists[b*pod_stride + k*list_stride] into out (lists == nullptr: the scenario's own block lists
-// into its candidate lists)
-// nl_max: the largest nl of the launch (<= 64 / L candidates per pod: one wave per pod)
-// bits (pruned lists, ks_scan.h; nullptr: read every list): the pods' bitmaps ([B][nwl]); list k of
-// the range is block blk0 + k
-// lset_fixed >= 0: read that list set's bitmaps (not the window's WinWS::lset)
-// L: the lists' length (kTopL, or kTopLOverlap for the pipelined sharded engines' part merges)
-hipError_t launch_merge(const EngineArgs* d, int S, int B, const uint64_t* lists, int64_t pod_stride, int32_t nl,
-                        int64_t list_stride, uint64_t* out, int nl_max, hipStream_t st, const uint64_t* bits = nullptr,
-                        int32_t nwl = 0, int32_t blk0 = 0, int32_t lset_fixed = -1, int L = kTopL);
+                       const ScanOpts& o = {});
+// Which sorted lists a merge reads: pod b's list k is lists[b * pod_stride + k * list_stride], k < nl
+// (lists == nullptr: each scenario's own block lists); nl_max: the largest nl of the launch (it
+// sizes the workgroup).
+struct ListSet {
+    const uint64_t* lists = nullptr;
+    int64_t pod_stride = 0;
+    int32_t nl = 0;
+    int64_t list_stride = 0;
+    int nl_max = 0;
+};
+// the engine's (each scenario's) own block lists, nblk the largest block count of the launch
+inline ListSet own_block_lists(int nblk) { return ListSet{nullptr, 0, 0, 0, nblk}; }
+// the exchange buffer [parts][B][L]: pod b's list of part p
+inline ListSet exchanged_lists(const uint64_t* cand_all, int parts, int B, int L) {
+    return ListSet{cand_all, L, parts, (int64_t)B * L, parts};
+}
+// per scenario and pod b < batch size: exact top-L over the lists into out (own block lists: into the
+// scenario's candidate lists; <= 64 / L candidates per pod: one wave per pod)
+struct MergeOpts {
+    const uint64_t* bits = nullptr;  // pruned lists (ks_scan.h; nullptr: read every list): the pods' bitmaps
+    int32_t nwl = 0;                 // ([B][nwl]); list k of the range is block blk0 + k
+    int32_t blk0 = 0;
+    int32_t lset_fixed = -1;  // >= 0: read that list set's bitmaps (not the window's WinWS::lset)
+    int L = kTopL;            // the lists' length (kTopL, or kTopLOverlap for the pipelined sharded engines' part merges)
+};
+hipError_t launch_merge(const EngineArgs* d, int S, int B, const ListSet& in, uint64_t* out, hipStream_t st,
+                        const MergeOpts& o = {});
 // the role-split resolver (ks_kernels.hip): batches of up to max_batch_pods() pods, any cluster
 hipError_t launch_resolve(const EngineArgs* d, int S, int mode, hipStream_t st);
 // the register-table resolver (ks_resolve.hip): batches of <= small_resolver_max_batch() pods of
@@ -995,17 +1028,15 @@ hipError_t launch_chunk_scan(const EngineArgs* d, const EngineArgs* ds, int work
 hipError_t launch_window_prep(const EngineArgs* d, bool head, bool spec, int slot, hipStream_t st);
 // merge + candidate lists (ks_cand.hip): per pod the merge kernel's exact top-L over its lists, then
 // its static candidates and their slots
-// L: the lists' length (the engine's block lists, or kTopL for the sharded second merge)
-#ifdef KS_MCL_BYVAL
-extern thread_local const EngineArgs* ks_mcl_host_args;
-#endif
-// own_fallback: when the window prep flagged a rescan, read the engine's own block lists over the
-// whole cluster instead of `lists` (the pipelined engines' rescan scans every block locally)
-// direct: the two-launch chain's form (EngineArgs::two_launch) — E keys and slot records from the
-// node table and the constants table, no staged WinWS::e_rec
-hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const uint64_t* lists, int64_t pod_stride,
-                           int32_t nl, int64_t list_stride, int nl_max, hipStream_t st, int L = kTopL,
-                           bool own_fallback = false, bool direct = false);
+struct MergeClOpts {
+    int L = kTopL;              // the lists' length (the engine's block lists, or kTopL for the sharded second merge)
+    bool own_fallback = false;  // when the window prep flagged a rescan, read the engine's own block lists over
+                                // the whole cluster instead (the pipelined engines' rescan scans every block locally)
+    bool direct = false;        // the two-launch chain's form (EngineArgs::two_launch) — E keys and slot records
+                                // from the node table and the constants table, no staged WinWS::e_rec
+};
+hipError_t launch_merge_cl(const EngineArgs* d, int mode, int B, const ListSet& in, hipStream_t st,
+                           const MergeClOpts& o = {});
 struct BindSeg {
     const int32_t* node;
     const int32_t* status;

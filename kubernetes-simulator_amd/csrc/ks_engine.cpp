@@ -1,6 +1,6 @@
 // ks_engine.cpp — host side of the C-ABI declared in include/ks_engine.h: create / destroy, load,
-// submit, step, scenario groups, node sharding, debug and statistics.  The engine record is in
-// ks_host.h; the entry points that answer about a run after the fact (filter / score, usage,
+// submit, scenario groups' life cycle, node sharding, debug and statistics.  The engine record is in
+// ks_host.h; ks_step and ks_group_step are in ks_step.cpp; the entry points that answer about a run after the fact (filter / score, usage,
 // past-tick state, headroom, placement and drain previews, name-keyed lookups) are in
 // ks_queries.cpp, the device self-tests in ks_selftest.cpp.
 //
@@ -35,7 +35,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <thread>
 
 #include "ks_host.h"
 
@@ -60,28 +59,22 @@ constexpr int64_t kStageMaxPods = 4096;  // submits of up to this many pods are 
 #ifndef KS_PG_MIN_WG
 #define KS_PG_MIN_WG 2048  // scan workgroups to keep when raising the pods per workgroup
 #endif
-constexpr int kProfEv = 11;  // per launch: prep | scan | part merges | exchange | merge | resolve (+ 4 on the
-                             // pipelined chain's second stream)
-constexpr int kRescanWgs = 1024;  // the pipelined chain's conditional local rescan: workgroups
 constexpr int64_t kNever = std::numeric_limits<int64_t>::max();
-// the overlap's limit on a rank's scan blocks (step_body)
-#ifndef KS_OVERLAP_MAX_BLOCKS
-#define KS_OVERLAP_MAX_BLOCKS 256
-#endif
-constexpr int kOverlapMaxBlocks = KS_OVERLAP_MAX_BLOCKS;
 
 void engine_free(ks_engine* e);  // ks_destroy's body; a group frees its members with it
+
+}  // namespace
 
 // Pod.passedSeconds is int32(clock.Sub(start).Seconds()) (kubesim/pod/pod.go:148-153): past 2^31
 // seconds Go's float -> int32 conversion is implementation-defined (amd64: INT32_MIN, so
 // IsRunning, pod.go:67-69, would revive every finished pod).  The engine's domain: every tick at
 // which a bound pod is evaluated stays below 2^31 seconds after the run's first bind; steps,
 // submits and usage queries past it are refused with KS_ERANGE (the oracle refuses the same).
-bool in_passed_domain(const ks_engine* e, int64_t first_bind, int64_t t) {
+bool ks_host::in_passed_domain(const ks_engine* e, int64_t first_bind, int64_t t) {
     return t - first_bind <= (int64_t)INT32_MAX / e->cfg.tick_seconds;
 }
 
-ks::EngineArgs make_args(ks_engine* e) {
+ks::EngineArgs ks_host::make_args(ks_engine* e) {
     ks::EngineArgs a{};
     a.c = e->dc;
     a.s = e->s;
@@ -110,29 +103,32 @@ ks::EngineArgs make_args(ks_engine* e) {
     a.lbit = e->prune ? e->lbit : nullptr;
     a.lthr = e->prune ? e->lthr : nullptr;
     a.nwl = e->nwl;
-    a.lset = 1;  // the engine's own scans (the speculative scan's record: set 0, step_body)
+    a.lset = 1;  // the engine's own scans (the speculative scan's record: set 0, ks_step.cpp upload_args)
     a.srec = e->srec.p;
     a.ncst = e->d_ncst;
-    a.two_launch = 0;  // (step_body sets it for the chain it runs)
+    a.two_launch = 0;  // (ks_step.cpp upload_args sets it for the chain the step runs)
     a.e_lim = (e->flags & KS_ENGINE_SMALL_E) ? ks::kSmallE : ks::kEMax;
     return a;
 }
+
+namespace {
 
 // ---- host-staged submits ---------------------------------------------------------------------
 // Staged rows are applied in submission order by one scatter launch (stage_flush) or by the
 // per-tick kernel, always before the device work that reads them (stream order).  The arena is
 // reused once the launch that consumed its last segment has completed.
 hipError_t stage_copy(ks_engine* e, void* dst, const void* src, int64_t bytes);
+
+}  // namespace
+
 // The rows of exp_pos that submits rewrote since the last flush, as one segment from the host
 // mirror: per-submit rewrites overlap, and the scatter applies segments in parallel.
-hipError_t stage_xpos(ks_engine* e) {
+hipError_t ks_host::stage_xpos(ks_engine* e) {
     const int64_t lo = e->xpos_lo;
     if (lo >= e->P) return hipSuccess;
     e->xpos_lo = INT64_MAX;
     return stage_copy(e, e->exp_pos.p + lo, e->h_exp_pos.data() + lo, sizeof(int64_t) * (e->P - lo));
 }
-
-}  // namespace
 
 hipError_t ks_host::stage_flush(ks_engine* e) {
     if (hipError_t r = stage_xpos(e); r != hipSuccess) return r;
@@ -201,22 +197,21 @@ hipError_t stage_append(ks_engine* e, DVec<T>& v, const T* h, int64_t k) {
     return r;
 }
 
+}  // namespace
+
 // every total + 1 fits the scan's 16-bit key table (weights and constant values are >= 0)
-bool key16(const ks_engine* e) {
+bool ks_host::key16(const ks_engine* e) {
     return (int64_t)e->dc.const_total + 10 * ((int64_t)e->dc.w_lr + e->dc.w_ba) + 1 < (1 << 16);
 }
 
 // the small (register-table) resolver holds this engine's batches
-bool small_resolver(const ks_engine* e) {
+bool ks_host::small_resolver(const ks_engine* e) {
     return e->B <= ks::small_resolver_max_batch() && e->dc.n_nodes <= ks::small_resolver_max_nodes();
 }
 
-// Resolvers, the same binds: the role-split resolve_kernel (16 waves, ks_kernels.hip) takes any
-// engine; the register-table resolver (4 waves, ks_resolve.hip) is lighter — four per CU, so a
-// what-if group's resolvers run side by side (C4 2.29e11 against 2.16e11 evals/s with the
-// role-split kernel's half-size class); the chunk resolver (ks_chunk.hip) takes one
-// engine per launch, batches of <= kWinMaxB pods.
-// the chunk resolver: node state in 32-bit words (every scaled capacity < 2^32 - 1: the modes >=
+namespace {
+
+// the chunk resolver (the resolvers: ks_plan.h Resolver): node state in 32-bit words (every scaled capacity < 2^32 - 1: the modes >=
 // narrow, and the wide mode's decimal-SI memory class, whose capacities scale to 2^31), totals in
 // 16 bits
 bool chunk_eligible(const ks_engine* e) {
@@ -227,10 +222,12 @@ bool chunk_eligible(const ks_engine* e) {
     }
     return e->B <= ks::kWinMaxB && words && key16(e);
 }
-enum Resolver { kResolveRole = 0, kResolveSmall = 1, kResolveChunk = 4 };
+
+}  // namespace
+
 // an explicit resolver flag wins over the size class (every resolver is exact on every engine
 // its limits admit; the flags exist to test them against each other)
-int resolver_of(const ks_engine* e) {
+int ks_host::resolver_of(const ks_engine* e) {
     if ((e->flags & KS_ENGINE_CHUNK_RESOLVER) && chunk_eligible(e)) return kResolveChunk;
     if (e->flags & KS_ENGINE_ONE_POD_RESOLVER) return kResolveRole;
     // default: the register-table resolver for the small class, else the chunk resolver where
@@ -239,10 +236,14 @@ int resolver_of(const ks_engine* e) {
     if (small_resolver(e)) return kResolveSmall;
     return chunk_eligible(e) ? kResolveChunk : kResolveRole;
 }
-// (the chunk resolver runs fused into the batch chain, step_body)
-hipError_t launch_resolver(const ks::EngineArgs* d, int S, int mode, int which, hipStream_t st) {
+
+// (the chunk resolver runs fused into the batch chain, ks_step.cpp)
+hipError_t ks_host::launch_resolver(const ks::EngineArgs* d, int S, int mode, int which, hipStream_t st) {
     return which == kResolveSmall ? ks::launch_resolve_small(d, S, mode, st) : ks::launch_resolve(d, S, mode, st);
 }
+
+namespace {
+
 void update_mode(ks_engine* e) {
     int64_t m[3];
     for (int k = 0; k < 3; k++) m[k] = e->max_alloc[k] / e->scale[k];
@@ -339,6 +340,7 @@ void engine_free(ks_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->st) (void)hipStreamSynchronize(e->st);
+    if (e->st2) (void)hipStreamSynchronize(e->st2);  // (the pipelined chain's side passes read the buffers below)
     e->pods.release(); e->dur.release(); e->b_node.release(); e->b_status.release();
     e->phase_off.release(); e->cum_sec.release(); e->exp_pod.release(); e->exp_off.release();
     e->t0.release(); e->fin.release(); e->use.release(); e->expired.release(); e->exp_pos.release();
@@ -368,7 +370,6 @@ void engine_free(ks_engine* e) {
     if (e->d_spec) (void)hipFree(e->d_spec);
     if (e->d_args_spec) (void)hipFree(e->d_args_spec);
     if (e->h_args_spec) (void)hipHostFree(e->h_args_spec);
-    if (e->st2) (void)hipStreamSynchronize(e->st2);
     if (e->d_args_full) (void)hipFree(e->d_args_full);
     if (e->h_args_full) (void)hipHostFree(e->h_args_full);
     if (e->pev_m) (void)hipEventDestroy(e->pev_m);
@@ -540,7 +541,7 @@ ks_status ks_load_nodes(ks_engine* e, int64_t n, const int64_t* alloc, const uin
            (int64_t)e->blk_n * ((e->B + pg * 2 - 1) / (pg * 2)) >= KS_PG_MIN_WG)
         pg *= 2;
     e->PG = pg;
-    // (the overlap's single-shard engines may scan lists of kTopLOverlap keys: step_body)
+    // (the two-launch chain's engines may scan lists of kTopLOverlap keys: ks_plan.h plan_step)
     // (and the pipelined sharded engines': every sharded engine may)
     const int lmax = (G == 1 && e->blk_n <= kOverlapMaxBlocks) || G > 1 ? ks::kTopLOverlap : ks::kTopL;
     HIPCHK(e, hipMalloc(&e->lists, sizeof(uint64_t) * (size_t)e->B * e->nblk * lmax));
@@ -794,71 +795,6 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
 
 }  // extern "C"
 
-namespace {
-
-// ks_step, first half: the pods whose bind tick falls in (tick, tick + ticks] and the device
-// counters for them.  Returns false when there is nothing to schedule (the caller just advances
-// the tick once the step as a whole has succeeded).
-bool step_prepare(ks_engine* e, int64_t ticks, int64_t* p_hi_out) {
-    const int64_t t_end = e->tick + ticks;
-    const int64_t p_hi = std::upper_bound(e->h_bind_tick.begin() + e->done, e->h_bind_tick.end(), t_end) -
-                         e->h_bind_tick.begin();
-    *p_hi_out = p_hi;
-    e->stats = ks_step_stats{};
-    e->kstats = ks_kernel_stats{};
-    e->h_ctr[0] = e->done;
-    e->h_ctr[1] = std::max(p_hi, e->done);
-    e->h_ctr[2] = 0;
-    e->h_ctr[3] = -1;
-    e->h_ctr[4] = 0;
-    *e->h_args = make_args(e);
-    return p_hi > e->done;
-}
-
-// A device failure inside a step leaves the device counters and the binds of the step unknown:
-// the engine stops (sticky KS_EDEVICE) with its tick and binds at the last completed step.
-ks_status device_stop(ks_engine* e, ks_status r) {
-    if (r == KS_EDEVICE && e->err == KS_OK) {
-        e->err = KS_EDEVICE;
-        if (e->errmsg.empty()) e->errmsg = "device failure during a step";
-    }
-    return r;
-}
-
-// ks_step, second half: the binds [done, new_done) (node / status copied back by the caller),
-// errors as Run would return them (kubesim.go:114-120, 217-220).
-ks_status step_finish(ks_engine* e, int64_t t_end, int64_t new_done, const int32_t* node, const int32_t* status,
-                      ks_bind* out, int64_t cap, int64_t* n_out) {
-    const int64_t nb = new_done - e->done;
-    for (int64_t i = 0; i < nb && i < cap; i++) {
-        out[i].pod = e->done + i;
-        out[i].node = node[i];
-        out[i].status = status[i];
-        out[i].tick = e->h_bind_tick[e->done + i];
-    }
-    for (int64_t i = 0; i < nb; i++) {
-        e->h_node[e->done + i] = node[i];
-        e->h_status[e->done + i] = (int8_t)status[i];
-    }
-    *n_out = nb;
-    e->done = new_done;
-    if (e->h_ctr[2] != 0) {
-        const int64_t pod = e->h_ctr[3];
-        e->err = (int)e->h_ctr[2];
-        e->tick = e->h_bind_tick[pod];
-        e->done = pod + 1;  // popped from the queue, not bound
-        if (e->err == KS_ENOTFOUND)
-            fail(e, KS_ENOTFOUND, "node \"\" not found (pod %lld, tick %lld)", (long long)pod, (long long)e->tick);
-        else
-            fail(e, KS_EINVAL, "pod %lld: invalid pod key or simSpec (tick %lld)", (long long)pod, (long long)e->tick);
-        return (ks_status)e->err;
-    }
-    e->tick = t_end;
-    return KS_OK;
-}
-
-}  // namespace
-
 // Apply every not-yet-applied expiry with finish tick <= the current tick (ks_filter / ks_score
 // see the state Run's next scheduleOne would).  While the run is live the host knows them
 // exactly: every expiry attached to a pod < done has been applied (mirror_expired), an expiry
@@ -899,501 +835,7 @@ ks_status ks_host::flush_expiries(ks_engine* e) {
 
 extern "C" {
 
-static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int64_t* n_out);
-
-ks_status ks_step(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int64_t* n_out) {
-    if (!e || !n_out || ticks < 0 || cap < 0 || (cap > 0 && !out)) return KS_EINVAL;
-    *n_out = 0;
-    if (e->err) return (ks_status)e->err;
-    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
-    if (e->P > 0 && !in_passed_domain(e, e->h_bind_tick[0], e->tick + ticks))
-        return fail(e, KS_ERANGE, "step to tick %lld: more than 2^31 s after the first bind (tick %lld)",
-                    (long long)(e->tick + ticks), (long long)e->h_bind_tick[0]);
-    return device_stop(e, step_body(e, ticks, out, cap, n_out));
-}
-
-// Expiries attached to pods [lo, hi) have been applied on the device (the batch path applies
-// every expiry attached to a processed pod whose pod was bound Ok): mirror them.
-static void mirror_expired(ks_engine* e, int64_t lo, int64_t hi) {
-    for (int64_t j = lo; j < hi; j++)
-        for (int64_t u = e->h_exp_off[j]; u < e->h_exp_off[j + 1]; u++) {
-            const int32_t q = e->h_exp_pod[u];
-            if (e->h_status[q] == KS_POD_OK) e->h_expired[q] = 1;
-        }
-}
-
-// The per-tick path (ks_tick.hip): exactly one pod binds in this step — one launch does the
-// staged submits, the pod's expiries, the full-cluster evaluation, the argmax and the bind.
-// Returns false (nothing done) when the pod's expiries do not fit the launch's by-value list.
-static bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* n_out, ks_status* rc) {
-    const int64_t j = e->done;
-    ks::TickArgs a{};
-    for (int64_t u = e->h_exp_off[j]; u < e->h_exp_off[j + 1]; u++) {
-        const int32_t q = e->h_exp_pod[u];
-        if (e->h_status[q] != KS_POD_OK || e->h_expired[q]) continue;
-        if (a.n_exp == ks::kTickMaxExp) return false;
-        ks::TickExp& x = a.exp[a.n_exp++];
-        x.node = e->h_node[q];
-        x.q = q;
-        for (int k = 0; k < 3; k++) x.req[k] = e->h_pods[q].req[k];
-    }
-    *rc = KS_OK;
-    if (!e->d_tick) {
-        hipError_t r = hipMalloc(&e->d_tick, sizeof(ks::TickScratch));
-        if (r == hipSuccess) r = hipMemsetAsync(e->d_tick, 0, sizeof(ks::TickScratch), e->st);
-        if (r == hipSuccess) r = hipHostMalloc(&e->h_tick, sizeof(ks::TickOut), hipHostMallocMapped);
-        if (r == hipSuccess) r = hipHostGetDevicePointer((void**)&e->h_tick_dev, e->h_tick, 0);
-        if (r == hipSuccess && !e->stage_ev) r = hipEventCreateWithFlags(&e->stage_ev, hipEventDisableTiming);
-        if (r != hipSuccess) { *rc = fail(e, KS_EDEVICE, "per-tick path setup: %s", hipGetErrorString(r)); return true; }
-    }
-    a.c = e->dc;
-    a.s = e->s;
-    a.pod = e->h_pods[j];
-    a.j = j;
-    a.run = e->h_dur[j] > 0;
-    a.b_node = e->b_node.p;
-    a.b_status = e->b_status.p;
-    a.expired = e->expired.p;
-    a.scr = e->d_tick;
-    a.out = e->h_tick_dev;
-    if (stage_xpos(e) != hipSuccess) { *rc = fail(e, KS_EDEVICE, "per-tick path: staging failed"); return true; }
-    // the pending staged rows inline in the arguments when they fit (one pod's submit does), else
-    // one scatter launch ahead of the kernel
-    {
-        int32_t off = 0;
-        bool fits = e->nseg - e->seg_done <= ks::kTickInlSeg;
-        for (int k = e->seg_done; fits && k < e->nseg; k++) {
-            off += (int32_t)((e->segs[k].bytes + 15) / 16 * 16);
-            fits = off <= ks::kTickInl;
-        }
-        if (fits) {
-            off = 0;
-            for (int k = e->seg_done; k < e->nseg; k++) {
-                const ks::CopySeg& sg = e->segs[k];
-                std::memcpy(a.inl + off, e->stage + (sg.src - e->stage_dev), (size_t)sg.bytes);
-                a.iseg[a.n_iseg++] = ks::TickSeg{sg.dst, off, (int32_t)sg.bytes};
-                off += (int32_t)((sg.bytes + 15) / 16 * 16);
-            }
-            e->seg_done = e->nseg;
-        } else if (stage_flush(e) != hipSuccess) {
-            *rc = fail(e, KS_EDEVICE, "per-tick path: staging failed");
-            return true;
-        }
-    }
-    __atomic_store_n(&e->h_tick->code, -1, __ATOMIC_RELAXED);
-    hipError_t r = ks::launch_tick(a, e->mode, e->st);
-    if (r == hipSuccess) r = hipEventRecord(e->stage_ev, e->st);
-    // the result: poll the host-mapped code the last workgroup stores (release) after node and
-    // status — microseconds sooner than a stream synchronisation; the stream is queried now and
-    // then so that a failed launch still ends the wait
-    for (uint32_t spin = 1; r == hipSuccess; spin++) {
-        if (__atomic_load_n(&e->h_tick->code, __ATOMIC_ACQUIRE) >= 0) break;
-        if ((spin & 1023) == 0) {
-            const hipError_t q = hipStreamQuery(e->st);
-            if (q == hipSuccess) break;  // done: the code is read below
-            if (q != hipErrorNotReady) r = q;
-        }
-        __builtin_ia32_pause();
-    }
-    if (r != hipSuccess) { *rc = fail(e, KS_EDEVICE, "per-tick launch: %s", hipGetErrorString(r)); return true; }
-    ks::TickOut o;
-    o.code = __atomic_load_n(&e->h_tick->code, __ATOMIC_ACQUIRE);
-    o.node = ((volatile ks::TickOut*)e->h_tick)->node;
-    o.status = ((volatile ks::TickOut*)e->h_tick)->status;
-    for (int k = 0; k < a.n_exp; k++) e->h_expired[a.exp[k].q] = 1;
-    e->stats = ks_step_stats{};
-    e->stats.launches = 1;
-    e->h_ctr[2] = o.code;
-    e->h_ctr[3] = j;
-    if (o.code < 0) { *rc = fail(e, KS_EDEVICE, "per-tick kernel wrote no result"); return true; }
-    const int32_t node = o.node, status = o.status;
-    *rc = step_finish(e, t_end, o.code ? j : j + 1, &node, &status, out, cap, n_out);
-    e->stats.pods = *n_out;
-    return true;
-}
-
-// The batch window workspace (~0.8 MB) and the node -> E index, allocated on the first step that
-// runs a resolver using them (what-if group members never do).
-// pruned block lists for chunk-resolver engines of >= this many scan blocks (or KS_ENGINE_PRUNED_LISTS)
-#ifndef KS_PRUNE_MIN_BLOCKS
-#define KS_PRUNE_MIN_BLOCKS 1024  // (A/B: make variant NAME=noprune DEFS=-DKS_PRUNE_MIN_BLOCKS=1000000)
-#endif
-constexpr int kPruneMinBlocks = KS_PRUNE_MIN_BLOCKS;
-
-
-static ks_status ensure_window_ws(ks_engine* e) {
-    const int r = resolver_of(e);
-    e->prune = r == kResolveChunk && !e->group && (e->nblk >= kPruneMinBlocks || (e->flags & KS_ENGINE_PRUNED_LISTS));
-    if (e->prune && !e->lbit) {
-        e->nwl = (e->nblk + 63) / 64;
-        HIPCHK(e, hipMalloc(&e->lbit, sizeof(uint64_t) * 2 * (size_t)e->B * e->nwl));  // two sets (EngineArgs)
-        HIPCHK(e, hipMemsetAsync(e->lbit, 0, sizeof(uint64_t) * 2 * (size_t)e->B * e->nwl, e->st));
-        HIPCHK(e, hipMalloc(&e->lthr, sizeof(uint64_t) * 2 * ks::kThrCopies * (size_t)e->B));
-        HIPCHK(e, hipMemsetAsync(e->lthr, 0, sizeof(uint64_t) * 2 * ks::kThrCopies * (size_t)e->B, e->st));
-    }
-    if (e->d_sweep || r != kResolveChunk) return KS_OK;
-    HIPCHK(e, hipMalloc(&e->d_sweep, sizeof(ks::WinWS)));
-    HIPCHK(e, hipMemsetAsync(e->d_sweep, 0, sizeof(ks::WinWS), e->st));
-    HIPCHK(e, hipMalloc(&e->d_eidx, sizeof(int32_t) * e->n_pad));
-    HIPCHK(e, hipMemsetAsync(e->d_eidx, 0xFF, sizeof(int32_t) * e->n_pad, e->st));
-    HIPCHK(e, hipMalloc(&e->d_nslot, sizeof(int32_t) * e->n_pad));
-    HIPCHK(e, hipMemsetAsync(e->d_nslot, 0xFF, sizeof(int32_t) * e->n_pad, e->st));
-    HIPCHK(e, hipMalloc(&e->d_first, sizeof(int32_t) * e->n_pad));
-    HIPCHK(e, hipMemsetAsync(e->d_first, 0x7F, sizeof(int32_t) * e->n_pad, e->st));  // kNoFirst
-    HIPCHK(e, hipMalloc(&e->d_spec, 2 * ks::kSpecStride * sizeof(int64_t)));
-    HIPCHK(e, hipMemsetAsync(e->d_spec, 0, 2 * ks::kSpecStride * sizeof(int64_t), e->st));
-    HIPCHK(e, hipMalloc(&e->d_args_spec, 2 * sizeof(ks::EngineArgs)));
-    HIPCHK(e, hipHostMalloc(&e->h_args_spec, 2 * sizeof(ks::EngineArgs), hipHostMallocDefault));
-    {   // the fused scan's workgroups: one per CU beside the resolver's (the resolver's LDS
-        // footprint allows one workgroup per CU)
-        int cus = 0;
-        HIPCHK(e, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
-#ifndef KS_SCAN_WORKERS_DIV
-#define KS_SCAN_WORKERS_DIV 1  // (A/B builds: make variant DEFS=-DKS_SCAN_WORKERS_DIV=2)
-#endif
-        e->scan_workers = std::max(15, cus / KS_SCAN_WORKERS_DIV - 1);  // (>= 15: every XCD deals its share to at least one)
-    }
-    if (e->world * e->vsh > 1) {  // the pipelined sharded chain's stream, events and full-range arguments
-        HIPCHK(e, hipStreamCreateWithFlags(&e->st2, hipStreamNonBlocking));
-        HIPCHK(e, hipEventCreateWithFlags(&e->pev_m, hipEventDisableTiming));
-        HIPCHK(e, hipEventCreateWithFlags(&e->pev_x, hipEventDisableTiming));
-        HIPCHK(e, hipMalloc(&e->d_args_full, sizeof(ks::EngineArgs)));
-        HIPCHK(e, hipHostMalloc(&e->h_args_full, sizeof(ks::EngineArgs), hipHostMallocDefault));
-    }
-    return KS_OK;
-}
-
-// This rank's per-part merges of its block lists into its parts' slices of cand_all (a: the
-// argument record whose counters name the batch; lset_fixed >= 0: that list set's bitmaps)
-static hipError_t part_merges(ks_engine* e, const ks::EngineArgs* a, hipStream_t s, int lset_fixed) {
-    const int64_t L = e->L, BL = (int64_t)e->B * L;
-    for (int v = 0; v < e->vsh; v++) {
-        const int p = e->rank * e->vsh + v;
-        const int nlp = e->part_lo[p + 1] - e->part_lo[p];
-        const hipError_t r = ks::launch_merge(a, 1, e->B, e->lists + (int64_t)e->part_lo[p] * L, (int64_t)e->nblk * L, nlp,
-                                              L, e->cand_all + p * BL, nlp, s, e->prune ? e->lbit : nullptr, e->nwl,
-                                              e->part_lo[p], lset_fixed, (int)L);
-        if (r != hipSuccess) return r;
-    }
-    return hipSuccess;
-}
-
-// The all-gather of every rank's parts of cand_all on stream s: RCCL, or the host callback
-static ks_status exchange(ks_engine* e, hipStream_t s) {
-    const int64_t BL = (int64_t)e->B * e->L;
-    if (e->comm) {
-        const ncclResult_t nr = ncclAllGather(e->cand_all + (int64_t)e->rank * e->vsh * BL, e->cand_all,
-                                              (size_t)e->vsh * BL, ncclUint64, e->comm, s);
-        if (nr != ncclSuccess) return fail(e, KS_EDEVICE, "ncclAllGather: %s", ncclGetErrorString(nr));
-    } else if (e->xfn) {  // host exchange: this rank's parts out, every rank's parts back
-        const int64_t slice = (int64_t)e->vsh * BL, off = (int64_t)e->rank * slice;
-        HIPCHK(e, hipMemcpyAsync(e->h_xbuf + off, e->cand_all + off, sizeof(uint64_t) * slice, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipStreamSynchronize(s));
-        const ks_status xr = e->xfn(e->xuser, e->rank, e->world, e->h_xbuf, (int64_t)sizeof(uint64_t) * slice);
-        if (xr != KS_OK) return fail(e, KS_EDEVICE, "host exchange failed (%d)", (int)xr);
-        HIPCHK(e, hipMemcpyAsync(e->cand_all, e->h_xbuf, sizeof(uint64_t) * slice * e->world, hipMemcpyHostToDevice, s));
-    }
-    return KS_OK;
-}
-
-// One batch of the pipelined sharded chain (step_body).  Main stream: [the pass's first batch: window
-// prep, scan of this rank's blocks, part merges, exchange | later batches: wait for the second
-// stream's exchange, the conditional local rescan (E overflow only) with the E staging] -> merge_cl
-// -> the resolve with the next batch's window in its tail.  Second stream, once merge_cl has read
-// the lists and cleared the speculative set: the next batch's speculative scan of this rank's blocks
-// (the counters this batch's window prep wrote), its part merges and the exchange — beside the
-// resolve.  cand_all and the block lists are single-buffered: each side pass starts after the
-// merge_cl that read the previous one.
-static ks_status pipe_batch(ks_engine* e, int64_t b, int64_t nbat, hipEvent_t* ev) {
-    hipStream_t st = e->st, s2 = e->st2;
-    const ks::EngineArgs* d = e->d_args;
-    const int G = e->world * e->vsh;
-    const int64_t L = e->L, BL = (int64_t)e->B * L;  // (kTopLOverlap: step_body)
-    const bool first = b == 0, more = b + 1 < nbat;
-    if (ev[0]) HIPCHK(e, hipEventRecord(ev[0], st));
-    if (first) {
-        HIPCHK(e, ks::launch_window_prep(d, true, false, (int)(b & 1), st));
-        if (ev[1]) HIPCHK(e, hipEventRecord(ev[1], st));
-        HIPCHK(e, ks::launch_scan(d, 1, e->blk_n, e->B, e->PG, e->mode, key16(e), st, false, e->prune, (int)L, true));
-        if (ev[2]) HIPCHK(e, hipEventRecord(ev[2], st));
-        HIPCHK(e, part_merges(e, d, st, -1));
-        if (ev[5]) HIPCHK(e, hipEventRecord(ev[5], st));
-        if (ks_status r = exchange(e, st); r != KS_OK) return r;
-        if (ev[6]) HIPCHK(e, hipEventRecord(ev[6], st));
-    } else {
-        HIPCHK(e, hipStreamWaitEvent(st, e->pev_x, 0));
-        if (ev[1]) HIPCHK(e, hipEventRecord(ev[1], st));
-        HIPCHK(e, ks::launch_scan(e->d_args_full, 1, e->nblk, e->B, e->PG, e->mode, key16(e), st, true, e->prune, (int)L,
-                                  true, kRescanWgs));
-        if (ev[2]) HIPCHK(e, hipEventRecord(ev[2], st));
-        if (ev[5]) HIPCHK(e, hipEventRecord(ev[5], st));
-        if (ev[6]) HIPCHK(e, hipEventRecord(ev[6], st));
-    }
-    HIPCHK(e, ks::launch_merge_cl(d, e->mode, e->B, e->cand_all, L, G, BL, G, st, (int)L, !first));
-    if (ev[3]) HIPCHK(e, hipEventRecord(ev[3], st));
-    if (more) {
-        HIPCHK(e, hipEventRecord(e->pev_m, st));
-        // (no scan workers: the resolver and the next window only; the list length is the workers')
-        HIPCHK(e, ks::launch_chunk_scan(d, e->d_args_spec + (b & 1), 0, (int)((b + 1) & 1), e->mode, e->prune, ks::kTopL, st));
-    } else {
-        HIPCHK(e, ks::launch_chunk_only(d, e->mode, st));
-    }
-    if (ev[4]) HIPCHK(e, hipEventRecord(ev[4], st));
-    if (more) {
-        const ks::EngineArgs* ds = e->d_args_spec + (b & 1);
-        HIPCHK(e, hipStreamWaitEvent(s2, e->pev_m, 0));
-        if (ev[7]) HIPCHK(e, hipEventRecord(ev[7], s2));
-        HIPCHK(e, ks::launch_scan(ds, 1, e->blk_n, e->B, e->PG, e->mode, key16(e), s2, false, e->prune, (int)L, false));
-        if (ev[8]) HIPCHK(e, hipEventRecord(ev[8], s2));
-        HIPCHK(e, part_merges(e, ds, s2, 0));
-        if (ev[9]) HIPCHK(e, hipEventRecord(ev[9], s2));
-        if (ks_status r = exchange(e, s2); r != KS_OK) return r;
-        if (ev[10]) HIPCHK(e, hipEventRecord(ev[10], s2));
-        HIPCHK(e, hipEventRecord(e->pev_x, s2));
-    }
-    return KS_OK;
-}
-
-static ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int64_t* n_out) {
-    HIPCHK(e, hipSetDevice(e->device));
-    if (ks_status r = ensure_window_ws(e); r != KS_OK) return r;
-    const int64_t t_end = e->tick + ticks;
-    int64_t p_hi = 0;
-    if (!step_prepare(e, ticks, &p_hi)) {
-        e->tick = t_end;
-        return KS_OK;
-    }
-    // (an explicitly forced resolver keeps one-pod steps on that resolver: its A/B tests)
-    if (p_hi == e->done + 1 && !e->group && e->world * e->vsh == 1 && e->n > 0 && !e->profiling &&
-        !(e->flags & (KS_ENGINE_CHUNK_RESOLVER | KS_ENGINE_ONE_POD_RESOLVER))) {
-        ks_status rc = KS_OK;
-        if (tick_step(e, t_end, out, cap, n_out, &rc)) return rc;
-    }
-    const int64_t done0 = e->done;
-    HIPCHK(e, stage_flush(e));
-    hipStream_t st = e->st;
-    const int which = resolver_of(e);
-    const bool fused = which == kResolveChunk;
-    HIPCHK(e, hipMemcpyAsync(e->d_ctr, e->h_ctr, 5 * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    // the overlap (chunk class, 16-bit keys, not profiling): batch b + 1's scan fused into batch b's
-    // chunk kernel, over the pods after batch b (the speculative counters window prep writes) and
-    // this rank's scan blocks.  Sharded engines too: every rank's lists are speculative alike and its
-    // touched nodes (the same on every rank: the resolvers are identical) join E; the exchange runs
-    // every batch whether or not window prep flagged a rescan, so every rank issues the same
-    // collectives.  In the fused kernel the scan runs one workgroup per CU (the resolver's LDS fixes
-    // the kernel's), ~3 blocks per us: ranks scanning more than kOverlapMaxBlocks blocks keep the
-    // plain chain, whose scan runs at full occupancy (C5 on 8 ranks, 512 blocks each: fused kernel
-    // 129 us against a 78 us resolve + a 37 us scan; C3: 196 blocks hide under the resolve)
-    // (profiling keeps it: the per-kernel events bracket the same launches)
-    const bool overlap = fused && e->overlap && e->d_args_spec && key16(e) && e->blk_n <= kOverlapMaxBlocks;
-    // The pipelined sharded chain (round 6; sharded engines the fused overlap does not take, e.g. C5 on
-    // 8 ranks, 512 blocks each): batch b + 1's speculative scan of this rank's blocks, its per-part
-    // merges and the exchange run on a second stream beside batch b's resolve, so only the resolve
-    // (with the next window in its tail), the E staging and merge_cl stay on the critical path.  A
-    // batch that starts inside its predecessor (an early stop) reuses its merged lists (ks_prep.h),
-    // so the exchanged lists always serve; when E overflows, the conditional rescan scans every block
-    // locally (no second exchange: every rank holds the whole table) and merge_cl merges those.
-    const bool pipe = fused && !overlap && e->overlap && e->st2 && e->world * e->vsh > 1;
-    // The two-launch chain (single-shard engines on the fused overlap): an overlapped batch is merge_cl
-    // -> chunk kernel, with no conditional scan launch in front (a launch that scanned 0-4 times per
-    // 32,768-pod step at C3 and otherwise only staged E records).  merge_cl reads its E nodes from
-    // the node table and the constants table filled here (after the stage flush, and after any
-    // rescale: ks_submit_pods runs it); a window prep that must rescan publishes an empty batch
-    // instead, whose round's fused scan lists the same pods again (ks_prep.h).
-    const bool two = overlap && e->world * e->vsh == 1;
-    e->h_args->two_launch = two ? 1 : 0;
-    HIPCHK(e, hipMemcpyAsync(e->d_args, e->h_args, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
-    if (two) HIPCHK(e, ks::launch_node_consts(e->s, e->n_pad, e->d_ncst, st));
-    // the overlap's single-shard lists are longer (ks_device.h kTopLOverlap, ks_cand.hip cand_list)
-    // (and the pipelined chain's: its speculative lists go stale like the overlap's)
-    e->L = (overlap && e->world * e->vsh == 1 && !e->prune) || pipe ? ks::kTopLOverlap : ks::kTopL;
-    if (pipe) {
-        *e->h_args_full = *e->h_args;
-        e->h_args_full->blk_lo = 0;
-        e->h_args_full->blk_n = e->nblk;
-        HIPCHK(e, hipMemcpyAsync(e->d_args_full, e->h_args_full, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
-    }
-    if (overlap || pipe) {
-        for (int k = 0; k < 2; k++) {
-            e->h_args_spec[k] = *e->h_args;
-            e->h_args_spec[k].ctr = e->d_spec + ks::kSpecStride * k;
-            e->h_args_spec[k].lset = 0;  // pruned lists: the speculative set
-        }
-        HIPCHK(e, hipMemcpyAsync(e->d_args_spec, e->h_args_spec, 2 * sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(e, hipEventRecord(e->ev[0], st));
-    const ks::EngineArgs* d = e->d_args;
-#ifdef KS_MCL_BYVAL
-    ks::ks_mcl_host_args = e->h_args;  // (diagnostic build only; one engine per thread at a time is not guaranteed)
-#endif
-    int64_t start = e->done;
-    int64_t launches = 0;
-    double scan_ms = 0, res_ms = 0;
-    ks_kernel_stats ks{};
-    std::vector<uint8_t> kind;  // per launch: 1 window prep launched, 2 fused resolve, 16 scan launched
-    while (true) {
-        const int64_t nbat = (p_hi - start + e->B - 1) / e->B;
-        for (int64_t b = 0; b < nbat; b++) {
-            // profiling: events around the scan kernel alone and the resolve kernel alone (on
-            // the engine's stream), so their averages agree with rocprofv3's kernel trace
-            hipEvent_t ev[kProfEv] = {};
-            if (e->profiling) {
-                while ((int64_t)e->prof_ev.size() < kProfEv * (launches + 1)) {
-                    hipEvent_t x;
-                    HIPCHK(e, hipEventCreate(&x));
-                    e->prof_ev.push_back(x);
-                }
-                for (int k = 0; k < kProfEv; k++) ev[k] = e->prof_ev[kProfEv * launches + k];
-            }
-            if (pipe) {
-                ks_status pr = pipe_batch(e, b, nbat, ev);
-                if (pr != KS_OK) return pr;
-                if (e->profiling) kind.push_back((uint8_t)(8 | (b == 0 ? 1 : 0) | (b + 1 < nbat ? 2 : 0)));
-                launches++;
-                continue;
-            }
-            // the chunk resolver's chain is fused: window prep with the head's expiries, the scan,
-            // merge with the candidate lists, the resolver (four launches per batch)
-            // overlap: batch b > 0 of this pass takes the speculative scan's lists (a conditional
-            // rescan when they do not fit, ks_cand.hip window_prep_kernel)
-            const bool spec = overlap && b > 0;
-            if (ev[0]) HIPCHK(e, hipEventRecord(ev[0], st));
-            // (an overlapped batch's window was computed by the previous chunk kernel after its commit)
-            if (!spec) HIPCHK(e, fused ? ks::launch_window_prep(d, true, false, (int)(b & 1), st) : ks::launch_expire_head(d, 1, st));
-            if (ev[1]) HIPCHK(e, hipEventRecord(ev[1], st));
-            // (chunk class: the scan launch also stages the batch's E records for merge_cl; the
-            // two-launch chain has neither the staging nor an overlapped batch's conditional scan)
-            const bool scan = !(two && spec);
-            if (scan) HIPCHK(e, ks::launch_scan(d, 1, e->blk_n, e->B, e->PG, e->mode, key16(e), st, spec, e->prune, e->L, fused && !two));
-            if (ev[2]) HIPCHK(e, hipEventRecord(ev[2], st));
-            const int G = e->world * e->vsh;
-            hipEvent_t evx[2] = {ev[5], ev[6]};  // part merges | exchange | merge (sharded engines)
-            const int64_t L = ks::kTopL, BL = (int64_t)e->B * L;
-            if (G == 1) {
-                HIPCHK(e, fused ? ks::launch_merge_cl(d, e->mode, e->B, nullptr, 0, 0, 0, e->nblk, st, e->L, false, two)
-                                : ks::launch_merge(d, 1, e->B, nullptr, 0, 0, 0, nullptr, e->nblk, st));
-            } else {
-                HIPCHK(e, part_merges(e, d, st, -1));
-                if (evx[0]) HIPCHK(e, hipEventRecord(evx[0], st));
-                if (ks_status r = exchange(e, st); r != KS_OK) return r;
-                if (evx[1]) HIPCHK(e, hipEventRecord(evx[1], st));
-                HIPCHK(e, fused ? ks::launch_merge_cl(d, e->mode, e->B, e->cand_all, L, G, BL, G, st)
-                                : ks::launch_merge(d, 1, e->B, e->cand_all, L, G, BL, e->cand, G, st));
-            }
-            if (ev[3]) HIPCHK(e, hipEventRecord(ev[3], st));
-            if (overlap && b + 1 < nbat)  // the resolver with the next batch's scan beside it
-                HIPCHK(e, ks::launch_chunk_scan(d, e->d_args_spec + (b & 1), e->scan_workers, (int)((b + 1) & 1), e->mode,
-                                                e->prune, e->L, st));
-            else
-                HIPCHK(e, fused ? ks::launch_chunk_only(d, e->mode, st) : launch_resolver(d, 1, e->mode, which, st));
-            if (ev[4]) HIPCHK(e, hipEventRecord(ev[4], st));
-            if (e->profiling) kind.push_back((uint8_t)((!spec ? 1 : 0) | (overlap && b + 1 < nbat ? 2 : 0) | (G > 1 ? 4 : 0) | (scan ? 16 : 0)));
-            launches++;
-        }
-        HIPCHK(e, hipMemcpyAsync(e->h_ctr, e->d_ctr, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipStreamSynchronize(st));
-        const int64_t prev = start;
-        start = e->h_ctr[0];
-        if (e->h_ctr[2] != 0 || start >= p_hi) break;
-        // every launch commits at least its first pod (resolve_kernel): no progress is a bug
-        if (start <= prev) return fail(e, KS_EDEVICE, "scheduling made no progress at pod %lld", (long long)start);
-    }
-    HIPCHK(e, hipEventRecord(e->ev[1], st));
-    const int64_t new_done = start;
-    const int64_t nb = new_done - e->done;
-    std::vector<int32_t> node(nb), status(nb);
-    if (nb) {
-        HIPCHK(e, hipMemcpyAsync(node.data(), e->b_node.p + e->done, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(status.data(), e->b_status.p + e->done, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(e, hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
-    double other_ms = 0;
-    if (e->profiling) {
-        for (int64_t l = 0; l < launches; l++) {
-            float t[4] = {};
-            hipEvent_t* E = &e->prof_ev[kProfEv * l];
-            if (kind[l] & 8) {  // pipelined: [0,1) exchange wait, [1,2) scan / rescan + staging, [2,5) part merges,
-                                // [5,6) exchange (the pass's first batch), [6,3) merge_cl, [3,4) resolve; side [7..10]
-                float w = 0, sc = 0, pm = 0, xc = 0, mg = 0, rs = 0;
-                (void)hipEventElapsedTime(&w, E[0], E[1]);
-                (void)hipEventElapsedTime(&sc, E[1], E[2]);
-                (void)hipEventElapsedTime(&pm, E[2], E[5]);
-                (void)hipEventElapsedTime(&xc, E[5], E[6]);
-                (void)hipEventElapsedTime(&mg, E[6], E[3]);
-                (void)hipEventElapsedTime(&rs, E[3], E[4]);
-                ks.wait_ms += w;
-                ks.scan_ms += sc; ks.scan_n += 1; scan_ms += sc;
-                ks.merge_ms += pm + xc + mg; ks.merge_n += 1; other_ms += pm + xc + mg + w;
-                if (kind[l] & 1) { ks.part_ms += pm; ks.xchg_ms += xc; ks.xchg_n += 1; }
-                if (kind[l] & 2) { ks.fused_ms += rs; ks.fused_n += 1; } else { ks.resolve_ms += rs; ks.resolve_n += 1; }
-                res_ms += rs;
-                if (kind[l] & 2) {
-                    float a0 = 0, a1 = 0, a2 = 0;
-                    (void)hipEventElapsedTime(&a0, E[7], E[8]);
-                    (void)hipEventElapsedTime(&a1, E[8], E[9]);
-                    (void)hipEventElapsedTime(&a2, E[9], E[10]);
-                    ks.side_scan_ms += a0; ks.side_part_ms += a1; ks.side_xchg_ms += a2; ks.side_n += 1;
-                }
-                continue;
-            }
-            for (int k = 0; k < 4; k++) (void)hipEventElapsedTime(&t[k], E[k], E[k + 1]);
-            if (kind[l] & 4) {  // sharded: [2, 5) part merges, [5, 6) exchange, [6, 3) merge
-                float pm = 0, xc = 0;
-                (void)hipEventElapsedTime(&pm, E[2], E[5]);
-                (void)hipEventElapsedTime(&xc, E[5], E[6]);
-                ks.part_ms += pm; ks.xchg_ms += xc;
-                ks.xchg_n += 1;
-            }
-            other_ms += t[0] + t[2];
-            scan_ms += t[1];
-            res_ms += t[3];
-            ks.prep_ms += t[0]; ks.prep_n += kind[l] & 1;
-            ks.scan_ms += t[1]; ks.scan_n += kind[l] & 16 ? 1 : 0;  // (scan launches actually made)
-            ks.merge_ms += t[2]; ks.merge_n += 1;
-            if (kind[l] & 2) { ks.fused_ms += t[3]; ks.fused_n += 1; }
-            else { ks.resolve_ms += t[3]; ks.resolve_n += 1; }
-        }
-    }
-    e->kstats = ks;
-    e->stats.step_ms = ms;
-    e->stats.scan_ms = scan_ms;
-    e->stats.resolve_ms = res_ms;
-    e->stats.other_ms = other_ms;
-    e->stats.launches = launches;
-    e->stats.pods = nb;
-    const ks_status rc = step_finish(e, t_end, new_done, node.data(), status.data(), out, cap, n_out);
-    if (rc == KS_OK) mirror_expired(e, done0, e->done);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Scenario groups (BASELINE.json configs[3]): independent what-if clusters stepped together, one
-// launch per kernel for all of them (scenario = a grid dimension; one resolve workgroup each).
-// ---------------------------------------------------------------------------------------------
-struct ks_group {
-    int device = 0;
-    int cap = 0;
-    hipStream_t st = nullptr;
-    std::vector<ks_engine*> engs;
-    int64_t* d_ctr = nullptr;           // [cap][32]
-    int64_t* h_ctr = nullptr;           // pinned
-    ks::EngineArgs* d_args = nullptr;   // [cap]
-    ks::EngineArgs* h_args = nullptr;   // pinned
-    ks::BindSeg* d_seg = nullptr;       // [cap]
-    ks::BindSeg* h_seg = nullptr;       // pinned
-    int32_t* d_out = nullptr;           // packed binds: node, then status
-    int32_t* h_out = nullptr;           // pinned mirror of d_out
-    int64_t out_cap = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // the second half of the scenarios runs its batch rounds on its own stream: one half's
-    // latency-bound resolvers then share the GPU with the other half's throughput-bound scans
-    hipStream_t st2 = nullptr;
-    hipEvent_t xev = nullptr;  // argument upload done (st -> st2)
-    std::string errmsg;
-};
-
+// Scenario groups (struct ks_group: ks_host.h; ks_group_step: ks_step.cpp)
 ks_status ks_group_create(int32_t device, int32_t max_scenarios, ks_group** out) {
     if (!out || max_scenarios < 1 || max_scenarios > 65535) return KS_EINVAL;
     *out = nullptr;
@@ -1470,191 +912,6 @@ ks_status ks_group_add(ks_group* g, const ks_config* cfg, ks_engine** out) {
 
 int32_t ks_group_size(const ks_group* g) { return g ? (int32_t)g->engs.size() : -1; }
 
-// groups of at least this many scenarios run as two halves on two streams
-#ifndef KS_GROUP_SPLIT_MIN
-#define KS_GROUP_SPLIT_MIN 64
-#endif
-constexpr int kGroupSplitMin = KS_GROUP_SPLIT_MIN;
-
-ks_status ks_group_step(ks_group* g, int64_t ticks, ks_bind* out, int64_t cap, int64_t* n_out, int32_t* status_out,
-                        ks_step_stats* stats) {
-    if (!g || !n_out || !status_out || ticks < 0 || cap < 0) return KS_EINVAL;
-    const int S = (int)g->engs.size();
-    if (S == 0) return KS_OK;
-    if (hipSetDevice(g->device) != hipSuccess) return KS_EDEVICE;
-    std::vector<int64_t> p_hi(S, 0), t_end(S, 0);
-    std::vector<char> live(S, 0), part(S, 0);  // part: takes part in this step
-    int mode = ks::kEvalMicro, blk_n = 0, B = 0;  // B: the largest member batch (grid size)
-    bool k16 = true, small = true;
-    for (ks_engine* e : g->engs) {
-        B = std::max(B, e->B);
-        k16 = k16 && key16(e);
-        small = small && small_resolver(e);
-    }
-    // (the chunk resolver takes one engine per launch: not in groups)
-    const int which = small ? kResolveSmall : kResolveRole;
-    int64_t blocks = 0;
-    for (int i = 0; i < S; i++) {
-        ks_engine* e = g->engs[i];
-        n_out[i] = 0;
-        status_out[i] = KS_OK;
-        const bool out_of_domain = e->P > 0 && !in_passed_domain(e, e->h_bind_tick[0], e->tick + ticks);
-        if (e->err || !e->nodes_loaded || e->world * e->vsh != 1 || out_of_domain) {
-            status_out[i] = e->err ? e->err : out_of_domain ? KS_ERANGE : KS_EINVAL;
-            if (!e->err) {
-                if (out_of_domain) fail(e, KS_ERANGE, "step past 2^31 s after the first bind");
-                else fail(e, KS_EINVAL, "group step needs loaded, unsharded nodes");
-            }
-            e->h_ctr[0] = e->h_ctr[1] = e->done;
-            e->h_ctr[2] = 0;
-            *e->h_args = e->nodes_loaded ? make_args(e) : ks::EngineArgs{};
-            e->h_args->ctr = e->d_ctr;
-            e->h_args->blk_n = 0;
-            continue;
-        }
-        t_end[i] = e->tick + ticks;
-        part[i] = 1;
-        live[i] = step_prepare(e, ticks, &p_hi[i]);
-        // the widest evaluator any scenario needs (each is exact on every narrower domain)
-        mode = std::min(mode, e->mode);
-        blk_n = std::max(blk_n, e->blk_n);
-        blocks += e->blk_n;
-    }
-    // pods per scan workgroup for the whole group: the most node-record reuse that still leaves
-    // >= ~2048 workgroups per scan
-    int pg = 1;
-    while (pg < ks::max_pods_per_scan_wg() && pg < B && blocks * ((B + pg * 2 - 1) / (pg * 2)) >= 2048) pg *= 2;
-    for (int i = 0; i < S; i++) g->h_args[i].PG = pg;
-    hipStream_t st = g->st;
-    auto dev = [&](hipError_t r) { return r == hipSuccess; };
-    // a device failure leaves every participating member's step unknown: sticky KS_EDEVICE, ticks
-    // and binds stay at the last completed step
-    auto dev_fail = [&](const char* what) {
-        g->errmsg = what;
-        for (int i = 0; i < S; i++)
-            if (part[i]) {
-                ks_engine* e = g->engs[i];
-                e->err = KS_EDEVICE;
-                e->errmsg = what;
-                status_out[i] = KS_EDEVICE;
-            }
-        return KS_EDEVICE;
-    };
-    if (!dev(hipMemcpyAsync(g->d_ctr, g->h_ctr, sizeof(int64_t) * 32 * S, hipMemcpyHostToDevice, st)) ||
-        !dev(hipMemcpyAsync(g->d_args, g->h_args, sizeof(ks::EngineArgs) * S, hipMemcpyHostToDevice, st)) ||
-        !dev(hipEventRecord(g->ev[0], st)))
-        return dev_fail("group step: argument upload failed");
-    std::vector<int64_t> start(S);
-    for (int i = 0; i < S; i++) start[i] = g->engs[i]->done;
-    int64_t launches = 0;
-    // scenario halves [h_lo[h], h_lo[h + 1]) on streams st / st2 (one stream for small groups)
-    const int nh = S >= kGroupSplitMin ? 2 : 1;
-    const int h_lo[3] = {0, nh == 2 ? S / 2 : S, S};
-    hipStream_t hst[2] = {st, g->st2};
-    if (nh == 2 && (!dev(hipEventRecord(g->xev, st)) || !dev(hipStreamWaitEvent(g->st2, g->xev, 0))))
-        return dev_fail("group step: stream ordering failed");
-    while (true) {
-        int64_t nbat[2] = {0, 0};
-        for (int h = 0; h < nh; h++)
-            for (int i = h_lo[h]; i < h_lo[h + 1]; i++)
-                if (live[i]) nbat[h] = std::max(nbat[h], (p_hi[i] - start[i] + B - 1) / B);
-        if (nbat[0] == 0 && nbat[1] == 0) break;
-        // the halves' rounds issued alternately: independent scenarios, no ordering between them
-        // (a token that made the halves' scans take turns measured no better)
-        for (int64_t b = 0; b < std::max(nbat[0], nbat[1]); b++) {
-            for (int h = 0; h < nh; h++) {
-                if (b >= nbat[h]) continue;
-                const ks::EngineArgs* d = g->d_args + h_lo[h];
-                const int Sh = h_lo[h + 1] - h_lo[h];
-                if (!dev(ks::launch_expire_head(d, Sh, hst[h])) ||
-                    !dev(ks::launch_scan(d, Sh, blk_n, B, pg, mode, k16, hst[h])) ||
-                    !dev(ks::launch_merge(d, Sh, B, nullptr, 0, 0, 0, nullptr, blk_n, hst[h])) ||
-                    !dev(launch_resolver(d, Sh, mode, which, hst[h])))
-                    return dev_fail("group step: kernel launch failed");
-            }
-            launches++;
-        }
-        for (int h = 0; h < nh; h++) {
-            const int64_t lo = h_lo[h], n = h_lo[h + 1] - h_lo[h];
-            if (n && !dev(hipMemcpyAsync(g->h_ctr + 32 * lo, g->d_ctr + 32 * lo, sizeof(int64_t) * 32 * n,
-                                         hipMemcpyDeviceToHost, hst[h])))
-                return dev_fail("group step: device synchronisation failed");
-        }
-        for (int h = 0; h < nh; h++)
-            if (!dev(hipStreamSynchronize(hst[h]))) return dev_fail("group step: device synchronisation failed");
-        for (int i = 0; i < S; i++) {
-            if (!live[i]) continue;
-            ks_engine* e = g->engs[i];
-            const int64_t prev = start[i];
-            start[i] = e->h_ctr[0];
-            if (e->h_ctr[2] != 0 || start[i] >= p_hi[i]) live[i] = 0;
-            else if (start[i] <= prev)  // every launch commits at least its first pod
-                return dev_fail("group step: scheduling made no progress");
-        }
-    }
-    // binds back: one gather into a packed buffer, one copy
-    int64_t total = 0, max_n = 0;
-    for (int i = 0; i < S; i++) {
-        ks_engine* e = g->engs[i];
-        const int64_t nb = status_out[i] == KS_OK && part[i] ? start[i] - e->done : 0;
-        g->h_seg[i] = ks::BindSeg{e->b_node.p, e->b_status.p, e->done, std::max<int64_t>(nb, 0), total};
-        total += std::max<int64_t>(nb, 0);
-        max_n = std::max(max_n, nb);
-    }
-    if (total > g->out_cap) {
-        if (g->d_out) (void)hipFree(g->d_out);
-        if (g->h_out) (void)hipHostFree(g->h_out);
-        g->d_out = g->h_out = nullptr;
-        g->out_cap = std::max<int64_t>(total, 2 * g->out_cap);
-        if (!dev(hipMalloc(&g->d_out, sizeof(int32_t) * 2 * g->out_cap)) ||
-            !dev(hipHostMalloc(&g->h_out, sizeof(int32_t) * 2 * g->out_cap, hipHostMallocDefault))) {
-            g->out_cap = 0;
-            return dev_fail("group step: bind buffer allocation failed");
-        }
-    }
-    if (total) {
-        if (!dev(hipMemcpyAsync(g->d_seg, g->h_seg, sizeof(ks::BindSeg) * S, hipMemcpyHostToDevice, st)) ||
-            !dev(ks::launch_gather_binds(g->d_seg, S, max_n, g->d_out, g->d_out + total, st)) ||
-            !dev(hipMemcpyAsync(g->h_out, g->d_out, sizeof(int32_t) * 2 * total, hipMemcpyDeviceToHost, st)))
-            return dev_fail("group step: bind copy failed");
-    }
-    if (!dev(hipEventRecord(g->ev[1], st)) || !dev(hipStreamSynchronize(st)))
-        return dev_fail("group step: device synchronisation failed");
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
-    // unpack into the caller's ks_bind rows: members are independent, so large groups fill them
-    // on several host threads (this is host-memory-bound: 24 B written per bind)
-    auto finish = [&](int lo, int hi) {
-        for (int i = lo; i < hi; i++) {
-            ks_engine* e = g->engs[i];
-            if (status_out[i] != KS_OK || !part[i]) continue;
-            const ks::BindSeg& sg = g->h_seg[i];
-            status_out[i] = step_finish(e, t_end[i], start[i], g->h_out + sg.off, g->h_out + total + sg.off,
-                                        out ? out + (int64_t)i * cap : nullptr, out ? cap : 0, &n_out[i]);
-        }
-    };
-    // the host's CPU share: OMP_NUM_THREADS when the job sets it (the GPU box does: 16), else the
-    // hardware threads, at most 32
-    int hw = (int)std::thread::hardware_concurrency();
-    if (const char* v = std::getenv("OMP_NUM_THREADS"))
-        if (std::atoi(v) > 0) hw = std::atoi(v);
-    const int nth = total >= (1 << 18) ? std::min<int>(S, std::clamp<int>(hw, 1, 32)) : 1;
-    if (nth <= 1) {
-        finish(0, S);
-    } else {
-        std::vector<std::thread> pool;
-        for (int k = 1; k < nth; k++) pool.emplace_back(finish, (int)((int64_t)S * k / nth), (int)((int64_t)S * (k + 1) / nth));
-        finish(0, (int)((int64_t)S / nth));
-        for (auto& th : pool) th.join();
-    }
-    if (stats) {
-        *stats = ks_step_stats{};
-        stats->step_ms = ms;
-        stats->launches = launches;
-        for (int i = 0; i < S; i++) stats->pods += n_out[i];
-    }
-    return KS_OK;
-}
 
 int64_t ks_current_tick(const ks_engine* e) { return e ? e->tick : -1; }
 int32_t ks_tick_seconds(const ks_engine* e) { return e ? e->cfg.tick_seconds : -1; }

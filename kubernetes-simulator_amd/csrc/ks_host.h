@@ -1,5 +1,6 @@
 // ks_host.h — the engine record and the few host functions its translation units share
-// (internal: ks_engine.cpp runs the simulation, ks_queries.cpp answers about it after the fact).
+// (internal: ks_engine.cpp owns the engine's life cycle and loads it, ks_step.cpp steps it,
+// ks_queries.cpp answers about it after the fact).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -13,6 +14,7 @@
 
 #include "../../include/ks_engine.h"
 #include "ks_device.h"
+#include "ks_plan.h"
 
 namespace ks_host {
 
@@ -184,7 +186,7 @@ struct ks_engine {
     int64_t* d_spec = nullptr;
     ks::EngineArgs* d_args_spec = nullptr;  // [2]: ctr = d_spec + kSpecStride * parity
     ks::EngineArgs* h_args_spec = nullptr;
-    // the pipelined sharded chain (round 6, step_body): the next batch's speculative scan, per-part
+    // the pipelined sharded chain (round 6, ks_step.cpp batch_pipe): the next batch's speculative scan, per-part
     // merges and exchange on a second stream beside the resolve; a rescan scans every block locally
     // (d_args_full: the whole block range, the engine's own list set)
     hipStream_t st2 = nullptr;
@@ -193,7 +195,7 @@ struct ks_engine {
     ks::EngineArgs* h_args_full = nullptr;
     // group membership (ks_group_add): stream, counters and argument slots belong to the group
     ks_group* group = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (kEvStepBegin ... kEvUsageEnd)
     std::vector<hipEvent_t> prof_ev;
     ks_step_stats stats{};
     ks_kernel_stats kstats{};
@@ -222,6 +224,10 @@ struct ks_engine {
 
 namespace ks_host {
 
+// ks_engine::ev (and the first two: ks_group::ev): a step's first and last stream operation (ks_step_stats'
+// step_ms), a profiled usage query's kernel
+enum { kEvStepBegin = 0, kEvStepEnd = 1, kEvUsageBegin = 2, kEvUsageEnd = 3 };
+
 // record the message for ks_last_error and return code
 ks_status fail(ks_engine* e, ks_status code, const char* fmt, ...);
 
@@ -234,7 +240,50 @@ ks_status fail(ks_engine* e, ks_status code, const char* fmt, ...);
 
 // apply the staged submits (ks_engine.cpp, host-staged submits): before any device work reads them
 hipError_t stage_flush(ks_engine* e);
+// stage the rows of exp_pos that submits rewrote since the last flush (stage_flush does; the per-tick
+// path passes the staged rows inline instead)
+hipError_t stage_xpos(ks_engine* e);
+// the kernels' argument record of the engine as it stands (ks_engine.cpp)
+ks::EngineArgs make_args(ks_engine* e);
+// tick t lies in the int32 passed-seconds domain of a run whose first bind is at first_bind
+bool in_passed_domain(const ks_engine* e, int64_t first_bind, int64_t t);
+// every total + 1 fits the scan's 16-bit key table (weights and constant values are >= 0)
+bool key16(const ks_engine* e);
+// the small (register-table) resolver holds this engine's batches
+bool small_resolver(const ks_engine* e);
+// the engine's resolver (Resolver, ks_plan.h): an explicit flag, else by size class
+int resolver_of(const ks_engine* e);
+// the role-split or the register-table resolver (the chunk resolver runs fused into the batch chain)
+hipError_t launch_resolver(const ks::EngineArgs* d, int S, int mode, int which, hipStream_t st);
+// the batch window workspace, pruned-list bitmaps and the second stream, allocated on the first
+// step that runs a resolver using them (ks_step.cpp)
+ks_status ensure_window_ws(ks_engine* e);
 // apply every not-yet-applied expiry with finish tick <= the current tick (ks_engine.cpp)
 ks_status flush_expiries(ks_engine* e);
 
 }  // namespace ks_host
+
+// Scenario groups (BASELINE.json configs[3]): independent what-if clusters stepped together, one
+// launch per kernel for all of them (scenario = a grid dimension; one resolve workgroup each).
+// ks_engine.cpp creates, fills and destroys them, ks_step.cpp steps them.
+struct ks_group {
+    int device = 0;
+    int cap = 0;
+    hipStream_t st = nullptr;
+    std::vector<ks_engine*> engs;
+    int64_t* d_ctr = nullptr;           // [cap][32]
+    int64_t* h_ctr = nullptr;           // pinned
+    ks::EngineArgs* d_args = nullptr;   // [cap]
+    ks::EngineArgs* h_args = nullptr;   // pinned
+    ks::BindSeg* d_seg = nullptr;       // [cap]
+    ks::BindSeg* h_seg = nullptr;       // pinned
+    int32_t* d_out = nullptr;           // packed binds: node, then status
+    int32_t* h_out = nullptr;           // pinned mirror of d_out
+    int64_t out_cap = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // the second half of the scenarios runs its batch rounds on its own stream: one half's
+    // latency-bound resolvers then share the GPU with the other half's throughput-bound scans
+    hipStream_t st2 = nullptr;
+    hipEvent_t xev = nullptr;  // argument upload done (st -> st2)
+    std::string errmsg;
+};

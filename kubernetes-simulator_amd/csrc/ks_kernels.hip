@@ -1139,7 +1139,7 @@ __global__ __launch_bounds__(256) void rescale_kernel(NodeSoA s, int64_t n_pad, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Launchers, called by ks_engine.cpp.
+// Launchers, called by the host code (ks_engine.cpp, ks_step.cpp, ks_queries.cpp).
 // ---------------------------------------------------------------------------------------------
 int max_batch_pods() { return kMaxBatchR; }
 int max_pods_per_scan_wg() { return kMaxPG; }
@@ -1150,80 +1150,64 @@ hipError_t launch_expire_head(const EngineArgs* d, int S, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <typename KT, bool kPrune, int kLL>
-static void launch_scan_t(const EngineArgs* d, const dim3& g, size_t lds, int mode, int xcd, int cond, int stage, int pers,
-                          hipStream_t st) {
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL((scan_kernel<kEvalMicro, KT, kPrune, kLL>), g, dim3(kBlockNodes), lds, st, d, xcd, cond, stage, pers); break;
-        case kEvalTiny: hipLaunchKernelGGL((scan_kernel<kEvalTiny, KT, kPrune, kLL>), g, dim3(kBlockNodes), lds, st, d, xcd, cond, stage, pers); break;
-        case kEvalNarrow: hipLaunchKernelGGL((scan_kernel<kEvalNarrow, KT, kPrune, kLL>), g, dim3(kBlockNodes), lds, st, d, xcd, cond, stage, pers); break;
-        default: hipLaunchKernelGGL((scan_kernel<kEvalWide, KT, kPrune, kLL>), g, dim3(kBlockNodes), lds, st, d, xcd, cond, stage, pers); break;
-    }
-}
-
 hipError_t launch_scan(const EngineArgs* d, int S, int blk_n, int B, int PG, int mode, bool key16, hipStream_t st,
-                       bool cond, bool prune, int L, bool stage, int pw) {
+                       const ScanOpts& o) {
     // (a staging launch runs even when this rank scans no blocks: merge_cl reads the E records)
-    if ((blk_n > 0 || (stage && S == 1)) && S > 0) {
+    if ((blk_n > 0 || (o.stage && S == 1)) && S > 0) {
         // one (block, pod group) item per workgroup; one engine: the XCD-aware 1-D deal
         const int groups = (B + PG - 1) / PG;
         const size_t lds = (key16 ? sizeof(uint16_t) : sizeof(uint32_t)) * kBlockNodes * PG;
         const bool xcd = S == 1;
-        int64_t wgs = std::max<int64_t>(((int64_t)blk_n * groups + 7) / 8 * 8, stage ? kStageWgs : 0);
-        if (pw > 0 && S == 1) wgs = std::max<int64_t>(std::min<int64_t>(wgs, pw / 8 * 8), kStageWgs);  // (persistent)
+        int64_t wgs = std::max<int64_t>(((int64_t)blk_n * groups + 7) / 8 * 8, o.stage ? kStageWgs : 0);
+        if (o.pw > 0 && S == 1) wgs = std::max<int64_t>(std::min<int64_t>(wgs, o.pw / 8 * 8), kStageWgs);  // (persistent)
         const dim3 g = xcd ? dim3((unsigned)wgs, 1, 1) : dim3(blk_n, groups, S);
-        const int x = xcd ? 1 : 0, c = cond ? 1 : 0, sg = stage && xcd ? 1 : 0;
-        if (L != kTopL) {  // the overlap's single-shard lists and the pipelined sharded engines' (ks_engine.cpp)
-            if (L != kTopLOverlap) return hipErrorInvalidValue;
-            if (key16) {
-                if (prune) launch_scan_t<uint16_t, true, kTopLOverlap>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-                else launch_scan_t<uint16_t, false, kTopLOverlap>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-            } else {
-                if (prune) launch_scan_t<uint32_t, true, kTopLOverlap>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-                else launch_scan_t<uint32_t, false, kTopLOverlap>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-            }
-        } else if (key16) {
-            if (prune) launch_scan_t<uint16_t, true, kTopL>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-            else launch_scan_t<uint16_t, false, kTopL>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-        } else {
-            if (prune) launch_scan_t<uint32_t, true, kTopL>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-            else launch_scan_t<uint32_t, false, kTopL>(d, g, lds, mode, x, c, sg, pw > 0 ? 1 : 0, st);
-        }
+        const int x = xcd ? 1 : 0, c = o.cond ? 1 : 0, sg = o.stage && xcd ? 1 : 0, pers = o.pw > 0 ? 1 : 0;
+        // one instantiation per (evaluator, key width, pruned, list length); kt: a value of the key type
+        auto go = [&](auto kt, auto prune, auto ll) {
+            with_eval_mode(mode, [&](auto m) {
+                hipLaunchKernelGGL((scan_kernel<decltype(m)::value, decltype(kt), decltype(prune)::value, decltype(ll)::value>),
+                                   g, dim3(kBlockNodes), lds, st, d, x, c, sg, pers);
+            });
+        };
+        using std::integral_constant;
+        // (kTopLOverlap: the two-launch chain's lists and the pipelined sharded engines', ks_plan.h)
+        if (o.L != kTopL && o.L != kTopLOverlap) return hipErrorInvalidValue;
+        auto with_len = [&](auto kt, auto prune) {
+            if (o.L != kTopL) go(kt, prune, integral_constant<int, kTopLOverlap>{});
+            else go(kt, prune, integral_constant<int, kTopL>{});
+        };
+        auto with_prune = [&](auto kt) {
+            if (o.prune) with_len(kt, std::true_type{});
+            else with_len(kt, std::false_type{});
+        };
+        if (key16) with_prune(uint16_t{});
+        else with_prune(uint32_t{});
     }
     return hipGetLastError();
 }
 
-hipError_t launch_merge(const EngineArgs* d, int S, int B, const uint64_t* lists, int64_t pod_stride, int32_t nl,
-                        int64_t list_stride, uint64_t* out, int nl_max, hipStream_t st, const uint64_t* bits,
-                        int32_t nwl, int32_t blk0, int32_t lset_fixed, int L) {
-    const dim3 g(B, S), t(nl_max > 1024 ? 1024 : 256);
-    if (L == kTopLOverlap && L != kTopL) {
-        hipLaunchKernelGGL(merge_kernel<kTopLOverlap>, g, t, 0, st, d, lists, pod_stride, nl, list_stride, out, bits,
-                           nwl, blk0, lset_fixed);
-    } else if (L != kTopL) {
+hipError_t launch_merge(const EngineArgs* d, int S, int B, const ListSet& in, uint64_t* out, hipStream_t st,
+                        const MergeOpts& o) {
+    const dim3 g(B, S), t(in.nl_max > 1024 ? 1024 : 256);
+    if (o.L == kTopLOverlap && o.L != kTopL) {
+        hipLaunchKernelGGL(merge_kernel<kTopLOverlap>, g, t, 0, st, d, in.lists, in.pod_stride, in.nl, in.list_stride, out,
+                           o.bits, o.nwl, o.blk0, o.lset_fixed);
+    } else if (o.L != kTopL) {
         return hipErrorInvalidValue;
-    } else if ((int64_t)nl_max * kL <= kWave && !bits) {
-        hipLaunchKernelGGL(merge_small_kernel, dim3((B + 3) / 4, S), dim3(256), 0, st, d, lists, pod_stride, nl,
-                           list_stride, out);
+    } else if ((int64_t)in.nl_max * kL <= kWave && !o.bits) {
+        hipLaunchKernelGGL(merge_small_kernel, dim3((B + 3) / 4, S), dim3(256), 0, st, d, in.lists, in.pod_stride, in.nl,
+                           in.list_stride, out);
     } else {
-        hipLaunchKernelGGL(merge_kernel<kTopL>, g, t, 0, st, d, lists, pod_stride, nl, list_stride, out, bits, nwl, blk0,
-                           lset_fixed);
+        hipLaunchKernelGGL(merge_kernel<kTopL>, g, t, 0, st, d, in.lists, in.pod_stride, in.nl, in.list_stride, out, o.bits,
+                           o.nwl, o.blk0, o.lset_fixed);
     }
     return hipGetLastError();
-}
-
-template <class C>
-static void launch_resolve_t(const EngineArgs* d, int S, int mode, hipStream_t st) {
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL((resolve_kernel<kEvalMicro, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-        case kEvalTiny: hipLaunchKernelGGL((resolve_kernel<kEvalTiny, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-        case kEvalNarrow: hipLaunchKernelGGL((resolve_kernel<kEvalNarrow, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-        default: hipLaunchKernelGGL((resolve_kernel<kEvalWide, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-    }
 }
 
 hipError_t launch_resolve(const EngineArgs* d, int S, int mode, hipStream_t st) {
-    launch_resolve_t<RBig>(d, S, mode, st);
+    with_eval_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((resolve_kernel<decltype(m)::value, RBig>), dim3(S), dim3(RBig::kThreads), 0, st, d);
+    });
     return hipGetLastError();
 }
 
@@ -1271,12 +1255,9 @@ hipError_t launch_rescale(const NodeSoA& s, int64_t n_pad, PodRec* pods, int64_t
 hipError_t launch_eval_pod(const Cfg& c, const NodeSoA& s, const PodRec* pod, uint32_t filters, uint8_t* mask,
                            int64_t* score, int mode, hipStream_t st) {
     const dim3 g((c.n_nodes + 255) / 256);
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL(eval_pod_kernel<kEvalMicro>, g, dim3(256), 0, st, c, s, pod, filters, mask, score); break;
-        case kEvalTiny: hipLaunchKernelGGL(eval_pod_kernel<kEvalTiny>, g, dim3(256), 0, st, c, s, pod, filters, mask, score); break;
-        case kEvalNarrow: hipLaunchKernelGGL(eval_pod_kernel<kEvalNarrow>, g, dim3(256), 0, st, c, s, pod, filters, mask, score); break;
-        default: hipLaunchKernelGGL(eval_pod_kernel<kEvalWide>, g, dim3(256), 0, st, c, s, pod, filters, mask, score); break;
-    }
+    with_eval_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(eval_pod_kernel<decltype(m)::value>, g, dim3(256), 0, st, c, s, pod, filters, mask, score);
+    });
     return hipGetLastError();
 }
 

@@ -134,16 +134,16 @@ ks_status ks_usage_at(ks_engine* e, int64_t t, int64_t* usage_out) {
     HIPCHK(e, hipMemsetAsync(e->d_usage, 0, sizeof(unsigned long long) * 3 * e->n, e->st));
     if (nb) {
         // (profiling: HIP events around the usage kernel alone — its roofline in bench.py)
-        if (e->profiling && e->ev[2]) HIPCHK(e, hipEventRecord(e->ev[2], e->st));
+        if (e->profiling && e->ev[kEvUsageBegin]) HIPCHK(e, hipEventRecord(e->ev[kEvUsageBegin], e->st));
         HIPCHK(e, ks::launch_usage(e->d_blk.p, nb, q_hi, t, e->cfg.tick_seconds, e->b_node.p, e->b_status.p, e->t0.p,
                                    e->dur.p, e->phase_off.p, e->cum_sec.p, e->use.p, e->d_usage, e->st));
-        if (e->profiling && e->ev[3]) HIPCHK(e, hipEventRecord(e->ev[3], e->st));
+        if (e->profiling && e->ev[kEvUsageEnd]) HIPCHK(e, hipEventRecord(e->ev[kEvUsageEnd], e->st));
     }
     HIPCHK(e, hipMemcpyAsync(usage_out, e->d_usage, sizeof(int64_t) * 3 * e->n, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
-    if (e->profiling && nb && e->ev[2]) {
+    if (e->profiling && nb && e->ev[kEvUsageBegin]) {
         float ms = 0;
-        (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
+        (void)hipEventElapsedTime(&ms, e->ev[kEvUsageBegin], e->ev[kEvUsageEnd]);
         e->kstats.usage_ms += ms;
         e->kstats.usage_n += 1;
         e->kstats.usage_pods += (int64_t)nb * ks::usage_block_pods();

@@ -524,16 +524,6 @@ __global__ __launch_bounds__(C::kThreads) void resolve_kernel(const EngineArgs* 
     }
 }
 
-template <class C>
-void launch_t(const EngineArgs* d, int S, int mode, hipStream_t st) {
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL((resolve_kernel<kEvalMicro, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-        case kEvalTiny: hipLaunchKernelGGL((resolve_kernel<kEvalTiny, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-        case kEvalNarrow: hipLaunchKernelGGL((resolve_kernel<kEvalNarrow, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-        default: hipLaunchKernelGGL((resolve_kernel<kEvalWide, C>), dim3(S), dim3(C::kThreads), 0, st, d); break;
-    }
-}
-
 // ks_selftest_eval, the register-entry columns: conv() of the case's node into the mode's entry type
 // (NodeS32, NodeM with its cached invariants, NodeV), then eval_t and the bound prepared from the
 // entry (prune_prep), as the resolver's owner lanes do
@@ -558,7 +548,9 @@ __global__ __launch_bounds__(256) void evtest_conv_kernel(EvalCases e) {
 }  // namespace
 
 hipError_t launch_resolve_small(const EngineArgs* d, int S, int mode, hipStream_t st) {
-    launch_t<RSmall>(d, S, mode, st);
+    with_eval_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((resolve_kernel<decltype(m)::value, RSmall>), dim3(S), dim3(RSmall::kThreads), 0, st, d);
+    });
     return hipGetLastError();
 }
 

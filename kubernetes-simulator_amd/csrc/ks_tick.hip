@@ -160,12 +160,9 @@ hipError_t launch_apply_exp(const NodeSoA& s, uint8_t* expired, const ExpList& l
 hipError_t launch_tick(const TickArgs& a, int mode, hipStream_t st) {
     const int64_t per = (int64_t)kTickThreads * kTickNodes;
     const int grid = (int)((a.c.n_nodes + per - 1) / per) + 1;  // + the copy workgroup
-    switch (mode) {
-        case kEvalMicro: hipLaunchKernelGGL(tick_kernel<kEvalMicro>, dim3(grid), dim3(kTickThreads), 0, st, a); break;
-        case kEvalTiny: hipLaunchKernelGGL(tick_kernel<kEvalTiny>, dim3(grid), dim3(kTickThreads), 0, st, a); break;
-        case kEvalNarrow: hipLaunchKernelGGL(tick_kernel<kEvalNarrow>, dim3(grid), dim3(kTickThreads), 0, st, a); break;
-        default: hipLaunchKernelGGL(tick_kernel<kEvalWide>, dim3(grid), dim3(kTickThreads), 0, st, a); break;
-    }
+    with_eval_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(tick_kernel<decltype(m)::value>, dim3(grid), dim3(kTickThreads), 0, st, a);
+    });
     return hipGetLastError();
 }
 

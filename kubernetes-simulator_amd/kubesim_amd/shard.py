@@ -1,6 +1,6 @@
 """Node-shard geometry and the candidate exchange of the sharded engine.
 
-The device path lives in ks_engine.cpp (ks_shard / ks_step): rank r scans its contiguous range
+The device path lives in ks_engine.cpp (ks_shard) and ks_step.cpp (ks_step): rank r scans its contiguous range
 of 256-node blocks, merges it to an exact per-pod top-L list of packed keys, the lists are
 all-gathered over RCCL, and a second merge gives the global top-L.  This module restates the
 geometry (``part_blocks``, identical to ks_load_nodes) and the merge for the host side: the

@@ -1,6 +1,6 @@
 """Dev tool (not a test): the exact scores of one pod of the C5 trace after the pods before it are
 bound (unsharded engine, ks_step + ks_score at the current tick) — for a bind that differs between
-two builds (tests/dev/byval_diag.py).  python tests/dev/pod_keys.py POD NODE..."""
+two builds.  python tests/dev/pod_keys.py POD NODE..."""
 import os
 import sys
 

@@ -1,7 +1,7 @@
 """Scenario groups whose members differ: the inputs of tests/test_group_mixed_gpu.py, pinned on the
 traces and the oracle alone by tests/test_group_cases.py.
 
-ks_group_step (ks_engine.cpp) decides for the whole group, per step: the evaluator class (the widest
+ks_group_step (ks_step.cpp) decides for the whole group, per step: the evaluator class (the widest
 any member needs), the scan's key-table word (16 bits only if every member's totals fit), the
 resolver (the register-table one only if every member is in the small class), the scan grid (largest
 block count x largest batch) and the merge kernel (merge_small up to 8 blocks).  MEMBERS are

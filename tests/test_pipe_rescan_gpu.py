@@ -1,4 +1,4 @@
-"""The pipelined sharded chain's E-overflow branch (ks_engine.cpp pipe_batch).  A sharded engine
+"""The pipelined sharded chain's E-overflow branch (ks_step.cpp batch_pipe).  A sharded engine
 whose rank scans more than kOverlapMaxBlocks = 256 blocks runs batch b + 1's speculative scan, part
 merges and exchange on a second stream beside batch b's resolve.  When the window prep flags a
 rescan (more changed nodes than E holds), the main stream scans every block of the cluster locally
@@ -33,7 +33,7 @@ MODE = "feeds_all_lrba"
 BATCH = 192
 PODS = 1536
 STEPS = (700, 836)
-OVERLAP_MAX_BLOCKS = 256  # csrc/ks_engine.cpp kOverlapMaxBlocks
+OVERLAP_MAX_BLOCKS = 256  # csrc/ks_plan.h kOverlapMaxBlocks
 NODES = (OVERLAP_MAX_BLOCKS + 1) * shard.BLOCK_NODES  # 65,792
 
 _traces, _oracles = {}, {}
@@ -70,7 +70,10 @@ def _oracle(case):
 
 def _lockstep(case, flags):
     """One engine with two parts (257 blocks: the pipelined chain), profiled, in lockstep with the
-    oracle.  Returns (engine, binds, side passes summed over the steps)."""
+    oracle.  Returns (engine, binds, side passes summed over the steps).  Every step's launch counts
+    are the pipelined chain's (N batches): a scan (or the conditional rescan) and a merge_cl per batch,
+    no window prep counted, an exchange on the main stream once per pass (its first batch), the
+    unfused resolve once per pass (its last), a side pass beside every fused resolve."""
     tr, enc = _trace(case)
     assert np.diff(shard.engine_part_blocks(tr["nodes"]["n"], 1, 2)).sum() == OVERLAP_MAX_BLOCKS + 1
     eng = make_engine(tr, enc, MODE, BATCH, flags, shard=(1, 0, None, 2))
@@ -82,7 +85,10 @@ def _lockstep(case, flags):
         eb = eng.step(k)
         assert_same_binds(eb, ob)
         np.testing.assert_array_equal(eng.usage(), ou)
-        side += int(eng.last_step_kernels()["side_n"])
+        kn, n = eng.last_step_kernels(), eng.last_step_stats()["launches"]
+        assert n > 0 and kn["scan_n"] == kn["merge_n"] == n and kn["prep_n"] == 0, (n, kn)
+        assert kn["xchg_n"] == kn["resolve_n"] and kn["fused_n"] == kn["side_n"] == n - kn["resolve_n"], (n, kn)
+        side += int(kn["side_n"])
         got.append(eb)
     return eng, np.concatenate(got), side
 

@@ -102,7 +102,7 @@ def test_chunk_decimal_memory_class():
     _run(tr, "feeds_all_lrba", 8000, 0, 0, (2500, 5500))
 
 
-# ---- the overlap (next batch's scan fused into the chunk kernel, ks_engine.cpp step loop) ------
+# ---- the overlap (next batch's scan fused into the chunk kernel, ks_step.cpp) ------
 def _engine_env(tr, enc, mode, overlap, engine_flags=0, **kw):
     flags = engine_flags | (0 if overlap else _lib.KS_ENGINE_NO_OVERLAP)
     return make_engine(tr, enc, mode, engine_flags=flags, **kw)

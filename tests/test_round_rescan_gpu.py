@@ -1,4 +1,4 @@
-"""The two-launch overlapped chain (ks_engine.cpp step_body): a single-shard engine on
+"""The two-launch overlapped chain (ks_step.cpp batch_two_launch): a single-shard engine on
 the fused overlap launches merge_cl -> chunk kernel per overlapped batch, with no conditional scan
 in between.  merge_cl reads its E nodes from the node table and the node constants table, and a
 window prep that must rescan (E overflow) publishes an empty batch whose round's fused scan lists
@@ -18,6 +18,7 @@ from kubesim_amd import encode as E
 pytestmark = pytest.mark.gpu
 
 CHUNK = _lib.KS_ENGINE_CHUNK_RESOLVER
+ONE_POD = _lib.KS_ENGINE_ONE_POD_RESOLVER
 SMALL_E = _lib.KS_ENGINE_SMALL_E
 PRUNED = _lib.KS_ENGINE_PRUNED_LISTS
 BATCH = 192
@@ -123,15 +124,15 @@ def test_same_binds_with_and_without_small_e():
     b.close()
 
 
-def test_constants_table_after_a_rescale():
-    """The first fractional-byte pod arrives between two batched steps (tests/test_engine_gpu.py
-    test_memory_unit_rescale_mid_run, its sizes): the submit rescales the node table's memory
-    fields, which the node constants table packs.  Chunk resolver forced, overlap on."""
+def _rescale_run(flags, batch=256, profile=False):
+    """The 500-node, 1,200-pod trace whose first fractional-byte pod arrives between two batched
+    steps, in lockstep with the oracle; yields the engine after each step."""
     tr = small_trace(31, n_nodes=500, n_pods=1200, taints=False, selectors=False, tolerations=False)
     tr["pods"]["req"][700:, 1] += 1  # +1 milli-byte: not a whole byte
     mode = "feeds_all_lrba"
     enc = encoded(tr)
-    eng = make_engine(tr, enc, mode, 256, CHUNK)
+    eng = make_engine(tr, enc, mode, batch, flags)
+    eng.set_profiling(profile)
     ora = make_oracle(tr, mode)
     for lo, hi in ((0, 600), (600, 1200)):
         part = tracegen.slice_pods(tr, lo, hi)
@@ -142,20 +143,60 @@ def test_constants_table_after_a_rescale():
         assert orc == 0
         assert_same_binds(eb, ob)
         np.testing.assert_array_equal(eng.usage(), ora.usage())
-    _no_marks(eng)
+        yield eng
     eng.close()
+
+
+def test_constants_table_after_a_rescale():
+    """The first fractional-byte pod arrives between two batched steps (tests/test_engine_gpu.py
+    test_memory_unit_rescale_mid_run, its sizes): the submit rescales the node table's memory
+    fields, which the node constants table packs.  Chunk resolver forced, overlap on."""
+    for step, eng in enumerate(_rescale_run(CHUNK)):
+        if step == 1:  # (after the last step)
+            _no_marks(eng)
+
+
+def _launch_counts(eng):
+    """(launches of the last step, its per-kernel statistics), profiling on."""
+    k, n = eng.last_step_kernels(), eng.last_step_stats()["launches"]
+    print(n, {f: v for f, v in k.items() if f.endswith("_n")})
+    assert n > 0
+    return n, k
+
+
+@pytest.mark.parametrize("flags,batch", [(ONE_POD, 256), (0, 0)], ids=["one_pod_resolver", "small_resolver"])
+def test_plain_chain_launches_every_kernel_per_batch(flags, batch):
+    """The plain chain (ks_step.cpp batch_plain) is four launches per batch whatever the resolver:
+    expiries, scan, merge and the resolver once each, nothing fused.  The role-split resolver forced
+    on 256-pod batches; and no resolver flag with the engine's own batch size (64 pods on 500 nodes,
+    within the register-table resolver's 128), which selects that resolver — with 256-pod batches the
+    default would be the chunk resolver's two-launch chain, whose fused launches fail this."""
+    for eng in _rescale_run(flags, batch, profile=True):
+        n, k = _launch_counts(eng)
+        assert k["prep_n"] == k["scan_n"] == k["merge_n"] == k["resolve_n"] == n, (n, k)
+        assert k["fused_n"] == 0 and k["xchg_n"] == 0 and k["side_n"] == 0, k
 
 
 def test_unchanged_chains_still_launch_their_scan():
     """A sharded overlapped engine keeps its conditional scan launch per batch (scan_n == merge_n);
     the single-shard overlapped engine launches a scan only for a pass's first batch, the batches
-    whose window prep is a launch of its own (scan_n == prep_n)."""
+    whose window prep is a launch of its own (scan_n == prep_n).  Per chain, the launch counts of the
+    step (N batches): the sharded overlap (ks_step.cpp batch_overlap_sharded) scans, merges and
+    exchanges every batch, preps once per pass and resolves unfused once per pass (its last batch);
+    the two-launch chain (batch_two_launch) merges every batch, scans only where it preps, and never
+    exchanges."""
     steps = CASES["dense_expiries"][1]
     eng, _ = _lockstep("dense_expiries", "feeds_all_lrba", steps, CHUNK, shard=(1, 0, None, 2), profile=True)
     k = eng.last_step_kernels()
     assert k["merge_n"] > k["prep_n"] > 0 and k["scan_n"] == k["merge_n"], k
+    n, k = _launch_counts(eng)
+    assert k["scan_n"] == k["merge_n"] == k["xchg_n"] == n, (n, k)
+    assert k["prep_n"] == k["resolve_n"] and k["fused_n"] == n - k["prep_n"], (n, k)
     eng.close()
     eng, _ = _lockstep("dense_expiries", "feeds_all_lrba", steps, CHUNK, profile=True)
     k = eng.last_step_kernels()
     assert k["merge_n"] > k["prep_n"] > 0 and k["fused_n"] > 0 and k["scan_n"] == k["prep_n"], k
+    n, k = _launch_counts(eng)
+    assert k["merge_n"] == n and k["scan_n"] == k["prep_n"] == k["resolve_n"], (n, k)
+    assert k["fused_n"] == n - k["prep_n"] and k["xchg_n"] == 0, (n, k)
     eng.close()

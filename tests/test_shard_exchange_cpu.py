@@ -3,7 +3,7 @@
 Each rank evaluates pods against its node shard only (the oracle's Filter+Score,
 oracle/ks_oracle.c ko_eval), keeps the exact per-pod top-L packed keys, the lists are
 all-gathered, and the merge must equal the global top-L — whose head is the oracle's bind.
-This is the algorithm the device runs (ks_engine.cpp ks_step: per-shard merge, RCCL
+This is the algorithm the device runs (ks_step.cpp ks_step: per-shard merge, RCCL
 all-gather, merge); the GPU suite checks the device path itself (tests/test_engine_gpu.py).
 """
 import os

@@ -106,7 +106,7 @@ def _c5_golden_ranks(world, **kw):
 
 def test_c5_whole_trace_sixteen_ranks_overlapped_match_oracle_golden():
     """BASELINE configs[4] as 16 ranks: 256 scan blocks per rank, so every rank runs the overlap
-    (its speculative scan fused into its chunk kernel; ks_engine.cpp kOverlapMaxBlocks) on pruned
+    (its speculative scan fused into its chunk kernel; ks_plan.h kOverlapMaxBlocks) on pruned
     lists (1M nodes), with the exchange every batch — every pod of the C5 leg against
     tests/golden/full_run.json on every rank.  (The candidate slots stay within the claims a batch
     can make; their overflow past the staged ones is tests/test_candidate_capacity_gpu.py's.)"""
@@ -116,8 +116,8 @@ def test_c5_whole_trace_sixteen_ranks_overlapped_match_oracle_golden():
 
 def test_c5_whole_trace_eight_ranks_deployment_layout_match_oracle_golden():
     """BASELINE configs[4] in the 8-GPU deployment layout: 8 thread-ranks x 1 part, 512 scan blocks
-    per rank — above kOverlapMaxBlocks, so every rank runs the pipelined chain (ks_engine.cpp
-    pipe_batch; no rescans here: tests/test_pipe_rescan_gpu.py) on pruned lists (1M nodes) with the
+    per rank — above kOverlapMaxBlocks, so every rank runs the pipelined chain (ks_step.cpp
+    batch_pipe; no rescans here: tests/test_pipe_rescan_gpu.py) on pruned lists (1M nodes) with the
     exchange every batch; every pod against tests/golden/full_run.json on every
     rank.  (The candidate slots stay within the claims a batch can make; their overflow past the
     staged ones is tests/test_candidate_capacity_gpu.py's.)"""

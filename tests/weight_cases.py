@@ -2,7 +2,7 @@
 the inputs of tests/test_weight_paths_gpu.py (the engine against the oracle on every path), pinned on
 the oracle alone by tests/test_weight_cases.py.
 
-The host changes how the device works at three values of that maximum (ks_engine.cpp): key16() keeps
+The host changes how the device works at three values of that maximum (ks_engine.cpp, ks_plan.h): key16() keeps
 the scan's 16-bit key table, and chunk_eligible() the chunk resolver, while maximum + 1 < 2^16;
 update_mode() takes the micro evaluator while both weights are below kMicroWeight = 2^24; ks_create
 accepts a maximum up to 2^30 - 3 (the resolvers' 30-bit key of total + 1).  CLASSES put a
