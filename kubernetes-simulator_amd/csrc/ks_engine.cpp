@@ -355,6 +355,10 @@ void engine_free(ks_engine* e) {
     if (e->lthr) (void)hipFree(e->lthr);
     if (e->comm) (void)ncclCommDestroy(e->comm);
     if (e->h_xbuf) (void)hipHostFree(e->h_xbuf);
+    if (e->st_copy) { (void)hipStreamSynchronize(e->st_copy); (void)hipStreamDestroy(e->st_copy); }
+    if (e->snap_ev) (void)hipEventDestroy(e->snap_ev);
+    if (e->h_bnode) (void)hipHostFree(e->h_bnode);
+    if (e->h_bstat) (void)hipHostFree(e->h_bstat);
     if (!e->group) {
         if (e->d_ctr) (void)hipFree(e->d_ctr);
         if (e->h_ctr) (void)hipHostFree(e->h_ctr);
@@ -935,6 +939,10 @@ ks_status ks_debug_counters(ks_engine* e, int64_t* out32) {
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipMemcpyAsync(out32, e->d_ctr, 32 * sizeof(int64_t), hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
+#if !defined(KS_CHUNK_DIAG) && !defined(KS_MCL_DIAG)  // (those builds count in ctr[8], ctr[9] on the device)
+    out32[8] = e->early_pods;  // host side: no kernel of the product writes ctr[8] or ctr[9]
+    out32[9] = e->snap_pods;
+#endif
     return KS_OK;
 }
 

@@ -176,7 +176,18 @@ struct ks_engine {
     uint64_t* lthr = nullptr;  // [2][kThrCopies][B]
     int nwl = 0;
     int64_t* d_ctr = nullptr;
-    int64_t* h_ctr = nullptr;  // pinned
+    int64_t* h_ctr = nullptr;  // pinned ([8]: the early read-back's snapshot of the start counter)
+    // a batched step's read-back (ks_step.cpp step_body): the node and status words of the step's
+    // pods [done, p_hi), pinned, grown geometrically; the copy stream and the event of the early
+    // read-back (ks_plan.h early_round)
+    int32_t* h_bnode = nullptr;
+    int32_t* h_bstat = nullptr;
+    int64_t bind_cap = 0;
+    hipStream_t st_copy = nullptr;
+    hipEvent_t snap_ev = nullptr;
+    // the last batched step's binds finished on the host before its last wait, and those of them that
+    // came back below a snapshot, on the copy stream
+    int64_t early_pods = 0, snap_pods = 0;
     ks::EngineArgs* d_args = nullptr;  // the kernels' argument record (device)
     ks::EngineArgs* h_args = nullptr;  // its pinned host staging
     // overlap of the next batch's scan with the chunk resolver (chunk class, one shard): the

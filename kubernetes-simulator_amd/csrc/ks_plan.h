@@ -79,6 +79,22 @@ inline StepPlan plan_step(const PlanFacts& f) {
     return p;
 }
 
+// ---- the early read-back -------------------------------------------------------------------------
+// A pass enqueues its ceil(n / B) rounds blind and waits once, after the last.  On a two-launch pass
+// of at least kEarlyMinRounds rounds the host takes a snapshot of the start counter after round
+// early_round() (a kernel boundary: every bind below it is visible) and copies and finishes the
+// binds below it while the last kEarlyK rounds run: ~0.55 ms of device work at C3, about twice the
+// host's work on a 32,768-pod step, and the ~1,100 binds of those rounds are all that is left after
+// the wait.  -1: no snapshot (shorter passes, the other chains).
+#ifndef KS_EARLY_READBACK
+#define KS_EARLY_READBACK 1  // (A/B: make variant NAME=noearly DEFS=-DKS_EARLY_READBACK=0)
+#endif
+constexpr int kEarlyMinRounds = 16;
+constexpr int kEarlyK = 6;
+inline int64_t early_round(int64_t rounds, Chain chain) {
+    return KS_EARLY_READBACK && chain == kChainTwoLaunch && rounds >= kEarlyMinRounds ? rounds - 1 - kEarlyK : -1;
+}
+
 // ---- profile marks ---------------------------------------------------------------------------
 // One pooled HIP event per mark and batch while profiling is on.  A chain records the marks around
 // its launches in stream order; a mark it does not reach is not recorded for that batch.

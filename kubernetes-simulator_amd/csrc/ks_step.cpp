@@ -2,13 +2,17 @@
 //
 // A batched step (step_body) reads top to bottom: prepare the counters, take the per-tick shortcut
 // when exactly one pod binds, decide the plan once (ks_plan.h: which of the four launch chains, the
-// block lists' length), upload the argument records, then per pass issue the chain's batches, read
-// the counters back and check progress; at the end copy the binds back, account the profile and
-// finish.  Each chain has one function that issues one batch's launches in stream order
+// block lists' length), upload the argument records, then per pass issue the chain's batches,
+// enqueue the counters' and the binds' copies behind them and wait once; on a long pass the binds
+// below a snapshot of the start counter come back early, on a copy stream, and are finished while
+// the last rounds run (ks_plan.h early_round), and a later pass hides the finishing of the earlier
+// passes' binds.  A pass that leaves pods is followed by another.  At the end account the profile
+// and finish the remaining binds.  Each chain has one function that issues one batch's launches in stream order
 // (batch_plain, batch_overlap_sharded, batch_two_launch, batch_pipe); the only conditions left inside
 // are the batch's position in the pass and, on the plain chain, which kernels the resolver takes.
 // Profile marks (ks_plan.h Mark) are recorded by name around the launches while profiling is on and
 // cost nothing otherwise.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -20,6 +24,9 @@ using namespace ks_host;
 namespace {
 
 constexpr int kRescanWgs = 1024;  // the pipelined chain's conditional local rescan: workgroups
+// a pass copies the words of at most this many pods behind its last round, before it knows how many
+// of them were bound (step_body): 16 KB per array
+constexpr int64_t kCopyBehindMax = 4096;
 
 // ks_step, first half: the pods whose bind tick falls in (tick, tick + ticks] and the device
 // counters for them.  Returns false when there is nothing to schedule (the caller just advances
@@ -50,22 +57,29 @@ ks_status device_stop(ks_engine* e, ks_status r) {
     return r;
 }
 
-// ks_step, second half: the binds [done, new_done) (node / status copied back by the caller),
-// errors as Run would return them (kubesim.go:114-120, 217-220).
-ks_status step_finish(ks_engine* e, int64_t t_end, int64_t new_done, const int32_t* node, const int32_t* status,
-                      ks_bind* out, int64_t cap, int64_t* n_out) {
-    const int64_t nb = new_done - e->done;
-    for (int64_t i = 0; i < nb && i < cap; i++) {
-        out[i].pod = e->done + i;
-        out[i].node = node[i];
-        out[i].status = status[i];
-        out[i].tick = e->h_bind_tick[e->done + i];
+// The binds of pods [lo, hi) of a step that began at pod e->done (node / status: the words of the
+// step's pods from e->done on, copied back by the caller) into the caller's rows, clipped at cap,
+// and into the host mirror.
+void bind_rows(ks_engine* e, int64_t lo, int64_t hi, const int32_t* node, const int32_t* status, ks_bind* out,
+               int64_t cap) {
+    const int64_t base = e->done;
+    for (int64_t j = lo; j < hi && j - base < cap; j++) {
+        ks_bind& o = out[j - base];
+        o.pod = j;
+        o.node = node[j - base];
+        o.status = status[j - base];
+        o.tick = e->h_bind_tick[j];
     }
-    for (int64_t i = 0; i < nb; i++) {
-        e->h_node[e->done + i] = node[i];
-        e->h_status[e->done + i] = (int8_t)status[i];
+    for (int64_t j = lo; j < hi; j++) {
+        e->h_node[j] = node[j - base];
+        e->h_status[j] = (int8_t)status[j - base];
     }
-    *n_out = nb;
+}
+
+// ks_step's end once the rows of [done, new_done) are written: the counts, the error as Run would
+// return it (kubesim.go:114-120, 217-220), the tick.
+ks_status step_close(ks_engine* e, int64_t t_end, int64_t new_done, int64_t* n_out) {
+    *n_out = new_done - e->done;
     e->done = new_done;
     if (e->h_ctr[2] != 0) {
         const int64_t pod = e->h_ctr[3];
@@ -80,6 +94,14 @@ ks_status step_finish(ks_engine* e, int64_t t_end, int64_t new_done, const int32
     }
     e->tick = t_end;
     return KS_OK;
+}
+
+// ks_step, second half: the binds [done, new_done) (node / status copied back by the caller) and the
+// step's end.
+ks_status step_finish(ks_engine* e, int64_t t_end, int64_t new_done, const int32_t* node, const int32_t* status,
+                      ks_bind* out, int64_t cap, int64_t* n_out) {
+    bind_rows(e, e->done, new_done, node, status, out, cap);
+    return step_close(e, t_end, new_done, n_out);
 }
 
 // Expiries attached to pods [lo, hi) have been applied on the device (the batch path applies
@@ -533,7 +555,70 @@ ks_status upload_args(ks_engine* e, const StepPlan& plan) {
     return KS_OK;
 }
 
+// The step's read-back buffers: pinned node and status words for n pods, allocated once and grown
+// geometrically (nothing is in flight into them between steps); `early`: the chain may read back
+// early, on its copy stream.
+ks_status ensure_readback(ks_engine* e, int64_t n, bool early) {
+    if (n > e->bind_cap) {
+        const int64_t want = std::max<int64_t>({n, 2 * e->bind_cap, 4096});
+        if (e->h_bnode) (void)hipHostFree(e->h_bnode);
+        if (e->h_bstat) (void)hipHostFree(e->h_bstat);
+        e->h_bnode = e->h_bstat = nullptr;
+        e->bind_cap = 0;
+        HIPCHK(e, hipHostMalloc(&e->h_bnode, sizeof(int32_t) * want, hipHostMallocDefault));
+        HIPCHK(e, hipHostMalloc(&e->h_bstat, sizeof(int32_t) * want, hipHostMallocDefault));
+        e->bind_cap = want;
+    }
+    if (early && !e->st_copy) {
+        HIPCHK(e, hipStreamCreateWithFlags(&e->st_copy, hipStreamNonBlocking));
+        HIPCHK(e, hipEventCreateWithFlags(&e->snap_ev, hipEventDisableTiming));
+    }
+    return KS_OK;
+}
+
+// the node and status words of pods [lo, hi) into the read-back buffers (which begin at pod done0), on stream s
+ks_status copy_binds(ks_engine* e, int64_t done0, int64_t lo, int64_t hi, hipStream_t s) {
+    if (hi <= lo) return KS_OK;
+    const size_t bytes = sizeof(int32_t) * (size_t)(hi - lo);
+    HIPCHK(e, hipMemcpyAsync(e->h_bnode + (lo - done0), e->b_node.p + lo, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_bstat + (lo - done0), e->b_status.p + lo, bytes, hipMemcpyDeviceToHost, s));
+    return KS_OK;
+}
+
+// Diagnostic build only (-DKS_TAIL_SPLIT): host timestamps around the sections of step_body outside
+// the rounds, one line per step on stderr (us since the step began) — the product executes none of it.
+#ifdef KS_TAIL_SPLIT
+}  // namespace
+#include <chrono>
+#include <cstdio>
+namespace {
+enum { kTsPrepare, kTsUpload, kTsEnqueue, kTsSnapWait, kTsEarlyCopy, kTsEarlyRows, kTsEarlyMirror, kTsSync, kTsStats,
+       kTsRows, kTsMirror, kTsCount };
+constexpr const char* kTsNames[kTsCount] = {"prepare", "upload", "enqueue", "snap_wait", "early_copy", "early_rows",
+                                            "early_mirror", "sync", "stats", "rows", "mirror"};
+#define TAIL_BEGIN()                                               \
+    double tail_us[kTsCount] = {};                                 \
+    auto tail_t = std::chrono::steady_clock::now()
+#define TAIL_AT(I)                                                                             \
+    do {                                                                                       \
+        const auto t_ = std::chrono::steady_clock::now();                                      \
+        tail_us[I] += std::chrono::duration<double, std::micro>(t_ - tail_t).count();          \
+        tail_t = t_;                                                                           \
+    } while (0)
+#define TAIL_PRINT()                                                                           \
+    do {                                                                                       \
+        std::fprintf(stderr, "tail_split");                                                    \
+        for (int i_ = 0; i_ < kTsCount; i_++) std::fprintf(stderr, " %s=%.1f", kTsNames[i_], tail_us[i_]); \
+        std::fprintf(stderr, "\n");                                                            \
+    } while (0)
+#else
+#define TAIL_BEGIN()
+#define TAIL_AT(I)
+#define TAIL_PRINT()
+#endif
+
 ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int64_t* n_out) {
+    TAIL_BEGIN();
     HIPCHK(e, hipSetDevice(e->device));
     if (ks_status r = ensure_window_ws(e); r != KS_OK) return r;
     const int64_t t_end = e->tick + ticks;
@@ -562,33 +647,96 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
     facts.side_stream = e->st2 != nullptr;
     const StepPlan plan = plan_step(facts);
     e->L = plan.L;
+    if (ks_status r = ensure_readback(e, p_hi - done0, plan.chain == kChainTwoLaunch); r != KS_OK) return r;
+    TAIL_AT(kTsPrepare);
     HIPCHK(e, hipMemcpyAsync(e->d_ctr, e->h_ctr, 5 * sizeof(int64_t), hipMemcpyHostToDevice, st));
     if (ks_status r = upload_args(e, plan); r != KS_OK) return r;
+    TAIL_AT(kTsUpload);
     HIPCHK(e, hipEventRecord(e->ev[kEvStepBegin], st));
-    int64_t start = e->done;
+    int64_t start = done0;
     int64_t launches = 0;
+    // The read-back buffers hold the final words of pods [done0, have); of those, [done0, fin) are
+    // finished on the host: rows written, mirrored, their expiries mirrored.  fin <= have <= start
+    // throughout.  A pass is one of three kinds:
+    //  * a snapshot pass (two-launch, long, every earlier bind buffered: have == start): the binds
+    //    below the snapshot come back on the copy stream and are finished under the last rounds,
+    //    the few above it are copied behind the last round;
+    //  * a short pass with every earlier bind buffered: its words are copied behind its last round;
+    //  * any other (a long pass without a snapshot, or a pass after one): nothing is copied, have
+    //    stays behind start, and one copy after the loop fetches [have, new_done) as ks_step always did.
+    // In the first two kinds the pass's one wait also delivers its binds, and have follows start.
+    int64_t have = done0, fin = done0, snap_pods = 0;
+    const int32_t* const node = e->h_bnode;
+    const int32_t* const status = e->h_bstat;
     StepProfile pf{e, {}};
     while (true) {
-        const int64_t nbat = (p_hi - start + e->B - 1) / e->B;
-        for (int64_t b = 0; b < nbat; b++, launches++)
-            if (ks_status r = chain_batch(e, plan, BatchPos{b, b == 0, b + 1 < nbat}, pf); r != KS_OK) return r;
+        const int64_t rounds = (p_hi - start + e->B - 1) / e->B;
+        const int64_t snap_at = early_round(rounds, plan.chain);
+        for (int64_t b = 0; b < rounds; b++, launches++) {
+            if (ks_status r = chain_batch(e, plan, BatchPos{b, b == 0, b + 1 < rounds}, pf); r != KS_OK) return r;
+            if (b == snap_at) {  // between two rounds: every bind below the counter is visible
+                HIPCHK(e, hipMemcpyAsync(e->h_ctr + 8, e->d_ctr + ks::kCtrStart, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+                HIPCHK(e, hipEventRecord(e->snap_ev, st));
+            }
+        }
+        HIPCHK(e, hipEventRecord(e->ev[kEvStepEnd], st));
         HIPCHK(e, hipMemcpyAsync(e->h_ctr, e->d_ctr, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipStreamSynchronize(st));
+        TAIL_AT(kTsEnqueue);
+        if (fin < have) {  // a later pass: the earlier passes' binds finish under it
+            bind_rows(e, fin, have, node, status, out, cap);
+            mirror_expired(e, fin, have);
+            fin = have;
+            TAIL_AT(kTsEarlyMirror);
+        }
+        int64_t lo = start;  // the pass's binds are [lo, its end): below lo they are in the buffers or come early
+        const bool snapped = snap_at >= 0 && have == start;
+        if (snapped) {
+            // The early read-back: the binds below the snapshot come back on the copy stream and are
+            // finished here while the pass's last rounds run.  Should the step fail after this (a
+            // device failure, or a pod's error past the snapshot), the host mirrors of these pods
+            // and of their expiries are already written, where a failed step used to leave them
+            // untouched: acceptable only because the engine is then sticky-failed (ks_step returns
+            // its error from then on) and the binds themselves are final — the device committed them.
+            HIPCHK(e, hipEventSynchronize(e->snap_ev));
+            TAIL_AT(kTsSnapWait);
+            lo = std::clamp(e->h_ctr[8], start, p_hi);
+        }
+        // The words of [lo, p_hi) behind the pass's last round, with the counters, when they are few
+        // (after a snapshot, or a short pass): one wait ends the pass.  A long pass without a snapshot
+        // would copy mostly unbound pods' words, once per pass: its binds are copied after the loop.
+        const bool behind = have == start && p_hi - lo <= kCopyBehindMax;
+        if (behind)
+            if (ks_status r = copy_binds(e, done0, lo, p_hi, st); r != KS_OK) return r;
+        if (snapped && lo > have) {
+            if (ks_status r = copy_binds(e, done0, have, lo, e->st_copy); r != KS_OK) return r;
+            HIPCHK(e, hipStreamSynchronize(e->st_copy));
+            snap_pods += lo - have;
+            have = lo;
+            TAIL_AT(kTsEarlyCopy);
+            bind_rows(e, fin, have, node, status, out, cap);
+            TAIL_AT(kTsEarlyRows);
+            mirror_expired(e, fin, have);
+            TAIL_AT(kTsEarlyMirror);
+            fin = have;
+        }
+        HIPCHK(e, hipStreamSynchronize(st));  // the pass's only wait for the main stream
+        TAIL_AT(kTsSync);
         const int64_t prev = start;
         start = e->h_ctr[0];
+        if (behind) have = std::clamp(start, have, p_hi);  // (the words below the counter are final)
         if (e->h_ctr[2] != 0 || start >= p_hi) break;
         // every launch commits at least its first pod (resolve_kernel): no progress is a bug
         if (start <= prev) return fail(e, KS_EDEVICE, "scheduling made no progress at pod %lld", (long long)start);
     }
-    HIPCHK(e, hipEventRecord(e->ev[kEvStepEnd], st));
-    const int64_t new_done = start;
-    const int64_t nb = new_done - e->done;
-    std::vector<int32_t> node(nb), status(nb);
-    if (nb) {
-        HIPCHK(e, hipMemcpyAsync(node.data(), e->b_node.p + e->done, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(status.data(), e->b_status.p + e->done, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+    if (have < start) {  // the binds no pass copied behind its rounds
+        if (ks_status r = copy_binds(e, done0, have, start, st); r != KS_OK) return r;
+        HIPCHK(e, hipStreamSynchronize(st));
+        TAIL_AT(kTsSync);
     }
-    HIPCHK(e, hipStreamSynchronize(st));
+    const int64_t new_done = start;
+    const int64_t nb = new_done - done0;
+    e->early_pods = fin - done0;  // (diagnostics: ks_debug_counters [8], [9])
+    e->snap_pods = snap_pods;
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e->ev[kEvStepBegin], e->ev[kEvStepEnd]);
     ks_kernel_stats ks{};
@@ -601,8 +749,13 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
     e->stats.other_ms = sums.other_ms;
     e->stats.launches = launches;
     e->stats.pods = nb;
-    const ks_status rc = step_finish(e, t_end, new_done, node.data(), status.data(), out, cap, n_out);
-    if (rc == KS_OK) mirror_expired(e, done0, e->done);
+    TAIL_AT(kTsStats);
+    bind_rows(e, std::min(fin, new_done), new_done, node, status, out, cap);
+    TAIL_AT(kTsRows);
+    const ks_status rc = step_close(e, t_end, new_done, n_out);
+    if (rc == KS_OK) mirror_expired(e, std::min(fin, new_done), new_done);
+    TAIL_AT(kTsMirror);
+    TAIL_PRINT();
     return rc;
 }
 
