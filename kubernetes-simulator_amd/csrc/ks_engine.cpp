@@ -1,17 +1,18 @@
 // ks_engine.cpp — host side of the C-ABI declared in include/ks_engine.h: create / destroy, load,
 // submit, scenario groups' life cycle, node sharding, debug and statistics.  The engine record is in
-// ks_host.h; ks_step and ks_group_step are in ks_step.cpp; the entry points that answer about a run after the fact (filter / score, usage,
+// ks_host.h, the owners that release its GPU resources in ks_own.h (engine_free only waits and deletes);
+// ks_step and ks_group_step are in ks_step.cpp; the entry points that answer about a run after the fact (filter / score, usage,
 // past-tick state, headroom, placement and drain previews, name-keyed lookups) are in
 // ks_queries.cpp, the device self-tests in ks_selftest.cpp.
 //
 // Host responsibilities (everything that is independent of placements):
 //  * FIFO + one-pod-per-tick: the bind tick of pod j is max(bind_tick[j-1] + 1, arrival_j)
 //    (kubesim/kubesim.go:105-121 pops at most one pod per tick and always binds it), so bind
-//    ticks are fixed at submit time.
+//    ticks are fixed at submit time (bind_tick below).
 //  * expiry schedule: a bound-Ok pod q runs while (t - t0) * tick < Σ phase seconds
-//    (kubesim/pod/pod.go:67-69), i.e. for dur = ceil(S / tick) ticks.  Its expiry is attached
-//    to the first later pod whose bind tick reaches t0 + dur; the device applies it (if q was
-//    bound Ok) right before that pod is scheduled.
+//    (kubesim/pod/pod.go:67-69), i.e. for dur = ceil(S / tick) ticks (run_ticks below).  Its
+//    expiry is attached to the first later pod whose bind tick reaches t0 + dur; the device applies
+//    it (if q was bound Ok) right before that pod is scheduled (ks_submit_pods).
 //  * resource scale: quantities arrive in milli-units; the device holds resource k in units of
 //    g_k = gcd of every capacity and request of k seen so far (exact: every fit / LeastRequested
 //    / BalancedAllocation result is unit-free).  A pod whose request g_k does not divide shrinks
@@ -59,9 +60,17 @@ constexpr int64_t kStageMaxPods = 4096;  // submits of up to this many pods are 
 #ifndef KS_PG_MIN_WG
 #define KS_PG_MIN_WG 2048  // scan workgroups to keep when raising the pods per workgroup
 #endif
-constexpr int64_t kNever = std::numeric_limits<int64_t>::max();
 
-void engine_free(ks_engine* e);  // ks_destroy's body; a group frees its members with it
+// ks_destroy's body; a group frees its members with it
+void engine_free(ks_engine* e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    // every stream that may still work on the engine's buffers, before the owners release anything
+    for (hipStream_t s : {e->st, e->pipe ? (hipStream_t)e->pipe->st2 : nullptr,
+                          e->early ? (hipStream_t)e->early->st_copy : nullptr})
+        if (s) (void)hipStreamSynchronize(s);
+    delete e;
+}
 
 }  // namespace
 
@@ -94,14 +103,11 @@ ks::EngineArgs ks_host::make_args(ks_engine* e) {
     a.ctr = e->d_ctr;
     a.B = e->B;
     a.PG = e->PG;
-    a.sw = e->d_sweep;
-    a.e_idx = e->d_eidx;
-    a.n_slot = e->d_nslot;
-    a.n_first = e->d_first;
+    if (const WindowWs* w = e->win ? &*e->win : nullptr) {
+        a.sw = w->d_sweep; a.e_idx = w->d_eidx; a.n_slot = w->d_nslot; a.n_first = w->d_first; a.spec_ctr = w->d_spec;
+    }
     a.det_cids = e->world * e->vsh > 1 ? 1 : 0;
-    a.spec_ctr = e->d_spec;
-    a.lbit = e->prune ? e->lbit : nullptr;
-    a.lthr = e->prune ? e->lthr : nullptr;
+    if (e->prune) { a.lbit = e->bits->lbit; a.lthr = e->bits->lthr; }
     a.nwl = e->nwl;
     a.lset = 1;  // the engine's own scans (the speculative scan's record: set 0, ks_step.cpp upload_args)
     a.srec = e->srec.p;
@@ -117,7 +123,50 @@ namespace {
 // Staged rows are applied in submission order by one scatter launch (stage_flush) or by the
 // per-tick kernel, always before the device work that reads them (stream order).  The arena is
 // reused once the launch that consumed its last segment has completed.
-hipError_t stage_copy(ks_engine* e, void* dst, const void* src, int64_t bytes);
+
+// room for `bytes` more in the arena and one more segment
+hipError_t stage_room(ks_engine* e, int64_t bytes) {
+    if (e->nseg > 0 && e->seg_done == e->nseg && hipEventQuery(e->stage_ev) == hipSuccess) {
+        e->stage_used = 0;
+        e->nseg = e->seg_done = 0;
+    }
+    const int64_t cap = e->arena ? e->arena->cap : 0;
+    if (e->stage_used + bytes + 16 <= cap && e->nseg < kSegCap) return hipSuccess;
+    KS_TRY(stage_flush(e));
+    KS_TRY(hipStreamSynchronize(e->st));
+    e->stage_used = 0;
+    e->nseg = e->seg_done = 0;
+    if (bytes + 16 <= cap) return hipSuccess;
+    e->arena.reset();  // (freed before the larger one is made)
+    return ks_own::build(e->arena, [&](StageArena& a) {
+        a.cap = std::max<int64_t>(bytes + 16, std::max<int64_t>(2 * cap, 1 << 20));
+        KS_TRY(ks_own::pinned_alloc(a.mem, a.cap, hipHostMallocMapped));
+        return ks_own::pinned_alloc(a.segs, kSegCap, hipHostMallocMapped);
+    });
+}
+
+// one staged copy of `bytes` host bytes to device address dst
+hipError_t stage_copy(ks_engine* e, void* dst, const void* src, int64_t bytes) {
+    if (bytes <= 0) return hipSuccess;
+    KS_TRY(stage_room(e, bytes));
+    StageArena& a = *e->arena;
+    std::memcpy(a.mem + e->stage_used, src, bytes);
+    a.segs[e->nseg++] = ks::CopySeg{(uint8_t*)dst, a.mem.dev + e->stage_used, bytes};
+    e->stage_used += (bytes + 15) / 16 * 16;
+    return hipSuccess;
+}
+
+// DVec::append through the arena (growth flushes first: the copy of the old contents must
+// follow the staged rows written into them)
+template <typename T>
+hipError_t stage_append(ks_engine* e, DVec<T>& v, const T* h, int64_t k) {
+    if (v.n + k > v.cap) {
+        KS_TRY(stage_flush(e));
+        KS_TRY(v.reserve(v.n + k, e->st));
+    }
+    v.n += k;
+    return stage_copy(e, v.p + (v.n - k), h, sizeof(T) * k);
+}
 
 }  // namespace
 
@@ -131,80 +180,18 @@ hipError_t ks_host::stage_xpos(ks_engine* e) {
 }
 
 hipError_t ks_host::stage_flush(ks_engine* e) {
-    if (hipError_t r = stage_xpos(e); r != hipSuccess) return r;
+    KS_TRY(stage_xpos(e));
     if (e->seg_done >= e->nseg) return hipSuccess;
-    hipError_t r = ks::launch_scatter(e->segs_dev + e->seg_done, e->nseg - e->seg_done, e->st);
+    hipError_t r = ks::launch_scatter(e->arena->segs.dev + e->seg_done, e->nseg - e->seg_done, e->st);
     if (r == hipSuccess) r = hipEventRecord(e->stage_ev, e->st);
     e->seg_done = e->nseg;
     return r;
 }
 
-namespace {
-
-// room for `bytes` more in the arena and one more segment
-hipError_t stage_room(ks_engine* e, int64_t bytes) {
-    if (e->nseg > 0 && e->seg_done == e->nseg && hipEventQuery(e->stage_ev) == hipSuccess) {
-        e->stage_used = 0;
-        e->nseg = e->seg_done = 0;
-    }
-    const int64_t need = e->stage_used + bytes + 16;
-    if (need <= e->stage_cap && e->nseg < e->seg_cap) return hipSuccess;
-    hipError_t r = stage_flush(e);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->st);
-    if (r != hipSuccess) return r;
-    e->stage_used = 0;
-    e->nseg = e->seg_done = 0;
-    if (bytes + 16 > e->stage_cap) {
-        if (e->stage) (void)hipHostFree(e->stage);
-        e->stage = nullptr;
-        e->stage_cap = std::max<int64_t>(bytes + 16, std::max<int64_t>(2 * e->stage_cap, 1 << 20));
-        r = hipHostMalloc(&e->stage, e->stage_cap, hipHostMallocMapped);
-        if (r == hipSuccess) r = hipHostGetDevicePointer((void**)&e->stage_dev, e->stage, 0);
-        if (r != hipSuccess) { e->stage = nullptr; e->stage_cap = 0; return r; }
-    }
-    if (e->seg_cap == 0) {
-        e->seg_cap = 1 << 16;
-        r = hipHostMalloc(&e->segs, sizeof(ks::CopySeg) * e->seg_cap, hipHostMallocMapped);
-        if (r == hipSuccess) r = hipHostGetDevicePointer((void**)&e->segs_dev, e->segs, 0);
-        if (r == hipSuccess && !e->stage_ev) r = hipEventCreateWithFlags(&e->stage_ev, hipEventDisableTiming);
-        if (r != hipSuccess) { e->seg_cap = 0; return r; }
-    }
-    return hipSuccess;
-}
-
-// one staged copy of `bytes` host bytes to device address dst
-hipError_t stage_copy(ks_engine* e, void* dst, const void* src, int64_t bytes) {
-    if (bytes <= 0) return hipSuccess;
-    hipError_t r = stage_room(e, bytes);
-    if (r != hipSuccess) return r;
-    std::memcpy(e->stage + e->stage_used, src, bytes);
-    e->segs[e->nseg++] = ks::CopySeg{(uint8_t*)dst, e->stage_dev + e->stage_used, bytes};
-    e->stage_used += (bytes + 15) / 16 * 16;
-    return hipSuccess;
-}
-
-// DVec::append through the arena (growth flushes first: the copy of the old contents must
-// follow the staged rows written into them)
-template <typename T>
-hipError_t stage_append(ks_engine* e, DVec<T>& v, const T* h, int64_t k) {
-    if (v.n + k > v.cap) {
-        hipError_t r = stage_flush(e);
-        if (r == hipSuccess) r = v.reserve(v.n + k, e->st);
-        if (r != hipSuccess) return r;
-    }
-    hipError_t r = stage_copy(e, v.p + v.n, h, sizeof(T) * k);
-    v.n += k;
-    return r;
-}
-
-}  // namespace
-
-// every total + 1 fits the scan's 16-bit key table (weights and constant values are >= 0)
 bool ks_host::key16(const ks_engine* e) {
     return (int64_t)e->dc.const_total + 10 * ((int64_t)e->dc.w_lr + e->dc.w_ba) + 1 < (1 << 16);
 }
 
-// the small (register-table) resolver holds this engine's batches
 bool ks_host::small_resolver(const ks_engine* e) {
     return e->B <= ks::small_resolver_max_batch() && e->dc.n_nodes <= ks::small_resolver_max_nodes();
 }
@@ -240,6 +227,39 @@ int ks_host::resolver_of(const ks_engine* e) {
 // (the chunk resolver runs fused into the batch chain, ks_step.cpp)
 hipError_t ks_host::launch_resolver(const ks::EngineArgs* d, int S, int mode, int which, hipStream_t st) {
     return which == kResolveSmall ? ks::launch_resolve_small(d, S, mode, st) : ks::launch_resolve(d, S, mode, st);
+}
+
+// Apply every not-yet-applied expiry with finish tick <= the current tick (ks_filter / ks_score
+// see the state Run's next scheduleOne would).  While the run is live the host knows them
+// exactly: every expiry attached to a pod < done has been applied (mirror_expired), an expiry
+// attached to a later pod j > done finishes after bind_tick[j - 1] >= bind_tick[done] > tick, so
+// only the next pod's attached expiries and the unattached ones (pending, when every submitted pod
+// is bound) can be due — usually none, and no launch is made.
+ks_status ks_host::flush_expiries(ks_engine* e) {
+    std::vector<int32_t> qs;
+    auto add = [&](int64_t q) {
+        if (e->h_status[q] == KS_POD_OK && !e->h_expired[q] && e->h_fin[q] <= e->tick) qs.push_back((int32_t)q);
+    };
+    if (e->err == KS_OK) {
+        if (e->done < e->P)
+            for (int64_t u = e->h_exp_off[e->done]; u < e->h_exp_off[e->done + 1]; u++) add(e->h_exp_pod[u]);
+        e->pending.for_each_due(e->tick, add);
+    }
+    if (e->err != KS_OK || (int)qs.size() > ks::kTickMaxExp) {
+        HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
+                                   e->expired.p, e->st));
+    } else if (!qs.empty()) {
+        ks::ExpList L{};
+        for (int32_t q : qs) {
+            ks::TickExp& x = L.x[L.n++];
+            x.node = e->h_node[q];
+            x.q = q;
+            for (int k = 0; k < 3; k++) x.req[k] = e->h_pods[q].req[k];
+        }
+        HIPCHK(e, ks::launch_apply_exp(e->s, e->expired.p, L, e->st));
+    }
+    for (int32_t q : qs) e->h_expired[q] = 1;
+    return KS_OK;
 }
 
 namespace {
@@ -307,6 +327,30 @@ ks_status engine_init(const ks_config* cfg, ks_engine** out) {
     return KS_OK;
 }
 
+// ---- ks_submit_pods' rules, each defined once --------------------------------------------------
+constexpr int64_t kNever = std::numeric_limits<int64_t>::max();
+// the arrival the bind-tick recurrence uses: a pod submitted late arrives at the next tick
+int64_t eff_arrival(int64_t arrival, int64_t tick) { return std::max(arrival, tick + 1); }
+// FIFO, one pod per tick: the bind tick of the pod after one bound at prev
+int64_t bind_tick(int64_t prev, int64_t arrival, int64_t tick) { return std::max(prev + 1, eff_arrival(arrival, tick)); }
+// Σ seconds of phases [lo, hi): S wraps int32 as Pod.totalSeconds does (kubesim/pod/pod.go:155-162), wide
+// does not; cum (optional) takes the wrapping running sums
+struct PhaseSum { int32_t S; int64_t wide; bool nonneg; };
+PhaseSum phase_sum(const int32_t* sec, int32_t lo, int32_t hi, int32_t* cum = nullptr) {
+    uint32_t acc = 0;
+    PhaseSum s{0, 0, true};
+    for (int32_t f = lo; f < hi; f++) {
+        acc += (uint32_t)sec[f];
+        s.wide += sec[f];
+        s.nonneg &= sec[f] >= 0;
+        if (cum) cum[f] = (int32_t)acc;
+    }
+    s.S = (int32_t)acc;
+    return s;
+}
+// the ticks a pod of S total seconds runs: while (t - t0) * tick < S, i.e. ceil(S / tick); none for S <= 0
+int64_t run_ticks(int32_t S, int64_t tick_seconds) { return S > 0 ? ((int64_t)S + tick_seconds - 1) / tick_seconds : 0; }
+
 }  // namespace
 
 extern "C" {
@@ -316,12 +360,15 @@ ks_status ks_create(const ks_config* cfg, ks_engine** out) {
     const ks_status v = engine_init(cfg, &e);
     if (v != KS_OK) return v;
     hipError_t r = hipSetDevice(e->device);
-    if (r == hipSuccess) r = hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking);
-    if (r == hipSuccess) r = hipMalloc(&e->d_ctr, 32 * sizeof(int64_t));
-    if (r == hipSuccess) r = hipHostMalloc(&e->h_ctr, 32 * sizeof(int64_t), hipHostMallocDefault);
-    if (r == hipSuccess) r = hipMalloc(&e->d_args, sizeof(ks::EngineArgs));
-    if (r == hipSuccess) r = hipHostMalloc(&e->h_args, sizeof(ks::EngineArgs), hipHostMallocDefault);
-    for (int i = 0; i < 4 && r == hipSuccess; i++) r = hipEventCreate(&e->ev[i]);
+    if (r == hipSuccess) r = ks_own::stream_create(e->own.st);
+    if (r == hipSuccess) r = ks_own::dev_alloc(e->own.d_ctr, 32);
+    if (r == hipSuccess) r = ks_own::pinned_alloc(e->own.h_ctr, 32);
+    if (r == hipSuccess) r = ks_own::dev_alloc(e->own.d_args, 1);
+    if (r == hipSuccess) r = ks_own::pinned_alloc(e->own.h_args, 1);
+    for (int i = 0; i < 4 && r == hipSuccess; i++) r = ks_own::event_create(e->ev[i]);
+    if (r == hipSuccess) r = ks_own::event_create(e->stage_ev, hipEventDisableTiming);
+    e->st = e->own.st; e->d_ctr = e->own.d_ctr; e->h_ctr = e->own.h_ctr;  // the views of its own
+    e->d_args = e->own.d_args; e->h_args = e->own.h_args;
     if (r == hipSuccess) r = hipMemsetAsync(e->d_ctr, 0, 32 * sizeof(int64_t), e->st);
     if (r == hipSuccess) r = hipStreamSynchronize(e->st);
     if (r != hipSuccess) {
@@ -331,69 +378,6 @@ ks_status ks_create(const ks_config* cfg, ks_engine** out) {
     *out = e;
     return KS_OK;
 }
-
-}  // extern "C"
-
-namespace {
-
-void engine_free(ks_engine* e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    if (e->st) (void)hipStreamSynchronize(e->st);
-    if (e->st2) (void)hipStreamSynchronize(e->st2);  // (the pipelined chain's side passes read the buffers below)
-    e->pods.release(); e->dur.release(); e->b_node.release(); e->b_status.release();
-    e->phase_off.release(); e->cum_sec.release(); e->exp_pod.release(); e->exp_off.release();
-    e->t0.release(); e->fin.release(); e->use.release(); e->expired.release(); e->exp_pos.release();
-    e->preg.release(); e->d_blk.release(); e->d_digest.release(); e->srec.release();
-    e->d_qs.release(); e->d_qi.release();
-    if (e->node_mem) (void)hipFree(e->node_mem);
-    if (e->d_ncst) (void)hipFree(e->d_ncst);
-    if (e->lists) (void)hipFree(e->lists);
-    if (e->cand) (void)hipFree(e->cand);
-    if (e->cand_all) (void)hipFree(e->cand_all);
-    if (e->lbit) (void)hipFree(e->lbit);
-    if (e->lthr) (void)hipFree(e->lthr);
-    if (e->comm) (void)ncclCommDestroy(e->comm);
-    if (e->h_xbuf) (void)hipHostFree(e->h_xbuf);
-    if (e->st_copy) { (void)hipStreamSynchronize(e->st_copy); (void)hipStreamDestroy(e->st_copy); }
-    if (e->snap_ev) (void)hipEventDestroy(e->snap_ev);
-    if (e->h_bnode) (void)hipHostFree(e->h_bnode);
-    if (e->h_bstat) (void)hipHostFree(e->h_bstat);
-    if (!e->group) {
-        if (e->d_ctr) (void)hipFree(e->d_ctr);
-        if (e->h_ctr) (void)hipHostFree(e->h_ctr);
-        if (e->d_args) (void)hipFree(e->d_args);
-        if (e->h_args) (void)hipHostFree(e->h_args);
-    }
-    if (e->d_mask) (void)hipFree(e->d_mask);
-    if (e->d_score) (void)hipFree(e->d_score);
-    if (e->d_sweep) (void)hipFree(e->d_sweep);
-    if (e->d_eidx) (void)hipFree(e->d_eidx);
-    if (e->d_nslot) (void)hipFree(e->d_nslot);
-    if (e->d_first) (void)hipFree(e->d_first);
-    if (e->d_spec) (void)hipFree(e->d_spec);
-    if (e->d_args_spec) (void)hipFree(e->d_args_spec);
-    if (e->h_args_spec) (void)hipHostFree(e->h_args_spec);
-    if (e->d_args_full) (void)hipFree(e->d_args_full);
-    if (e->h_args_full) (void)hipHostFree(e->h_args_full);
-    if (e->pev_m) (void)hipEventDestroy(e->pev_m);
-    if (e->pev_x) (void)hipEventDestroy(e->pev_x);
-    if (e->st2) (void)hipStreamDestroy(e->st2);
-    if (e->d_usage) (void)hipFree(e->d_usage);
-    if (e->stage) (void)hipHostFree(e->stage);
-    if (e->segs) (void)hipHostFree(e->segs);
-    if (e->stage_ev) (void)hipEventDestroy(e->stage_ev);
-    if (e->d_tick) (void)hipFree(e->d_tick);
-    if (e->h_tick) (void)hipHostFree(e->h_tick);
-    for (auto ev : e->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : e->prof_ev) (void)hipEventDestroy(ev);
-    if (e->st && !e->group) (void)hipStreamDestroy(e->st);
-    delete e;
-}
-
-}  // namespace
-
-extern "C" {
 
 // a group's members are destroyed with their group (ks_group_destroy)
 void ks_destroy(ks_engine* e) {
@@ -420,11 +404,8 @@ ks_status ks_shard(ks_engine* e, int32_t world, int32_t rank, const uint8_t* id,
     if (id) {
         ncclUniqueId uid;
         std::memcpy(&uid, id, sizeof uid);
-        const ncclResult_t r = ncclCommInitRank(&e->comm, world, uid, rank);
-        if (r != ncclSuccess) {
-            e->comm = nullptr;
-            return fail(e, KS_EDEVICE, "ncclCommInitRank: %s", ncclGetErrorString(r));
-        }
+        const ncclResult_t r = ks_own::comm_init(e->comm, world, uid, rank);
+        if (r != ncclSuccess) return fail(e, KS_EDEVICE, "ncclCommInitRank: %s", ncclGetErrorString(r));
     }
     e->world = world;
     e->rank = rank;
@@ -508,17 +489,15 @@ ks_status ks_load_nodes(ks_engine* e, int64_t n, const int64_t* alloc, const uin
         h[8 * np + i] = real ? (int64_t)taint[i] : 0;
         h[9 * np + i] = real ? (int64_t)label[i] : 0;
     }
-    HIPCHK(e, hipMalloc(&e->node_mem, sizeof(int64_t) * 10 * np));
+    HIPCHK(e, ks_own::dev_alloc(e->node_mem, 10 * np));
     HIPCHK(e, hipMemcpyAsync(e->node_mem, h.data(), sizeof(int64_t) * 10 * np, hipMemcpyHostToDevice, e->st));
-    HIPCHK(e, hipMalloc(&e->d_ncst, sizeof(uint4) * 2 * np));
-    int64_t* b = (int64_t*)e->node_mem;
+    HIPCHK(e, ks_own::dev_alloc(e->d_ncst, 2 * np));
+    int64_t* b = e->node_mem;
     e->s.ac = b; e->s.am = b + np; e->s.ag = b + 2 * np; e->s.ap = b + 3 * np;
     e->s.rc = b + 4 * np; e->s.rm = b + 5 * np; e->s.rg = b + 6 * np; e->s.nr = b + 7 * np;
     e->s.taint = (uint64_t*)(b + 8 * np); e->s.label = (uint64_t*)(b + 9 * np);
     e->dc.n_nodes = (int32_t)n;
     e->dc.nwb = e->nwb;
-    // pods per scan workgroup: the most pod reuse per node load that still leaves >= ~2048
-    // workgroups (8 per CU) per scan
     e->nblk = (int)((e->n_pad + ks::block_nodes() - 1) / ks::block_nodes());
     const int G = e->world * e->vsh;
     e->part_lo.assign(G + 1, 0);
@@ -548,13 +527,13 @@ ks_status ks_load_nodes(ks_engine* e, int64_t n, const int64_t* alloc, const uin
     // (the two-launch chain's engines may scan lists of kTopLOverlap keys: ks_plan.h plan_step)
     // (and the pipelined sharded engines': every sharded engine may)
     const int lmax = (G == 1 && e->blk_n <= kOverlapMaxBlocks) || G > 1 ? ks::kTopLOverlap : ks::kTopL;
-    HIPCHK(e, hipMalloc(&e->lists, sizeof(uint64_t) * (size_t)e->B * e->nblk * lmax));
-    HIPCHK(e, hipMalloc(&e->cand, sizeof(uint64_t) * (size_t)e->B * ks::kTopL));
-    if (G > 1) HIPCHK(e, hipMalloc(&e->cand_all, sizeof(uint64_t) * (size_t)G * e->B * ks::kTopLOverlap));
-    if (G > 1 && e->xfn) HIPCHK(e, hipHostMalloc(&e->h_xbuf, sizeof(uint64_t) * (size_t)G * e->B * ks::kTopLOverlap, hipHostMallocDefault));
-    HIPCHK(e, hipMalloc(&e->d_mask, std::max<int64_t>(n, 1)));
-    HIPCHK(e, hipMalloc(&e->d_score, sizeof(int64_t) * std::max<int64_t>(n, 1)));
-    HIPCHK(e, hipMalloc(&e->d_usage, sizeof(unsigned long long) * 3 * std::max<int64_t>(n, 1)));
+    HIPCHK(e, ks_own::dev_alloc(e->lists, (size_t)e->B * e->nblk * lmax));
+    HIPCHK(e, ks_own::dev_alloc(e->cand, (size_t)e->B * ks::kTopL));
+    if (G > 1) HIPCHK(e, ks_own::dev_alloc(e->cand_all, (size_t)G * e->B * ks::kTopLOverlap));
+    if (G > 1 && e->xfn) HIPCHK(e, ks_own::pinned_alloc(e->h_xbuf, (size_t)G * e->B * ks::kTopLOverlap));
+    HIPCHK(e, ks_own::dev_alloc(e->d_mask, std::max<int64_t>(n, 1)));
+    HIPCHK(e, ks_own::dev_alloc(e->d_score, std::max<int64_t>(n, 1)));
+    HIPCHK(e, ks_own::dev_alloc(e->d_usage, 3 * std::max<int64_t>(n, 1)));
     HIPCHK(e, hipStreamSynchronize(e->st));
     e->nodes_loaded = true;
     return KS_OK;
@@ -587,42 +566,33 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
         if (phase_use[f] < 0 || phase_use[f] >= kMaxValue) return fail(e, KS_EINVAL, "usage out of range");
     // the int32 passed-seconds domain (kubesim/pod/pod.go:148-153): every bind tick must stay
     // within 2^31 seconds of the run's first bind
-    {
-        int64_t pb = e->P ? e->h_bind_tick[e->P - 1] : e->tick;
-        const int64_t first = e->P ? e->h_bind_tick[0] : std::max<int64_t>(pb + 1, std::max<int64_t>(arrival[0], e->tick + 1));
-        for (int64_t i = 0; i < m; i++) {
-            pb = std::max<int64_t>(pb + 1, std::max<int64_t>(arrival[i], e->tick + 1));
-            if (!in_passed_domain(e, first, pb))
-                return fail(e, KS_ERANGE, "pod %lld: bind tick %lld is %lld ticks after the first bind (tick %lld): "
-                            "(t - t0) * %d s reaches 2^31 and Go's int32(passed seconds) leaves its domain",
-                            (long long)(e->P + i), (long long)pb, (long long)(pb - first), (long long)first,
-                            e->cfg.tick_seconds);
-        }
+    const int64_t last_bind = e->P ? e->h_bind_tick[e->P - 1] : e->tick;
+    const int64_t first = e->P ? e->h_bind_tick[0] : bind_tick(last_bind, arrival[0], e->tick);
+    for (int64_t i = 0, pb = last_bind; i < m; i++) {
+        pb = bind_tick(pb, arrival[i], e->tick);
+        if (!in_passed_domain(e, first, pb))
+            return fail(e, KS_ERANGE, "pod %lld: bind tick %lld is %lld ticks after the first bind (tick %lld): "
+                        "(t - t0) * %d s reaches 2^31 and Go's int32(passed seconds) leaves its domain",
+                        (long long)(e->P + i), (long long)pb, (long long)(pb - first), (long long)first,
+                        e->cfg.tick_seconds);
     }
     // Pod keys: a Store over a same-key pod that is still running on the chosen node would drop
     // that pod from the node's totals (kubesim/node/node.go:58).  Refuse the one case where that
     // can happen — an earlier pod with the key may still run at this pod's bind tick — so every
     // accepted trace schedules exactly as the reference (ks_engine.h, ks_submit_pods).
     std::unordered_map<int64_t, int64_t> new_end;  // this call's keys -> latest run end
-    if (key_id) {
-        int64_t pb = e->P ? e->h_bind_tick[e->P - 1] : e->tick;
-        for (int64_t i = 0; i < m; i++) {
-            const int64_t bt = std::max<int64_t>(pb + 1, std::max<int64_t>(arrival[i], e->tick + 1));
-            pb = bt;
-            int64_t prev = std::numeric_limits<int64_t>::min();
-            auto it = new_end.find(key_id[i]);
-            if (it != new_end.end()) prev = it->second;
-            else if (auto jt = e->key_end.find(key_id[i]); jt != e->key_end.end()) prev = jt->second;
-            if (prev > bt)
-                return fail(e, KS_ERANGE, "pod %lld: key %lld reused at bind tick %lld while an earlier pod with it may run "
-                            "until tick %lld (Store would replace a running pod: outside the exact domain)",
-                            (long long)(e->P + i), (long long)key_id[i], (long long)bt, (long long)prev);
-            uint32_t acc = 0;
-            for (int32_t f = phase_off[i]; f < phase_off[i + 1]; f++) acc += (uint32_t)phase_sec[f];
-            const int32_t S = (int32_t)acc;
-            const int64_t d = S > 0 ? ((int64_t)S + e->cfg.tick_seconds - 1) / e->cfg.tick_seconds : 0;
-            new_end[key_id[i]] = std::max(prev, bt + d);
-        }
+    for (int64_t i = 0, bt = last_bind; key_id && i < m; i++) {
+        bt = bind_tick(bt, arrival[i], e->tick);
+        int64_t prev = std::numeric_limits<int64_t>::min();
+        auto it = new_end.find(key_id[i]);
+        if (it != new_end.end()) prev = it->second;
+        else if (auto jt = e->key_end.find(key_id[i]); jt != e->key_end.end()) prev = jt->second;
+        if (prev > bt)
+            return fail(e, KS_ERANGE, "pod %lld: key %lld reused at bind tick %lld while an earlier pod with it may run "
+                        "until tick %lld (Store would replace a running pod: outside the exact domain)",
+                        (long long)(e->P + i), (long long)key_id[i], (long long)bt, (long long)prev);
+        const int32_t S = phase_sum(phase_sec, phase_off[i], phase_off[i + 1]).S;
+        new_end[key_id[i]] = std::max(prev, bt + run_ticks(S, e->cfg.tick_seconds));
     }
 
     {
@@ -653,18 +623,15 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
     }
     std::vector<ks::PodRec> recs(m);
     std::vector<ks::ScanRec> srecs(m);
-    std::vector<int32_t> dur(m), poff(m), cum(nf);
-    std::vector<int64_t> t0(m), fin(m), eoff(m);
-    std::vector<int32_t> tsec(m);
-    std::vector<int64_t> run_end(m);
+    std::vector<int32_t> dur(m), poff(m), cum(nf), tsec(m), neg(m, -1), epod;
+    std::vector<int64_t> t0(m), fin(m), eoff(m), run_end(m);
     std::vector<int64_t> arr_eff(m);  // the arrival the recurrence uses (ks_cluster_series' pending column)
-    std::vector<uint8_t> reg(m);
-    std::vector<int32_t> epod;
+    std::vector<uint8_t> reg(m), zero(m, 0);
     epod.reserve(m);
     const int64_t epod_base = e->exp_pod.n;
     e->h_exp_pos.resize(e->P + m, -1);
     int64_t pos_lo = e->P;  // lowest pod whose expiry position changed
-    int64_t prev_bind = e->P ? e->h_bind_tick[e->P - 1] : e->tick;
+    int64_t prev_bind = last_bind;
     for (int64_t i = 0; i < m; i++) {
         const int64_t j = e->P + i;
         ks::PodRec& r = recs[i];
@@ -675,29 +642,18 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
         r.keymask = km;
         r.flags = flags ? flags[i] : 0;
         srecs[i] = ks::scan_rec_micro(e->dc, r);
-        const int64_t arr = std::max<int64_t>(arrival[i], e->tick + 1);
-        const int64_t bt = std::max<int64_t>(prev_bind + 1, arr);
-        prev_bind = bt;
-        arr_eff[i] = arr;
-        uint32_t acc = 0;  // int32 wrapping, kubesim/pod/pod.go:155-162
-        int64_t acc64 = 0;
-        bool nonneg = true;
-        for (int32_t f = phase_off[i]; f < phase_off[i + 1]; f++) {
-            acc += (uint32_t)phase_sec[f];
-            acc64 += phase_sec[f];
-            nonneg &= phase_sec[f] >= 0;
-            cum[f] = (int32_t)acc;
-        }
-        const int32_t S = (int32_t)acc;
-        tsec[i] = S;
-        const int64_t d = S > 0 ? ((int64_t)S + e->cfg.tick_seconds - 1) / e->cfg.tick_seconds : 0;
+        arr_eff[i] = eff_arrival(arrival[i], e->tick);
+        const int64_t bt = prev_bind = bind_tick(prev_bind, arrival[i], e->tick);
+        const PhaseSum ps = phase_sum(phase_sec, phase_off[i], phase_off[i + 1], cum.data());
+        const int64_t d = run_ticks(ps.S, e->cfg.tick_seconds);
+        tsec[i] = ps.S;
         dur[i] = (int32_t)d;
         t0[i] = bt;
         fin[i] = d > 0 ? bt + d : kNever;
         run_end[i] = bt + d;
         // the digest's segment form: cumulative seconds non-decreasing and (t - t0) * tick never
         // wraps int32 while the pod runs (else the exact per-tick form)
-        reg[i] = nonneg && acc64 <= (int64_t)INT32_MAX - e->cfg.tick_seconds;
+        reg[i] = ps.nonneg && ps.wide <= (int64_t)INT32_MAX - e->cfg.tick_seconds;
         poff[i] = (int32_t)(e->F + phase_off[i]);
         // expiries due before pod j binds: finish tick in (bind_tick[j-1], bind_tick[j]]
         while (!e->pending.empty() && e->pending.top().first <= bt) {
@@ -711,62 +667,48 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
         if (d > 0) e->pending.push({fin[i], j});
     }
     // device uploads: small submits (a drop-in's per-tick calls) are staged in pinned memory and
-    // applied by the next launch (no copy call, no synchronisation here); large ones are copied
+    // applied by the next launch (no copy call, no synchronisation here); large ones are copied.  Either
+    // way the rows go behind the device arrays they extend in one order: app(v, h, k) appends the k rows at h to v
     hipStream_t st = e->st;
     HIPCHK(e, hipSetDevice(e->device));
-    std::vector<int32_t> neg(m, -1);
-    std::vector<uint8_t> zero(m, 0);
     const int32_t tail = (int32_t)(e->F + nf);
-    const int64_t z0 = 0;
-    if (!e->group && m <= kStageMaxPods) {
-        HIPCHK(e, stage_append(e, e->pods, recs.data(), m));
-        HIPCHK(e, stage_append(e, e->srec, srecs.data(), m));
-        HIPCHK(e, stage_append(e, e->dur, dur.data(), m));
-        HIPCHK(e, stage_append(e, e->t0, t0.data(), m));
-        HIPCHK(e, stage_append(e, e->fin, fin.data(), m));
-        HIPCHK(e, stage_append(e, e->b_node, neg.data(), m));
-        HIPCHK(e, stage_append(e, e->b_status, neg.data(), m));
-        HIPCHK(e, stage_append(e, e->expired, zero.data(), m));
-        HIPCHK(e, stage_append(e, e->preg, reg.data(), m));
+    const int64_t z0 = 0, P1 = e->P + m;
+    auto rows = [&](auto app) -> ks_status {
+        HIPCHK(e, app(e->pods, recs.data(), m));
+        HIPCHK(e, app(e->srec, srecs.data(), m));
+        HIPCHK(e, app(e->dur, dur.data(), m));
+        HIPCHK(e, app(e->t0, t0.data(), m));
+        HIPCHK(e, app(e->fin, fin.data(), m));
+        HIPCHK(e, app(e->b_node, neg.data(), m));
+        HIPCHK(e, app(e->b_status, neg.data(), m));
+        HIPCHK(e, app(e->expired, zero.data(), m));
+        HIPCHK(e, app(e->preg, reg.data(), m));
         if (e->phase_off.n) e->phase_off.n -= 1;  // phase_off holds P+1 entries: overwrite the sentinel
-        HIPCHK(e, stage_append(e, e->phase_off, poff.data(), m));
-        HIPCHK(e, stage_append(e, e->phase_off, &tail, 1));
-        HIPCHK(e, stage_append(e, e->cum_sec, cum.data(), nf));
-        HIPCHK(e, stage_append(e, e->use, phase_use, nf * 3));
-        if (e->exp_off.n == 0) HIPCHK(e, stage_append(e, e->exp_off, &z0, 1));
-        HIPCHK(e, stage_append(e, e->exp_off, eoff.data(), m));
-        HIPCHK(e, stage_append(e, e->exp_pod, epod.data(), (int64_t)epod.size()));
-        if (e->exp_pos.cap < e->P + m) {
+        HIPCHK(e, app(e->phase_off, poff.data(), m));
+        HIPCHK(e, app(e->phase_off, &tail, 1));
+        HIPCHK(e, app(e->cum_sec, cum.data(), nf));
+        HIPCHK(e, app(e->use, phase_use, nf * 3));
+        if (e->exp_off.n == 0) HIPCHK(e, app(e->exp_off, &z0, 1));
+        HIPCHK(e, app(e->exp_off, eoff.data(), m));
+        HIPCHK(e, app(e->exp_pod, epod.data(), (int64_t)epod.size()));
+        return KS_OK;
+    };
+    if (!e->group && m <= kStageMaxPods) {
+        if (ks_status r = rows([&](auto& v, const auto* h, int64_t k) { return stage_append(e, v, h, k); }); r != KS_OK) return r;
+        if (e->exp_pos.cap < P1) {
             HIPCHK(e, stage_flush(e));
-            HIPCHK(e, e->exp_pos.reserve(e->P + m, st));
+            HIPCHK(e, e->exp_pos.reserve(P1, st));
         }
         e->xpos_lo = std::min(e->xpos_lo, pos_lo);  // staged at the next flush (stage_xpos)
-        e->exp_pos.n = e->P + m;
     } else {
         HIPCHK(e, stage_flush(e));
-        HIPCHK(e, e->pods.append(recs.data(), m, st));
-        HIPCHK(e, e->srec.append(srecs.data(), m, st));
-        HIPCHK(e, e->dur.append(dur.data(), m, st));
-        HIPCHK(e, e->t0.append(t0.data(), m, st));
-        HIPCHK(e, e->fin.append(fin.data(), m, st));
-        HIPCHK(e, e->b_node.append(neg.data(), m, st));
-        HIPCHK(e, e->b_status.append(neg.data(), m, st));
-        HIPCHK(e, e->expired.append(zero.data(), m, st));
-        HIPCHK(e, e->preg.append(reg.data(), m, st));
-        if (e->phase_off.n) e->phase_off.n -= 1;  // phase_off holds P+1 entries: overwrite the sentinel
-        HIPCHK(e, e->phase_off.append(poff.data(), m, st));
-        HIPCHK(e, e->phase_off.append(&tail, 1, st));
-        HIPCHK(e, e->cum_sec.append(cum.data(), nf, st));
-        HIPCHK(e, e->use.append(phase_use, nf * 3, st));
-        if (e->exp_off.n == 0) HIPCHK(e, e->exp_off.append(&z0, 1, st));
-        HIPCHK(e, e->exp_off.append(eoff.data(), m, st));
-        HIPCHK(e, e->exp_pod.append(epod.data(), (int64_t)epod.size(), st));
-        HIPCHK(e, e->exp_pos.reserve(e->P + m, st));
-        HIPCHK(e, hipMemcpyAsync(e->exp_pos.p + pos_lo, e->h_exp_pos.data() + pos_lo, sizeof(int64_t) * (e->P + m - pos_lo),
+        if (ks_status r = rows([&](auto& v, const auto* h, int64_t k) { return v.append(h, k, st); }); r != KS_OK) return r;
+        HIPCHK(e, e->exp_pos.reserve(P1, st));
+        HIPCHK(e, hipMemcpyAsync(e->exp_pos.p + pos_lo, e->h_exp_pos.data() + pos_lo, sizeof(int64_t) * (P1 - pos_lo),
                                  hipMemcpyHostToDevice, st));
-        e->exp_pos.n = e->P + m;
         HIPCHK(e, hipStreamSynchronize(st));  // host staging vectors die here
     }
+    e->exp_pos.n = P1;
     e->h_pods.insert(e->h_pods.end(), recs.begin(), recs.end());
     e->h_exp_pod.insert(e->h_exp_pod.end(), epod.begin(), epod.end());
     e->h_expired.resize(e->P + m, 0);
@@ -797,47 +739,6 @@ ks_status ks_submit_pods(ks_engine* e, int64_t m, const int64_t* arrival, const 
     return KS_OK;
 }
 
-}  // extern "C"
-
-// Apply every not-yet-applied expiry with finish tick <= the current tick (ks_filter / ks_score
-// see the state Run's next scheduleOne would).  While the run is live the host knows them
-// exactly: every expiry attached to a pod < done has been applied (mirror_expired), an expiry
-// attached to a later pod j > done finishes after bind_tick[j - 1] >= bind_tick[done] > tick, so
-// only the next pod's attached expiries and the unattached ones (pending, when every submitted pod
-// is bound) can be due — usually none, and no launch is made.
-ks_status ks_host::flush_expiries(ks_engine* e) {
-    if (e->err == KS_OK) {
-        std::vector<int32_t> qs;
-        auto add = [&](int64_t q) {
-            if (e->h_status[q] == KS_POD_OK && !e->h_expired[q] && e->h_fin[q] <= e->tick) qs.push_back((int32_t)q);
-        };
-        if (e->done < e->P)
-            for (int64_t u = e->h_exp_off[e->done]; u < e->h_exp_off[e->done + 1]; u++) add(e->h_exp_pod[u]);
-        e->pending.for_each_due(e->tick, add);
-        if ((int)qs.size() <= ks::kTickMaxExp) {
-            if (!qs.empty()) {
-                ks::ExpList L{};
-                for (int32_t q : qs) {
-                    ks::TickExp& x = L.x[L.n++];
-                    x.node = e->h_node[q];
-                    x.q = q;
-                    for (int k = 0; k < 3; k++) x.req[k] = e->h_pods[q].req[k];
-                }
-                HIPCHK(e, ks::launch_apply_exp(e->s, e->expired.p, L, e->st));
-            }
-        } else {
-            HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
-                                       e->expired.p, e->st));
-        }
-        for (int32_t q : qs) e->h_expired[q] = 1;
-        return KS_OK;
-    }
-    HIPCHK(e, ks::launch_flush(e->s, e->pods.p, e->fin.p, e->tick, e->done, e->b_node.p, e->b_status.p,
-                               e->expired.p, e->st));
-    return KS_OK;
-}
-
-extern "C" {
 
 // Scenario groups (struct ks_group: ks_host.h; ks_group_step: ks_step.cpp)
 ks_status ks_group_create(int32_t device, int32_t max_scenarios, ks_group** out) {
@@ -847,16 +748,17 @@ ks_status ks_group_create(int32_t device, int32_t max_scenarios, ks_group** out)
     g->device = device;
     g->cap = max_scenarios;
     hipError_t r = hipSetDevice(device);
-    if (r == hipSuccess) r = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking);
-    if (r == hipSuccess) r = hipStreamCreateWithFlags(&g->st2, hipStreamNonBlocking);
-    if (r == hipSuccess) r = hipEventCreateWithFlags(&g->xev, hipEventDisableTiming);
-    if (r == hipSuccess) r = hipMalloc(&g->d_ctr, sizeof(int64_t) * 32 * max_scenarios);
-    if (r == hipSuccess) r = hipHostMalloc(&g->h_ctr, sizeof(int64_t) * 32 * max_scenarios, hipHostMallocDefault);
-    if (r == hipSuccess) r = hipMalloc(&g->d_args, sizeof(ks::EngineArgs) * max_scenarios);
-    if (r == hipSuccess) r = hipHostMalloc(&g->h_args, sizeof(ks::EngineArgs) * max_scenarios, hipHostMallocDefault);
-    if (r == hipSuccess) r = hipMalloc(&g->d_seg, sizeof(ks::BindSeg) * max_scenarios);
-    if (r == hipSuccess) r = hipHostMalloc(&g->h_seg, sizeof(ks::BindSeg) * max_scenarios, hipHostMallocDefault);
-    for (int i = 0; i < 2 && r == hipSuccess; i++) r = hipEventCreate(&g->ev[i]);
+    const size_t S = (size_t)max_scenarios;
+    if (r == hipSuccess) r = ks_own::stream_create(g->st);
+    if (r == hipSuccess) r = ks_own::stream_create(g->st2);
+    if (r == hipSuccess) r = ks_own::event_create(g->xev, hipEventDisableTiming);
+    if (r == hipSuccess) r = ks_own::dev_alloc(g->d_ctr, 32 * S);
+    if (r == hipSuccess) r = ks_own::pinned_alloc(g->h_ctr, 32 * S);
+    if (r == hipSuccess) r = ks_own::dev_alloc(g->d_args, S);
+    if (r == hipSuccess) r = ks_own::pinned_alloc(g->h_args, S);
+    if (r == hipSuccess) r = ks_own::dev_alloc(g->d_seg, S);
+    if (r == hipSuccess) r = ks_own::pinned_alloc(g->h_seg, S);
+    for (int i = 0; i < 2 && r == hipSuccess; i++) r = ks_own::event_create(g->ev[i]);
     if (r == hipSuccess) r = hipMemsetAsync(g->d_ctr, 0, sizeof(int64_t) * 32 * max_scenarios, g->st);
     if (r == hipSuccess) r = hipStreamSynchronize(g->st);
     if (r != hipSuccess) {
@@ -872,19 +774,7 @@ void ks_group_destroy(ks_group* g) {
     (void)hipSetDevice(g->device);
     if (g->st) (void)hipStreamSynchronize(g->st);
     for (ks_engine* e : g->engs) engine_free(e);
-    if (g->d_ctr) (void)hipFree(g->d_ctr);
-    if (g->h_ctr) (void)hipHostFree(g->h_ctr);
-    if (g->d_args) (void)hipFree(g->d_args);
-    if (g->h_args) (void)hipHostFree(g->h_args);
-    if (g->d_seg) (void)hipFree(g->d_seg);
-    if (g->h_seg) (void)hipHostFree(g->h_seg);
-    if (g->d_out) (void)hipFree(g->d_out);
-    if (g->h_out) (void)hipHostFree(g->h_out);
     if (g->st2) (void)hipStreamSynchronize(g->st2);
-    for (auto ev : g->ev) if (ev) (void)hipEventDestroy(ev);
-    if (g->xev) (void)hipEventDestroy(g->xev);
-    if (g->st2) (void)hipStreamDestroy(g->st2);
-    if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
 }
 
@@ -898,13 +788,10 @@ ks_status ks_group_add(ks_group* g, const ks_config* cfg, ks_engine** out) {
     if (v != KS_OK) return v;
     const int idx = (int)g->engs.size();
     e->group = g;
-    e->st = g->st;
-    e->d_ctr = g->d_ctr + 32 * idx;
-    e->h_ctr = g->h_ctr + 32 * idx;
-    e->d_args = g->d_args + idx;
-    e->h_args = g->h_args + idx;
+    e->st = g->st; e->d_ctr = g->d_ctr + 32 * idx; e->h_ctr = g->h_ctr + 32 * idx;  // the views of the group's
+    e->d_args = g->d_args + idx; e->h_args = g->h_args + idx;
     hipError_t r = hipSetDevice(g->device);
-    for (int i = 0; i < 4 && r == hipSuccess; i++) r = hipEventCreate(&e->ev[i]);
+    for (int i = 0; i < 4 && r == hipSuccess; i++) r = ks_own::event_create(e->ev[i]);
     if (r != hipSuccess) {
         engine_free(e);
         return KS_EDEVICE;
@@ -954,14 +841,14 @@ const char* ks_build_id(void) { return KS_SRC_HASH; }
 ks_status ks_debug_invariants(ks_engine* e, int64_t* out4) {
     if (!e || !out4) return KS_EINVAL;
     out4[0] = out4[1] = out4[2] = out4[3] = 0;
-    if (!e->d_sweep) return KS_OK;  // (no chunk-resolver batch ran: nothing to check)
+    if (!e->win) return KS_OK;  // (no chunk-resolver batch ran: nothing to check)
     HIPCHK(e, hipSetDevice(e->device));
     std::vector<int32_t> ns(e->n_pad), ei(e->n_pad), fi(e->n_pad);
     int32_t hw = 0;
-    HIPCHK(e, hipMemcpyAsync(ns.data(), e->d_nslot, sizeof(int32_t) * e->n_pad, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipMemcpyAsync(fi.data(), e->d_first, sizeof(int32_t) * e->n_pad, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipMemcpyAsync(ei.data(), e->d_eidx, sizeof(int32_t) * e->n_pad, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipMemcpyAsync(&hw, &e->d_sweep->nslot_hw, sizeof hw, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(ns.data(), e->win->d_nslot, sizeof(int32_t) * e->n_pad, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(fi.data(), e->win->d_first, sizeof(int32_t) * e->n_pad, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(ei.data(), e->win->d_eidx, sizeof(int32_t) * e->n_pad, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(&hw, &e->win->d_sweep->nslot_hw, sizeof hw, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
     for (int64_t i = 0; i < e->n_pad; i++) {
         out4[0] += ns[i] != -1 || fi[i] != ks::kNoFirst;
@@ -975,9 +862,9 @@ ks_status ks_debug_invariants(ks_engine* e, int64_t* out4) {
 ks_status ks_debug_window(ks_engine* e, void* out, int64_t cap, int64_t* size_out) {
     if (!e || !size_out) return KS_EINVAL;
     *size_out = (int64_t)sizeof(ks::WinWS);
-    if (!e->d_sweep || !out || cap <= 0) return KS_OK;
+    if (!e->win || !out || cap <= 0) return KS_OK;
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(out, e->d_sweep, std::min<int64_t>(cap, sizeof(ks::WinWS)), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(out, e->win->d_sweep, std::min<int64_t>(cap, sizeof(ks::WinWS)), hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
     return KS_OK;
 }
@@ -985,10 +872,10 @@ ks_status ks_debug_window(ks_engine* e, void* out, int64_t cap, int64_t* size_ou
 ks_status ks_debug_watch(ks_engine* e, int64_t pod) {
     if (!e) return KS_EINVAL;
 #ifdef KS_BATCH_LOG
-    if (ks_status r = ensure_window_ws(e); r != KS_OK) return r;
+    if (ks_status r = ensure_window_ws(e); r != KS_OK || !e->win) return r != KS_OK ? r : KS_EINVAL;  // (chunk resolver only)
     const int32_t w[2] = {(int32_t)pod, 0};
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(&e->d_sweep->watch_pod, w, sizeof w, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipMemcpyAsync(&e->win->d_sweep->watch_pod, w, sizeof w, hipMemcpyHostToDevice, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
     return KS_OK;
 #else

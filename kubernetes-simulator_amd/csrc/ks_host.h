@@ -1,12 +1,12 @@
 // ks_host.h — the engine record and the few host functions its translation units share
 // (internal: ks_engine.cpp owns the engine's life cycle and loads it, ks_step.cpp steps it,
-// ks_queries.cpp answers about it after the fact).
+// ks_queries.cpp answers about it after the fact).  Every GPU resource of the engine and of a group
+// is held by an owner of ks_own.h and released by the record's destructor; what is allocated on first
+// use is a bundle in an optional slot, whole or absent (ks_own::build).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
 #include <algorithm>
 #include <functional>
+#include <optional>
 #include <queue>
 #include <string>
 #include <unordered_map>
@@ -14,9 +14,12 @@
 
 #include "../../include/ks_engine.h"
 #include "ks_device.h"
+#include "ks_own.h"
 #include "ks_plan.h"
 
 namespace ks_host {
+
+using namespace ks_own;
 
 constexpr int64_t kMaxValue = 1LL << 59;
 constexpr int kDefaultBatch = 256;
@@ -24,39 +27,34 @@ constexpr int64_t kUBlk = 256;   // usage index: pods per block (= the usage ker
 constexpr int64_t kUSup = 64;    // blocks per super block
 constexpr int64_t kMaxDigestTicks = 1 << 20;
 
-// Growable device array (stream-ordered copies on growth).
+// Growable device array (stream-ordered copies on growth); move-only, freed with its holder.
 template <typename T>
 struct DVec {
-    T* p = nullptr;
+    Dev<T> p;
     int64_t n = 0, cap = 0;
+    DVec() = default;
+    DVec(DVec&& o) noexcept { *this = std::move(o); }
+    DVec& operator=(DVec&& o) noexcept {
+        p = std::move(o.p), n = std::exchange(o.n, 0), cap = std::exchange(o.cap, 0);
+        return *this;
+    }
     hipError_t reserve(int64_t want, hipStream_t st) {
         if (want <= cap) return hipSuccess;
-        int64_t nc = std::max<int64_t>(want, std::max<int64_t>(cap * 2, 1024));
-        T* q = nullptr;
-        hipError_t e = hipMalloc(&q, sizeof(T) * nc);
-        if (e != hipSuccess) return e;
+        const int64_t nc = std::max<int64_t>(want, std::max<int64_t>(cap * 2, 1024));
+        Dev<T> q;  // (freed here when the copy of the old contents fails)
+        KS_TRY(ks_own::dev_alloc(q, nc));
         if (n) {
-            e = hipMemcpyAsync(q, p, sizeof(T) * n, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return e;
-            e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return e;
+            KS_TRY(hipMemcpyAsync(q, p, sizeof(T) * n, hipMemcpyDeviceToDevice, st));
+            KS_TRY(hipStreamSynchronize(st));
         }
-        if (p) (void)hipFree(p);
-        p = q;
+        p = std::move(q);
         cap = nc;
         return hipSuccess;
     }
     hipError_t append(const T* h, int64_t k, hipStream_t st) {
-        hipError_t e = reserve(n + k, st);
-        if (e != hipSuccess) return e;
-        if (k) e = hipMemcpyAsync(p + n, h, sizeof(T) * k, hipMemcpyHostToDevice, st);
+        KS_TRY(reserve(n + k, st));
         n += k;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = cap = 0;
+        return k ? hipMemcpyAsync(p + (n - k), h, sizeof(T) * k, hipMemcpyHostToDevice, st) : hipSuccess;
     }
 };
 
@@ -78,11 +76,49 @@ struct PendingHeap : std::priority_queue<std::pair<int64_t, int64_t>, std::vecto
     }
 };
 
+// ---- what an engine makes on first use: one bundle per slot of ks_engine, whole or absent ---------
+// pruned block lists (ks_scan.h): per-pod bitmaps of the blocks that wrote a list [2][B][nwl], thresholds [2][kThrCopies][B]
+struct PruneBits { Dev<uint64_t> lbit, lthr; };
+// the chunk resolver's batch window workspace, and the overlap of the next batch's scan with the
+// resolver: the speculative scan's counters, argument records (ctr = d_spec + parity), workgroups
+struct WindowWs {
+    Dev<ks::WinWS> d_sweep;
+    Dev<int32_t> d_eidx;   // node -> E index (n_pad, -1)
+    Dev<int32_t> d_nslot;  // node -> candidate slot of the batch (ks_cand.hip), -1
+    Dev<int32_t> d_first;  // node -> its first kept entry of the batch, kNoFirst
+    Dev<int64_t> d_spec;
+    Dev<ks::EngineArgs> d_args_spec;  // [2]: ctr = d_spec + kSpecStride * parity
+    Pinned<ks::EngineArgs> h_args_spec;
+    int scan_workers = 0;
+};
+// the pipelined sharded chain (batch_pipe): the next batch's speculative scan, part merges and exchange on a second
+// stream beside the resolve; a rescan scans every block locally (d_args_full: every block, the engine's own list set)
+struct PipeSet { Stream st2; Event pev_m, pev_x; Dev<ks::EngineArgs> d_args_full; Pinned<ks::EngineArgs> h_args_full; };
+// the per-tick path (ks_tick.hip): its scratch and its mapped result (h_tick.dev)
+struct TickSet { Dev<ks::TickScratch> d_tick; Pinned<ks::TickOut> h_tick; };
+// a batched step's read-back (step_body): the node and status words of its pods [done, p_hi), grown geometrically
+struct Readback { Pinned<int32_t> h_bnode, h_bstat; int64_t cap = 0; };
+// the copy stream and the event of the early read-back (ks_plan.h early_round)
+struct EarlyCopy { Stream st_copy; Event snap_ev; };
+// host-staged submits: rows for the device arrays in a mapped arena and the table of kSegCap segments naming
+// them, applied by one scatter (or by the per-tick kernel) before any device work reads them
+struct StageArena { Pinned<uint8_t> mem; int64_t cap = 0; Pinned<ks::CopySeg> segs; };
+constexpr int kSegCap = 1 << 16;
+// what ks_create makes for an engine of its own; a group's member borrows the group's (ks_group_add)
+struct EngineOwn { Stream st; Dev<int64_t> d_ctr; Pinned<int64_t> h_ctr; Dev<ks::EngineArgs> d_args; Pinned<ks::EngineArgs> h_args; };
+
 }  // namespace ks_host
 
 struct ks_engine {
-    template <typename T>
-    using DVec = ks_host::DVec<T>;
+    template <typename T> using DVec = ks_host::DVec<T>;
+    template <typename T> using Dev = ks_own::Dev<T>;
+    // The streams' owners first, the communicator right after: members are destroyed in reverse, so every
+    // buffer and event goes before the communicator and that before the streams (all waited for by engine_free).
+    ks_host::EngineOwn own;
+    std::optional<ks_host::PipeSet> pipe;
+    std::optional<ks_host::EarlyCopy> early;
+    ks_own::Comm comm;
+
     ks_config cfg{};
     ks::Cfg dc{};
     hipStream_t st = nullptr;
@@ -93,8 +129,8 @@ struct ks_engine {
     int64_t n = 0, n_pad = 0;
     int nwb = 0;
     bool nodes_loaded = false;
-    void* node_mem = nullptr;
-    uint4* d_ncst = nullptr;  // the node constants table (ks::EngineArgs::ncst), [n_pad][2]
+    Dev<int64_t> node_mem;  // [10][n_pad], the fields of s
+    Dev<uint4> d_ncst;      // the node constants table (ks::EngineArgs::ncst), [n_pad][2]
     ks::NodeSoA s{};
 
     // pods (device)
@@ -128,20 +164,15 @@ struct ks_engine {
     std::vector<ks::PodRec> h_pods;
     std::vector<int32_t> h_exp_pod;
     std::vector<uint8_t> h_expired;
-    // host-staged submits: rows for the device arrays in a pinned, device-visible arena, applied by
-    // one scatter (or by the per-tick kernel) before any device work reads them
-    uint8_t* stage = nullptr;           // pinned host arena
-    uint8_t* stage_dev = nullptr;       // its device address
-    int64_t stage_cap = 0, stage_used = 0;
-    ks::CopySeg* segs = nullptr;        // pinned segment table
-    ks::CopySeg* segs_dev = nullptr;
-    int seg_cap = 0, nseg = 0, seg_done = 0;
+    // host-staged submits: the arena (rebuilt larger when a submit outgrows it), its fill, the segments applied
+    std::optional<ks_host::StageArena> arena;
+    int64_t stage_used = 0;
+    int nseg = 0, seg_done = 0;
     int64_t xpos_lo = INT64_MAX;        // exp_pos rows [xpos_lo, P) changed since the last flush
-    hipEvent_t stage_ev = nullptr;      // recorded after the launch that consumed the last segments
-    // per-tick path (ks_tick.hip)
-    ks::TickScratch* d_tick = nullptr;
-    ks::TickOut* h_tick = nullptr;      // pinned, device-visible
-    ks::TickOut* h_tick_dev = nullptr;
+    // recorded after the launch that consumed the last segments.  ks_create makes it; a group's member has none
+    // and needs none: both its users, the staged submit path and the per-tick path, are closed to members
+    ks_own::Event stage_ev;
+    std::optional<ks_host::TickSet> tickset;  // per-tick path (ks_tick.hip)
     // name-keyed index over binds [0, idx_upto), extended on each query
     int64_t idx_upto = 0;
     std::vector<std::vector<int64_t>> node_pods;      // per node: every pod bound there, FIFO
@@ -157,68 +188,41 @@ struct ks_engine {
 
     // batch machinery
     int B = ks_host::kDefaultBatch, PG = 32;
-    uint64_t* lists = nullptr;
-    uint64_t* cand = nullptr;
+    Dev<uint64_t> lists, cand;
     int nblk = 0;
-    // node sharding
+    // node sharding (comm above: RCCL)
     int world = 1, rank = 0, vsh = 1;
-    ncclComm_t comm = nullptr;
     ks_allgather_fn xfn = nullptr;  // host exchange (ks_shard_host) instead of RCCL
     void* xuser = nullptr;
-    uint64_t* h_xbuf = nullptr;     // pinned [world][vsh][B][L]
+    ks_own::Pinned<uint64_t> h_xbuf;  // [world][vsh][B][L]
     std::vector<int> part_lo;  // [world * vsh + 1] block boundaries of the parts
     int blk_lo = 0, blk_n = 0;  // this rank's scan range
-    uint64_t* cand_all = nullptr;  // [world * vsh][B][L]
-    // pruned block lists (ks_scan.h): per-pod bitmaps of the blocks that wrote a list and thresholds
+    Dev<uint64_t> cand_all;  // [world * vsh][B][L]
+    // pruned block lists: in use (then bits is there), the words per bitmap
     bool prune = false;
     int L = ks::kTopL;  // the block lists' length (kTopLOverlap: the overlap's single-shard engines)
-    uint64_t* lbit = nullptr;  // [B][nwl]
-    uint64_t* lthr = nullptr;  // [2][kThrCopies][B]
+    std::optional<ks_host::PruneBits> bits;
     int nwl = 0;
-    int64_t* d_ctr = nullptr;
-    int64_t* h_ctr = nullptr;  // pinned ([8]: the early read-back's snapshot of the start counter)
-    // a batched step's read-back (ks_step.cpp step_body): the node and status words of the step's
-    // pods [done, p_hi), pinned, grown geometrically; the copy stream and the event of the early
-    // read-back (ks_plan.h early_round)
-    int32_t* h_bnode = nullptr;
-    int32_t* h_bstat = nullptr;
-    int64_t bind_cap = 0;
-    hipStream_t st_copy = nullptr;
-    hipEvent_t snap_ev = nullptr;
+    // views all code reads (with st): the counters ([8] of h_ctr: the early read-back's snapshot of the start
+    // counter), the kernels' argument record and its pinned host staging — own's, or the group's slots
+    int64_t *d_ctr = nullptr, *h_ctr = nullptr;
+    ks::EngineArgs *d_args = nullptr, *h_args = nullptr;
+    std::optional<ks_host::Readback> rb;
     // the last batched step's binds finished on the host before its last wait, and those of them that
     // came back below a snapshot, on the copy stream
     int64_t early_pods = 0, snap_pods = 0;
-    ks::EngineArgs* d_args = nullptr;  // the kernels' argument record (device)
-    ks::EngineArgs* h_args = nullptr;  // its pinned host staging
-    // overlap of the next batch's scan with the chunk resolver (chunk class, one shard): the
-    // speculative scan's argument records (ctr = d_spec + parity) and counters, its workgroups
-    bool overlap = true;
-    int scan_workers = 0;
-    int64_t* d_spec = nullptr;
-    ks::EngineArgs* d_args_spec = nullptr;  // [2]: ctr = d_spec + kSpecStride * parity
-    ks::EngineArgs* h_args_spec = nullptr;
-    // the pipelined sharded chain (round 6, ks_step.cpp batch_pipe): the next batch's speculative scan, per-part
-    // merges and exchange on a second stream beside the resolve; a rescan scans every block locally
-    // (d_args_full: the whole block range, the engine's own list set)
-    hipStream_t st2 = nullptr;
-    hipEvent_t pev_m = nullptr, pev_x = nullptr;
-    ks::EngineArgs* d_args_full = nullptr;
-    ks::EngineArgs* h_args_full = nullptr;
-    // group membership (ks_group_add): stream, counters and argument slots belong to the group
-    ks_group* group = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (kEvStepBegin ... kEvUsageEnd)
-    std::vector<hipEvent_t> prof_ev;
+    bool overlap = true;  // the next batch's scan beside the chunk resolver (chunk class)
+    std::optional<ks_host::WindowWs> win;
+    ks_group* group = nullptr;  // group membership (ks_group_add)
+    ks_own::Event ev[4];  // (kEvStepBegin ... kEvUsageEnd)
+    std::vector<ks_own::Event> prof_ev;
     ks_step_stats stats{};
     ks_kernel_stats kstats{};
 
     // scratch for queries
-    uint8_t* d_mask = nullptr;
-    int64_t* d_score = nullptr;
-    ks::WinWS* d_sweep = nullptr;    // batch window workspace and node -> E index (n_pad, -1)
-    int32_t* d_eidx = nullptr;
-    int32_t* d_nslot = nullptr;      // node -> candidate slot of the batch (ks_cand.hip), -1
-    int32_t* d_first = nullptr;      // node -> its first kept entry of the batch, kNoFirst
-    unsigned long long* d_usage = nullptr;
+    Dev<uint8_t> d_mask;
+    Dev<int64_t> d_score;
+    Dev<unsigned long long> d_usage;
     DVec<int32_t> d_blk;                  // usage query: candidate pod blocks
     std::vector<int32_t> h_blk;
     DVec<unsigned long long> d_digest;    // [6][T + 1] difference arrays, then the prefix sums
@@ -235,24 +239,21 @@ struct ks_engine {
 
 namespace ks_host {
 
-// ks_engine::ev (and the first two: ks_group::ev): a step's first and last stream operation (ks_step_stats'
-// step_ms), a profiled usage query's kernel
+// ks_engine::ev (the first two: ks_group::ev): a step's first and last stream operation (step_ms), a profiled usage kernel
 enum { kEvStepBegin = 0, kEvStepEnd = 1, kEvUsageBegin = 2, kEvUsageEnd = 3 };
 
 // record the message for ks_last_error and return code
 ks_status fail(ks_engine* e, ks_status code, const char* fmt, ...);
 
-#define HIPCHK(e, expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _r = (expr);                                                                      \
-        if (_r != hipSuccess)                                                                        \
-            return ks_host::fail((e), KS_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(_r));    \
+#define HIPCHK(e, expr)                                                                                        \
+    do {                                                                                                       \
+        if (hipError_t _r = (expr); _r != hipSuccess)                                                          \
+            return ks_host::fail((e), KS_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(_r));              \
     } while (0)
 
 // apply the staged submits (ks_engine.cpp, host-staged submits): before any device work reads them
 hipError_t stage_flush(ks_engine* e);
-// stage the rows of exp_pos that submits rewrote since the last flush (stage_flush does; the per-tick
-// path passes the staged rows inline instead)
+// stage the rows of exp_pos that submits rewrote since the last flush (stage_flush does; the per-tick path inlines them)
 hipError_t stage_xpos(ks_engine* e);
 // the kernels' argument record of the engine as it stands (ks_engine.cpp)
 ks::EngineArgs make_args(ks_engine* e);
@@ -266,8 +267,7 @@ bool small_resolver(const ks_engine* e);
 int resolver_of(const ks_engine* e);
 // the role-split or the register-table resolver (the chunk resolver runs fused into the batch chain)
 hipError_t launch_resolver(const ks::EngineArgs* d, int S, int mode, int which, hipStream_t st);
-// the batch window workspace, pruned-list bitmaps and the second stream, allocated on the first
-// step that runs a resolver using them (ks_step.cpp)
+// the window workspace, pruned-list bitmaps and pipelined chain's set, made on the first step that needs them (ks_step.cpp)
 ks_status ensure_window_ws(ks_engine* e);
 // apply every not-yet-applied expiry with finish tick <= the current tick (ks_engine.cpp)
 ks_status flush_expiries(ks_engine* e);
@@ -280,21 +280,17 @@ ks_status flush_expiries(ks_engine* e);
 struct ks_group {
     int device = 0;
     int cap = 0;
-    hipStream_t st = nullptr;
-    std::vector<ks_engine*> engs;
-    int64_t* d_ctr = nullptr;           // [cap][32]
-    int64_t* h_ctr = nullptr;           // pinned
-    ks::EngineArgs* d_args = nullptr;   // [cap]
-    ks::EngineArgs* h_args = nullptr;   // pinned
-    ks::BindSeg* d_seg = nullptr;       // [cap]
-    ks::BindSeg* h_seg = nullptr;       // pinned
-    int32_t* d_out = nullptr;           // packed binds: node, then status
-    int32_t* h_out = nullptr;           // pinned mirror of d_out
-    int64_t out_cap = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     // the second half of the scenarios runs its batch rounds on its own stream: one half's
     // latency-bound resolvers then share the GPU with the other half's throughput-bound scans
-    hipStream_t st2 = nullptr;
-    hipEvent_t xev = nullptr;  // argument upload done (st -> st2)
+    ks_own::Stream st, st2;  // (first: destroyed last)
+    std::vector<ks_engine*> engs;
+    // each with its pinned mirror: counters [cap][32], argument records [cap], bind segments [cap]
+    ks_own::Dev<int64_t> d_ctr; ks_own::Pinned<int64_t> h_ctr;
+    ks_own::Dev<ks::EngineArgs> d_args; ks_own::Pinned<ks::EngineArgs> h_args;
+    ks_own::Dev<ks::BindSeg> d_seg; ks_own::Pinned<ks::BindSeg> h_seg;
+    struct OutBuf { ks_own::Dev<int32_t> d_out; ks_own::Pinned<int32_t> h_out; int64_t cap = 0; };
+    std::optional<OutBuf> out;  // packed binds of a step: node, then status; grown geometrically
+    ks_own::Event ev[2];
+    ks_own::Event xev;  // argument upload done (st -> st2)
     std::string errmsg;
 };

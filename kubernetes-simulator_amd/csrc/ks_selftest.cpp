@@ -158,14 +158,12 @@ bool run_merge_cases(uint64_t* d_lists, uint64_t* d_out, int64_t& bad) {
 
 ks_status selftest_list_merge(int64_t* failures) {
     constexpr int kMaxLists = 4096;
-    uint64_t *d_lists = nullptr, *d_out = nullptr;
+    ks_own::Dev<uint64_t> d_lists, d_out;
     int64_t bad = 0;
-    bool ok = hipMalloc(&d_lists, sizeof(uint64_t) * kMaxLists * ks::kTopLOverlap) == hipSuccess;
-    ok = ok && hipMalloc(&d_out, sizeof(uint64_t) * ks::kTopLOverlap) == hipSuccess;
+    bool ok = ks_own::dev_alloc(d_lists, (size_t)kMaxLists * ks::kTopLOverlap) == hipSuccess;
+    ok = ok && ks_own::dev_alloc(d_out, ks::kTopLOverlap) == hipSuccess;
     ok = ok && run_merge_cases<ks::kTopL>(d_lists, d_out, bad);
     if constexpr (ks::kTopLOverlap != ks::kTopL) ok = ok && run_merge_cases<ks::kTopLOverlap>(d_lists, d_out, bad);
-    if (d_lists) (void)hipFree(d_lists);
-    if (d_out) (void)hipFree(d_out);
     if (!ok) return KS_EDEVICE;
     *failures = bad;
     return KS_OK;
@@ -181,14 +179,13 @@ ks_status ks_selftest(int32_t device, int32_t test, int64_t* failures) {
     *failures = -1;
     if (hipSetDevice(device) != hipSuccess) return KS_EDEVICE;
     if (test == KS_SELFTEST_LIST_MERGE) return selftest_list_merge(failures);
-    unsigned long long* d = nullptr;
+    ks_own::Dev<unsigned long long> d;
     unsigned long long h = 0;
-    bool ok = hipMalloc(&d, sizeof h) == hipSuccess;
+    bool ok = ks_own::dev_alloc(d, 1) == hipSuccess;
     ok = ok && hipMemset(d, 0, sizeof h) == hipSuccess;
     ok = ok && (test == KS_SELFTEST_LR_MICRO ? ks::launch_selftest_lr_micro(d, nullptr)
                                              : ks::launch_selftest_micro_states(d, nullptr)) == hipSuccess;
     ok = ok && hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
-    if (d) (void)hipFree(d);
     if (!ok) return KS_EDEVICE;
     *failures = (int64_t)h;
     return KS_OK;
@@ -226,16 +223,17 @@ ks_status ks_selftest_eval(int32_t device, const ks_eval_cfg* cfg, int64_t n, co
     const size_t sz_alloc = (size_t)n * 4 * 8, sz_req = (size_t)n * 3 * 8, sz_km = (size_t)n * 4;
     const size_t sz_scan = (size_t)n * sizeof(ks::ScanRec);
     const size_t sz_tot = (size_t)n * 4 * ks::kEvTotalCols, sz_pr = (size_t)n * 4 * ks::kEvPruneCols;
-    void* buf[9] = {};
+    ks_own::Dev<char> buf[9];
     const size_t size[9] = {sz_alloc, sz_alloc, sz_req, sz_km, sz_alloc, sz_scan, sz_tot, sz_pr, sz_pr};
     const void* src[6] = {alloc, run, req, keymask, masks, srec.data()};
     bool ok = true;
-    for (int k = 0; k < 9 && ok; k++) ok = hipMalloc(&buf[k], size[k]) == hipSuccess;
+    for (int k = 0; k < 9 && ok; k++) ok = ks_own::dev_alloc(buf[k], size[k]) == hipSuccess;
     for (int k = 0; k < 6 && ok; k++) ok = hipMemcpy(buf[k], src[k], size[k], hipMemcpyHostToDevice) == hipSuccess;
     for (int k = 6; k < 9 && ok; k++) ok = hipMemset(buf[k], 0, size[k]) == hipSuccess;
-    ec.alloc = (const int64_t*)buf[0]; ec.run = (const int64_t*)buf[1]; ec.req = (const int64_t*)buf[2];
-    ec.keymask = (const uint32_t*)buf[3]; ec.masks = (const uint64_t*)buf[4]; ec.scan = (const ks::ScanRec*)buf[5];
-    ec.total1 = (uint32_t*)buf[6]; ec.tmax = (uint32_t*)buf[7]; ec.live = (uint32_t*)buf[8];
+    char* const bp[9] = {buf[0], buf[1], buf[2], buf[3], buf[4], buf[5], buf[6], buf[7], buf[8]};
+    ec.alloc = (const int64_t*)bp[0]; ec.run = (const int64_t*)bp[1]; ec.req = (const int64_t*)bp[2];
+    ec.keymask = (const uint32_t*)bp[3]; ec.masks = (const uint64_t*)bp[4]; ec.scan = (const ks::ScanRec*)bp[5];
+    ec.total1 = (uint32_t*)bp[6]; ec.tmax = (uint32_t*)bp[7]; ec.live = (uint32_t*)bp[8];
     ok = ok && ks::launch_evtest_nodev(ec, nullptr) == hipSuccess;
     ok = ok && ks::launch_evtest_rec12(ec, nullptr) == hipSuccess;
     ok = ok && ks::launch_evtest_ns32(ec, nullptr) == hipSuccess;
@@ -246,15 +244,13 @@ ks_status ks_selftest_eval(int32_t device, const ks_eval_cfg* cfg, int64_t n, co
         if (!((variants >> b) & 1u)) continue;
         const size_t col = (size_t)n * 4;
         if (b < ks::kEvPruneBit) {
-            ok = hipMemcpy(total1 + (size_t)b * n, (char*)buf[6] + b * col, col, hipMemcpyDeviceToHost) == hipSuccess;
+            ok = hipMemcpy(total1 + (size_t)b * n, buf[6] + b * col, col, hipMemcpyDeviceToHost) == hipSuccess;
         } else {
             const size_t j = (size_t)(b - ks::kEvPruneBit);
-            ok = hipMemcpy(tmax + j * n, (char*)buf[7] + j * col, col, hipMemcpyDeviceToHost) == hipSuccess;
-            ok = ok && hipMemcpy(live + j * n, (char*)buf[8] + j * col, col, hipMemcpyDeviceToHost) == hipSuccess;
+            ok = hipMemcpy(tmax + j * n, buf[7] + j * col, col, hipMemcpyDeviceToHost) == hipSuccess;
+            ok = ok && hipMemcpy(live + j * n, buf[8] + j * col, col, hipMemcpyDeviceToHost) == hipSuccess;
         }
     }
-    for (int k = 0; k < 9; k++)
-        if (buf[k]) (void)hipFree(buf[k]);
     return ok ? KS_OK : KS_EDEVICE;
 }
 

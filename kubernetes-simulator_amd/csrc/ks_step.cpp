@@ -114,6 +114,13 @@ void mirror_expired(ks_engine* e, int64_t lo, int64_t hi) {
         }
 }
 
+// a buffer of n T, every byte set to `byte` in the stream's order
+template <typename T>
+hipError_t alloc_set(ks_own::Dev<T>& o, size_t n, int byte, hipStream_t st) {
+    KS_TRY(ks_own::dev_alloc(o, n));
+    return hipMemsetAsync(o, byte, sizeof(T) * n, st);
+}
+
 // The per-tick path (ks_tick.hip): exactly one pod binds in this step — one launch does the
 // staged submits, the pod's expiries, the full-cluster evaluation, the argmax and the bind.
 // Returns false (nothing done) when the pod's expiries do not fit the launch's by-value list.
@@ -130,12 +137,11 @@ bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* 
         for (int k = 0; k < 3; k++) x.req[k] = e->h_pods[q].req[k];
     }
     *rc = KS_OK;
-    if (!e->d_tick) {
-        hipError_t r = hipMalloc(&e->d_tick, sizeof(ks::TickScratch));
-        if (r == hipSuccess) r = hipMemsetAsync(e->d_tick, 0, sizeof(ks::TickScratch), e->st);
-        if (r == hipSuccess) r = hipHostMalloc(&e->h_tick, sizeof(ks::TickOut), hipHostMallocMapped);
-        if (r == hipSuccess) r = hipHostGetDevicePointer((void**)&e->h_tick_dev, e->h_tick, 0);
-        if (r == hipSuccess && !e->stage_ev) r = hipEventCreateWithFlags(&e->stage_ev, hipEventDisableTiming);
+    if (!e->tickset) {
+        const hipError_t r = ks_own::build(e->tickset, [&](TickSet& t) {
+            KS_TRY(alloc_set(t.d_tick, 1, 0, e->st));
+            return ks_own::pinned_alloc(t.h_tick, 1, hipHostMallocMapped);
+        });
         if (r != hipSuccess) { *rc = fail(e, KS_EDEVICE, "per-tick path setup: %s", hipGetErrorString(r)); return true; }
     }
     a.c = e->dc;
@@ -146,8 +152,8 @@ bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* 
     a.b_node = e->b_node.p;
     a.b_status = e->b_status.p;
     a.expired = e->expired.p;
-    a.scr = e->d_tick;
-    a.out = e->h_tick_dev;
+    a.scr = e->tickset->d_tick;
+    a.out = e->tickset->h_tick.dev;
     if (stage_xpos(e) != hipSuccess) { *rc = fail(e, KS_EDEVICE, "per-tick path: staging failed"); return true; }
     // the pending staged rows inline in the arguments when they fit (one pod's submit does), else
     // one scatter launch ahead of the kernel
@@ -155,14 +161,14 @@ bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* 
         int32_t off = 0;
         bool fits = e->nseg - e->seg_done <= ks::kTickInlSeg;
         for (int k = e->seg_done; fits && k < e->nseg; k++) {
-            off += (int32_t)((e->segs[k].bytes + 15) / 16 * 16);
+            off += (int32_t)((e->arena->segs[k].bytes + 15) / 16 * 16);
             fits = off <= ks::kTickInl;
         }
         if (fits) {
             off = 0;
             for (int k = e->seg_done; k < e->nseg; k++) {
-                const ks::CopySeg& sg = e->segs[k];
-                std::memcpy(a.inl + off, e->stage + (sg.src - e->stage_dev), (size_t)sg.bytes);
+                const ks::CopySeg& sg = e->arena->segs[k];
+                std::memcpy(a.inl + off, e->arena->mem + (sg.src - e->arena->mem.dev), (size_t)sg.bytes);
                 a.iseg[a.n_iseg++] = ks::TickSeg{sg.dst, off, (int32_t)sg.bytes};
                 off += (int32_t)((sg.bytes + 15) / 16 * 16);
             }
@@ -172,14 +178,14 @@ bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* 
             return true;
         }
     }
-    __atomic_store_n(&e->h_tick->code, -1, __ATOMIC_RELAXED);
+    __atomic_store_n(&e->tickset->h_tick->code, -1, __ATOMIC_RELAXED);
     hipError_t r = ks::launch_tick(a, e->mode, e->st);
     if (r == hipSuccess) r = hipEventRecord(e->stage_ev, e->st);
     // the result: poll the host-mapped code the last workgroup stores (release) after node and
     // status — microseconds sooner than a stream synchronisation; the stream is queried now and
     // then so that a failed launch still ends the wait
     for (uint32_t spin = 1; r == hipSuccess; spin++) {
-        if (__atomic_load_n(&e->h_tick->code, __ATOMIC_ACQUIRE) >= 0) break;
+        if (__atomic_load_n(&e->tickset->h_tick->code, __ATOMIC_ACQUIRE) >= 0) break;
         if ((spin & 1023) == 0) {
             const hipError_t q = hipStreamQuery(e->st);
             if (q == hipSuccess) break;  // done: the code is read below
@@ -189,9 +195,9 @@ bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* 
     }
     if (r != hipSuccess) { *rc = fail(e, KS_EDEVICE, "per-tick launch: %s", hipGetErrorString(r)); return true; }
     ks::TickOut o;
-    o.code = __atomic_load_n(&e->h_tick->code, __ATOMIC_ACQUIRE);
-    o.node = ((volatile ks::TickOut*)e->h_tick)->node;
-    o.status = ((volatile ks::TickOut*)e->h_tick)->status;
+    o.code = __atomic_load_n(&e->tickset->h_tick->code, __ATOMIC_ACQUIRE);
+    o.node = ((volatile ks::TickOut*)e->tickset->h_tick)->node;
+    o.status = ((volatile ks::TickOut*)e->tickset->h_tick)->status;
     for (int k = 0; k < a.n_exp; k++) e->h_expired[a.exp[k].q] = 1;
     e->stats = ks_step_stats{};
     e->stats.launches = 1;
@@ -212,48 +218,52 @@ bool tick_step(ks_engine* e, int64_t t_end, ks_bind* out, int64_t cap, int64_t* 
 #endif
 constexpr int kPruneMinBlocks = KS_PRUNE_MIN_BLOCKS;
 
-// The batch window workspace (~0.8 MB) and the node -> E index, allocated on the first step that
-// runs a resolver using them (what-if group members never do).
+// The batch window workspace (~0.8 MB) with the node -> E index, the pruned lists' bitmaps and the
+// pipelined sharded chain's stream, events and full-range arguments, each made on the first step that
+// runs a resolver using it (what-if group members never do).
 ks_status ks_host::ensure_window_ws(ks_engine* e) {
+    hipStream_t st = e->st;
     const int r = resolver_of(e);
-    e->prune = r == kResolveChunk && !e->group && (e->nblk >= kPruneMinBlocks || (e->flags & KS_ENGINE_PRUNED_LISTS));
-    if (e->prune && !e->lbit) {
+    // (on a failed build only: prune is set once the bitmaps are there, and the pipelined set is
+    // looked for on every call, not only on the one that made the window workspace)
+    const bool prune = r == kResolveChunk && !e->group && (e->nblk >= kPruneMinBlocks || (e->flags & KS_ENGINE_PRUNED_LISTS));
+    ks_status s = KS_OK;
+    if (prune && !e->bits) {
         e->nwl = (e->nblk + 63) / 64;
-        HIPCHK(e, hipMalloc(&e->lbit, sizeof(uint64_t) * 2 * (size_t)e->B * e->nwl));  // two sets (EngineArgs)
-        HIPCHK(e, hipMemsetAsync(e->lbit, 0, sizeof(uint64_t) * 2 * (size_t)e->B * e->nwl, e->st));
-        HIPCHK(e, hipMalloc(&e->lthr, sizeof(uint64_t) * 2 * ks::kThrCopies * (size_t)e->B));
-        HIPCHK(e, hipMemsetAsync(e->lthr, 0, sizeof(uint64_t) * 2 * ks::kThrCopies * (size_t)e->B, e->st));
+        s = ks_own::build(e->bits, [&](PruneBits& b) {
+            HIPCHK(e, alloc_set(b.lbit, 2 * (size_t)e->B * e->nwl, 0, st));  // two sets (EngineArgs)
+            HIPCHK(e, alloc_set(b.lthr, 2 * ks::kThrCopies * (size_t)e->B, 0, st));
+            return KS_OK;
+        });
     }
-    if (e->d_sweep || r != kResolveChunk) return KS_OK;
-    HIPCHK(e, hipMalloc(&e->d_sweep, sizeof(ks::WinWS)));
-    HIPCHK(e, hipMemsetAsync(e->d_sweep, 0, sizeof(ks::WinWS), e->st));
-    HIPCHK(e, hipMalloc(&e->d_eidx, sizeof(int32_t) * e->n_pad));
-    HIPCHK(e, hipMemsetAsync(e->d_eidx, 0xFF, sizeof(int32_t) * e->n_pad, e->st));
-    HIPCHK(e, hipMalloc(&e->d_nslot, sizeof(int32_t) * e->n_pad));
-    HIPCHK(e, hipMemsetAsync(e->d_nslot, 0xFF, sizeof(int32_t) * e->n_pad, e->st));
-    HIPCHK(e, hipMalloc(&e->d_first, sizeof(int32_t) * e->n_pad));
-    HIPCHK(e, hipMemsetAsync(e->d_first, 0x7F, sizeof(int32_t) * e->n_pad, e->st));  // kNoFirst
-    HIPCHK(e, hipMalloc(&e->d_spec, 2 * ks::kSpecStride * sizeof(int64_t)));
-    HIPCHK(e, hipMemsetAsync(e->d_spec, 0, 2 * ks::kSpecStride * sizeof(int64_t), e->st));
-    HIPCHK(e, hipMalloc(&e->d_args_spec, 2 * sizeof(ks::EngineArgs)));
-    HIPCHK(e, hipHostMalloc(&e->h_args_spec, 2 * sizeof(ks::EngineArgs), hipHostMallocDefault));
-    {   // the fused scan's workgroups: one per CU beside the resolver's (the resolver's LDS
-        // footprint allows one workgroup per CU)
-        int cus = 0;
+    if (s != KS_OK) return s;
+    e->prune = prune;
+    if (r != kResolveChunk) return KS_OK;
+    if (!e->win) s = ks_own::build(e->win, [&](WindowWs& w) {
+        HIPCHK(e, alloc_set(w.d_sweep, 1, 0, st));
+        HIPCHK(e, alloc_set(w.d_eidx, e->n_pad, 0xFF, st));
+        HIPCHK(e, alloc_set(w.d_nslot, e->n_pad, 0xFF, st));
+        HIPCHK(e, alloc_set(w.d_first, e->n_pad, 0x7F, st));  // kNoFirst
+        HIPCHK(e, alloc_set(w.d_spec, 2 * ks::kSpecStride, 0, st));
+        HIPCHK(e, ks_own::dev_alloc(w.d_args_spec, 2));
+        HIPCHK(e, ks_own::pinned_alloc(w.h_args_spec, 2));
+        int cus = 0;  // the fused scan's workgroups: one per CU beside the resolver's (its LDS footprint allows one per CU)
         HIPCHK(e, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
 #ifndef KS_SCAN_WORKERS_DIV
 #define KS_SCAN_WORKERS_DIV 1  // (A/B builds: make variant DEFS=-DKS_SCAN_WORKERS_DIV=2)
 #endif
-        e->scan_workers = std::max(15, cus / KS_SCAN_WORKERS_DIV - 1);  // (>= 15: every XCD deals its share to at least one)
-    }
-    if (e->world * e->vsh > 1) {  // the pipelined sharded chain's stream, events and full-range arguments
-        HIPCHK(e, hipStreamCreateWithFlags(&e->st2, hipStreamNonBlocking));
-        HIPCHK(e, hipEventCreateWithFlags(&e->pev_m, hipEventDisableTiming));
-        HIPCHK(e, hipEventCreateWithFlags(&e->pev_x, hipEventDisableTiming));
-        HIPCHK(e, hipMalloc(&e->d_args_full, sizeof(ks::EngineArgs)));
-        HIPCHK(e, hipHostMalloc(&e->h_args_full, sizeof(ks::EngineArgs), hipHostMallocDefault));
-    }
-    return KS_OK;
+        w.scan_workers = std::max(15, cus / KS_SCAN_WORKERS_DIV - 1);  // (>= 15: every XCD deals its share to at least one)
+        return KS_OK;
+    });
+    if (s == KS_OK && !e->pipe && e->world * e->vsh > 1) s = ks_own::build(e->pipe, [&](PipeSet& p) {
+        HIPCHK(e, ks_own::stream_create(p.st2));
+        HIPCHK(e, ks_own::event_create(p.pev_m, hipEventDisableTiming));
+        HIPCHK(e, ks_own::event_create(p.pev_x, hipEventDisableTiming));
+        HIPCHK(e, ks_own::dev_alloc(p.d_args_full, 1));
+        HIPCHK(e, ks_own::pinned_alloc(p.h_args_full, 1));
+        return KS_OK;
+    });
+    return s;
 }
 
 namespace {
@@ -263,7 +273,7 @@ namespace {
 hipError_t part_merges(ks_engine* e, const ks::EngineArgs* a, hipStream_t s, int lset_fixed) {
     const int64_t L = e->L, BL = (int64_t)e->B * L;
     ks::MergeOpts o;
-    o.bits = e->prune ? e->lbit : nullptr;
+    o.bits = e->prune ? (uint64_t*)e->bits->lbit : nullptr;
     o.nwl = e->nwl;
     o.lset_fixed = lset_fixed;
     o.L = (int)L;
@@ -320,9 +330,9 @@ struct StepProfile {
         if (!e->profiling) return hipSuccess;
         recs.push_back(batch_record(chain, pos.first, pos.more, sharded));
         while (e->prof_ev.size() < (size_t)kMarkCount * recs.size()) {
-            hipEvent_t x;
-            if (hipError_t r = hipEventCreate(&x); r != hipSuccess) return r;
-            e->prof_ev.push_back(x);
+            ks_own::Event x;
+            KS_TRY(ks_own::event_create(x));
+            e->prof_ev.push_back(std::move(x));
         }
         return hipSuccess;
     }
@@ -383,7 +393,7 @@ ks_status sharded_merge(ks_engine* e, StepProfile& pf, bool fused) {
 // its speculative scan) fused in while the pass goes on, alone on its last batch
 hipError_t chunk_resolve(ks_engine* e, const BatchPos& pos, int workers, int L) {
     if (!pos.more) return ks::launch_chunk_only(e->d_args, e->mode, e->st);
-    return ks::launch_chunk_scan(e->d_args, e->d_args_spec + (pos.b & 1), workers, (int)((pos.b + 1) & 1), e->mode,
+    return ks::launch_chunk_scan(e->d_args, e->win->d_args_spec + (pos.b & 1), workers, (int)((pos.b + 1) & 1), e->mode,
                                  e->prune, L, e->st);
 }
 
@@ -436,7 +446,7 @@ ks_status batch_overlap_sharded(ks_engine* e, const BatchPos& pos, StepProfile& 
     HIPCHK(e, pf.mark(kMarkScan, st));
     if (ks_status r = sharded_merge(e, pf, true); r != KS_OK) return r;
     HIPCHK(e, pf.mark(kMarkMerge, st));
-    HIPCHK(e, chunk_resolve(e, pos, e->scan_workers, e->L));
+    HIPCHK(e, chunk_resolve(e, pos, e->win->scan_workers, e->L));
     HIPCHK(e, pf.mark(kMarkResolve, st));
     return KS_OK;
 }
@@ -457,7 +467,7 @@ ks_status batch_two_launch(ks_engine* e, const BatchPos& pos, StepProfile& pf) {
     o.direct = true;
     HIPCHK(e, ks::launch_merge_cl(e->d_args, e->mode, e->B, ks::own_block_lists(e->nblk), st, o));
     HIPCHK(e, pf.mark(kMarkMerge, st));
-    HIPCHK(e, chunk_resolve(e, pos, e->scan_workers, e->L));
+    HIPCHK(e, chunk_resolve(e, pos, e->win->scan_workers, e->L));
     HIPCHK(e, pf.mark(kMarkResolve, st));
     return KS_OK;
 }
@@ -473,7 +483,7 @@ ks_status batch_two_launch(ks_engine* e, const BatchPos& pos, StepProfile& pf) {
 // (ks_prep.h), so the exchanged lists always serve; when E overflows, the rescan scans every block
 // locally (no second exchange: every rank holds the whole table) and merge_cl merges those.
 ks_status batch_pipe(ks_engine* e, const BatchPos& pos, StepProfile& pf) {
-    hipStream_t st = e->st, s2 = e->st2;
+    hipStream_t st = e->st, s2 = e->pipe->st2;
     const ks::EngineArgs* d = e->d_args;
     HIPCHK(e, pf.begin(kChainPipe, pos, true));
     HIPCHK(e, pf.mark(kMarkBegin, st));
@@ -486,13 +496,13 @@ ks_status batch_pipe(ks_engine* e, const BatchPos& pos, StepProfile& pf) {
         HIPCHK(e, pf.mark(kMarkScan, st));
         if (ks_status r = parts_and_exchange(e, pf, d, st, -1, kMarkParts, kMarkXchg); r != KS_OK) return r;
     } else {
-        HIPCHK(e, hipStreamWaitEvent(st, e->pev_x, 0));
+        HIPCHK(e, hipStreamWaitEvent(st, e->pipe->pev_x, 0));
         HIPCHK(e, pf.mark(kMarkPrep, st));
         ks::ScanOpts rescan = scan_opts(e);  // every block, only when the window prep flagged it
         rescan.cond = true;
         rescan.stage = true;
         rescan.pw = kRescanWgs;  // (a small persistent grid)
-        HIPCHK(e, scan(e, e->d_args_full, e->nblk, st, rescan));
+        HIPCHK(e, scan(e, e->pipe->d_args_full, e->nblk, st, rescan));
         HIPCHK(e, pf.mark(kMarkScan, st));
         HIPCHK(e, pf.mark(kMarkParts, st));  // (on the second stream: zero intervals here)
         HIPCHK(e, pf.mark(kMarkXchg, st));
@@ -502,18 +512,18 @@ ks_status batch_pipe(ks_engine* e, const BatchPos& pos, StepProfile& pf) {
     mo.own_fallback = !pos.first;
     HIPCHK(e, ks::launch_merge_cl(d, e->mode, e->B, ks::exchanged_lists(e->cand_all, e->world * e->vsh, e->B, e->L), st, mo));
     HIPCHK(e, pf.mark(kMarkMerge, st));
-    if (pos.more) HIPCHK(e, hipEventRecord(e->pev_m, st));
+    if (pos.more) HIPCHK(e, hipEventRecord(e->pipe->pev_m, st));
     // (no scan workers: the resolver and the next window only; the list length is the workers')
     HIPCHK(e, chunk_resolve(e, pos, 0, ks::kTopL));
     HIPCHK(e, pf.mark(kMarkResolve, st));
     if (pos.more) {
-        const ks::EngineArgs* ds = e->d_args_spec + (pos.b & 1);
-        HIPCHK(e, hipStreamWaitEvent(s2, e->pev_m, 0));
+        const ks::EngineArgs* ds = e->win->d_args_spec + (pos.b & 1);
+        HIPCHK(e, hipStreamWaitEvent(s2, e->pipe->pev_m, 0));
         HIPCHK(e, pf.mark(kMarkSideBegin, s2));
         HIPCHK(e, scan(e, ds, e->blk_n, s2, scan_opts(e)));
         HIPCHK(e, pf.mark(kMarkSideScan, s2));
         if (ks_status r = parts_and_exchange(e, pf, ds, s2, 0, kMarkSideParts, kMarkSideXchg); r != KS_OK) return r;
-        HIPCHK(e, hipEventRecord(e->pev_x, s2));
+        HIPCHK(e, hipEventRecord(e->pipe->pev_x, s2));
     }
     return KS_OK;
 }
@@ -539,18 +549,20 @@ ks_status upload_args(ks_engine* e, const StepPlan& plan) {
     HIPCHK(e, hipMemcpyAsync(e->d_args, e->h_args, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
     if (two) HIPCHK(e, ks::launch_node_consts(e->s, e->n_pad, e->d_ncst, st));
     if (plan.chain == kChainPipe) {
-        *e->h_args_full = *e->h_args;
-        e->h_args_full->blk_lo = 0;
-        e->h_args_full->blk_n = e->nblk;
-        HIPCHK(e, hipMemcpyAsync(e->d_args_full, e->h_args_full, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
+        PipeSet& p = *e->pipe;
+        *p.h_args_full = *e->h_args;
+        p.h_args_full->blk_lo = 0;
+        p.h_args_full->blk_n = e->nblk;
+        HIPCHK(e, hipMemcpyAsync(p.d_args_full, p.h_args_full, sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
     }
     if (plan.chain != kChainPlain) {
+        WindowWs& w = *e->win;
         for (int k = 0; k < 2; k++) {
-            e->h_args_spec[k] = *e->h_args;
-            e->h_args_spec[k].ctr = e->d_spec + ks::kSpecStride * k;
-            e->h_args_spec[k].lset = 0;
+            w.h_args_spec[k] = *e->h_args;
+            w.h_args_spec[k].ctr = w.d_spec + ks::kSpecStride * k;
+            w.h_args_spec[k].lset = 0;
         }
-        HIPCHK(e, hipMemcpyAsync(e->d_args_spec, e->h_args_spec, 2 * sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(w.d_args_spec, w.h_args_spec, 2 * sizeof(ks::EngineArgs), hipMemcpyHostToDevice, st));
     }
     return KS_OK;
 }
@@ -559,29 +571,30 @@ ks_status upload_args(ks_engine* e, const StepPlan& plan) {
 // geometrically (nothing is in flight into them between steps); `early`: the chain may read back
 // early, on its copy stream.
 ks_status ensure_readback(ks_engine* e, int64_t n, bool early) {
-    if (n > e->bind_cap) {
-        const int64_t want = std::max<int64_t>({n, 2 * e->bind_cap, 4096});
-        if (e->h_bnode) (void)hipHostFree(e->h_bnode);
-        if (e->h_bstat) (void)hipHostFree(e->h_bstat);
-        e->h_bnode = e->h_bstat = nullptr;
-        e->bind_cap = 0;
-        HIPCHK(e, hipHostMalloc(&e->h_bnode, sizeof(int32_t) * want, hipHostMallocDefault));
-        HIPCHK(e, hipHostMalloc(&e->h_bstat, sizeof(int32_t) * want, hipHostMallocDefault));
-        e->bind_cap = want;
+    if (const int64_t cap = e->rb ? e->rb->cap : 0; n > cap) {
+        e->rb.reset();  // (freed before the larger ones are made)
+        const ks_status r = ks_own::build(e->rb, [&](Readback& b) {
+            b.cap = std::max<int64_t>({n, 2 * cap, 4096});
+            HIPCHK(e, ks_own::pinned_alloc(b.h_bnode, b.cap));
+            HIPCHK(e, ks_own::pinned_alloc(b.h_bstat, b.cap));
+            return KS_OK;
+        });
+        if (r != KS_OK) return r;
     }
-    if (early && !e->st_copy) {
-        HIPCHK(e, hipStreamCreateWithFlags(&e->st_copy, hipStreamNonBlocking));
-        HIPCHK(e, hipEventCreateWithFlags(&e->snap_ev, hipEventDisableTiming));
-    }
-    return KS_OK;
+    if (!early || e->early) return KS_OK;
+    return ks_own::build(e->early, [&](EarlyCopy& c) {
+        HIPCHK(e, ks_own::stream_create(c.st_copy));
+        HIPCHK(e, ks_own::event_create(c.snap_ev, hipEventDisableTiming));
+        return KS_OK;
+    });
 }
 
 // the node and status words of pods [lo, hi) into the read-back buffers (which begin at pod done0), on stream s
 ks_status copy_binds(ks_engine* e, int64_t done0, int64_t lo, int64_t hi, hipStream_t s) {
     if (hi <= lo) return KS_OK;
     const size_t bytes = sizeof(int32_t) * (size_t)(hi - lo);
-    HIPCHK(e, hipMemcpyAsync(e->h_bnode + (lo - done0), e->b_node.p + lo, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(e->h_bstat + (lo - done0), e->b_status.p + lo, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->rb->h_bnode + (lo - done0), e->b_node.p + lo, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(e->rb->h_bstat + (lo - done0), e->b_status.p + lo, bytes, hipMemcpyDeviceToHost, s));
     return KS_OK;
 }
 
@@ -639,12 +652,12 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
     PlanFacts facts{};
     facts.resolver = resolver_of(e);
     facts.overlap = e->overlap;
-    facts.spec_args = e->d_args_spec != nullptr;
+    facts.spec_args = e->win.has_value();
     facts.key16 = key16(e);
     facts.blk_n = e->blk_n;
     facts.parts = e->world * e->vsh;
     facts.prune = e->prune;
-    facts.side_stream = e->st2 != nullptr;
+    facts.side_stream = e->pipe.has_value();
     const StepPlan plan = plan_step(facts);
     e->L = plan.L;
     if (ks_status r = ensure_readback(e, p_hi - done0, plan.chain == kChainTwoLaunch); r != KS_OK) return r;
@@ -666,8 +679,8 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
     //    stays behind start, and one copy after the loop fetches [have, new_done) as ks_step always did.
     // In the first two kinds the pass's one wait also delivers its binds, and have follows start.
     int64_t have = done0, fin = done0, snap_pods = 0;
-    const int32_t* const node = e->h_bnode;
-    const int32_t* const status = e->h_bstat;
+    const int32_t* const node = e->rb->h_bnode;
+    const int32_t* const status = e->rb->h_bstat;
     StepProfile pf{e, {}};
     while (true) {
         const int64_t rounds = (p_hi - start + e->B - 1) / e->B;
@@ -676,7 +689,7 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
             if (ks_status r = chain_batch(e, plan, BatchPos{b, b == 0, b + 1 < rounds}, pf); r != KS_OK) return r;
             if (b == snap_at) {  // between two rounds: every bind below the counter is visible
                 HIPCHK(e, hipMemcpyAsync(e->h_ctr + 8, e->d_ctr + ks::kCtrStart, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-                HIPCHK(e, hipEventRecord(e->snap_ev, st));
+                HIPCHK(e, hipEventRecord(e->early->snap_ev, st));
             }
         }
         HIPCHK(e, hipEventRecord(e->ev[kEvStepEnd], st));
@@ -697,7 +710,7 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
             // and of their expiries are already written, where a failed step used to leave them
             // untouched: acceptable only because the engine is then sticky-failed (ks_step returns
             // its error from then on) and the binds themselves are final — the device committed them.
-            HIPCHK(e, hipEventSynchronize(e->snap_ev));
+            HIPCHK(e, hipEventSynchronize(e->early->snap_ev));
             TAIL_AT(kTsSnapWait);
             lo = std::clamp(e->h_ctr[8], start, p_hi);
         }
@@ -708,8 +721,8 @@ ks_status step_body(ks_engine* e, int64_t ticks, ks_bind* out, int64_t cap, int6
         if (behind)
             if (ks_status r = copy_binds(e, done0, lo, p_hi, st); r != KS_OK) return r;
         if (snapped && lo > have) {
-            if (ks_status r = copy_binds(e, done0, have, lo, e->st_copy); r != KS_OK) return r;
-            HIPCHK(e, hipStreamSynchronize(e->st_copy));
+            if (ks_status r = copy_binds(e, done0, have, lo, e->early->st_copy); r != KS_OK) return r;
+            HIPCHK(e, hipStreamSynchronize(e->early->st_copy));
             snap_pods += lo - have;
             have = lo;
             TAIL_AT(kTsEarlyCopy);
@@ -905,21 +918,21 @@ ks_status ks_group_step(ks_group* g, int64_t ticks, ks_bind* out, int64_t cap, i
         total += std::max<int64_t>(nb, 0);
         max_n = std::max(max_n, nb);
     }
-    if (total > g->out_cap) {
-        if (g->d_out) (void)hipFree(g->d_out);
-        if (g->h_out) (void)hipHostFree(g->h_out);
-        g->d_out = g->h_out = nullptr;
-        g->out_cap = std::max<int64_t>(total, 2 * g->out_cap);
-        if (!dev(hipMalloc(&g->d_out, sizeof(int32_t) * 2 * g->out_cap)) ||
-            !dev(hipHostMalloc(&g->h_out, sizeof(int32_t) * 2 * g->out_cap, hipHostMallocDefault))) {
-            g->out_cap = 0;
+    if (const int64_t cap0 = g->out ? g->out->cap : 0; total > cap0) {
+        g->out.reset();  // (freed before the larger ones are made)
+        if (!dev(ks_own::build(g->out, [&](ks_group::OutBuf& b) {
+                b.cap = std::max<int64_t>(total, 2 * cap0);
+                KS_TRY(ks_own::dev_alloc(b.d_out, 2 * b.cap));
+                return ks_own::pinned_alloc(b.h_out, 2 * b.cap);
+            })))
             return dev_fail("group step: bind buffer allocation failed");
-        }
     }
+    int32_t* const h_out = total ? (int32_t*)g->out->h_out : nullptr;
     if (total) {
+        int32_t* const d_out = g->out->d_out;
         if (!dev(hipMemcpyAsync(g->d_seg, g->h_seg, sizeof(ks::BindSeg) * S, hipMemcpyHostToDevice, st)) ||
-            !dev(ks::launch_gather_binds(g->d_seg, S, max_n, g->d_out, g->d_out + total, st)) ||
-            !dev(hipMemcpyAsync(g->h_out, g->d_out, sizeof(int32_t) * 2 * total, hipMemcpyDeviceToHost, st)))
+            !dev(ks::launch_gather_binds(g->d_seg, S, max_n, d_out, d_out + total, st)) ||
+            !dev(hipMemcpyAsync(h_out, d_out, sizeof(int32_t) * 2 * total, hipMemcpyDeviceToHost, st)))
             return dev_fail("group step: bind copy failed");
     }
     if (!dev(hipEventRecord(g->ev[kEvStepEnd], st)) || !dev(hipStreamSynchronize(st)))
@@ -933,7 +946,7 @@ ks_status ks_group_step(ks_group* g, int64_t ticks, ks_bind* out, int64_t cap, i
             ks_engine* e = g->engs[i];
             if (status_out[i] != KS_OK || !part[i]) continue;
             const ks::BindSeg& sg = g->h_seg[i];
-            status_out[i] = step_finish(e, t_end[i], start[i], g->h_out + sg.off, g->h_out + total + sg.off,
+            status_out[i] = step_finish(e, t_end[i], start[i], h_out + sg.off, h_out + total + sg.off,
                                         out ? out + (int64_t)i * cap : nullptr, out ? cap : 0, &n_out[i]);
         }
     };
