@@ -1,0 +1,219 @@
+"""The inputs of tests/test_expiry_burst_gpu.py, pinned on the traces and the CPU oracle alone
+(tests/expiry_burst_cases.py): every burst tick carries its planned count of live expiries, the
+windows of 128, 192 and 256 pods stand on the planned side of the 128 and 512 edges, the step plans
+put the burst pod where they say, and the edges restated in the cases module are the sources'.  A
+trace that misses its condition is changed in expiry_burst_cases.py; the conditions here stay.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import expiry_burst_cases as ec
+from kubesim_amd import _lib
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "kubernetes-simulator_amd", "csrc")
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _ran_to_end(name, mode, which="whole"):
+    steps = ec.reference(name, mode, which)
+    b = ec.all_binds(name, mode, which)
+    return all(s["rc"] == 0 for s in steps) and len(b["pod"]) == ec.case(name)["tr"]["pods"]["m"]
+
+
+def _carrier(name, f, mode=ec.MODE, which="whole"):
+    return int(np.searchsorted(ec.all_binds(name, mode, which)["tick"], f))
+
+
+# ---- per trace ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,which,sizes", [
+    ("bursts3k", "whole", ec.BURSTS), ("small", "whole", ec.BURSTS[:6]), ("gap", "whole", ec.GAP_BURSTS),
+    ("pending16", "parts", (16,)), ("pending17_600", "parts", (17, 600))])
+def test_every_burst_tick_carries_its_planned_count(name, which, sizes):
+    assert _ran_to_end(name, ec.MODE, which)
+    c, b = ec.case(name), ec.all_binds(name, ec.MODE, which)
+    np.testing.assert_array_equal(b["tick"], c["bt"])     # the bind ticks the run lengths were planted on
+    assert (b["status"] == 0).all()
+    got = ec.burst_counts(name, ec.MODE, which)
+    print(name, "burst tick: planned / live / in the CSR / refused")
+    for (f, _, _), row in zip(c["bursts"], got):
+        print(f"  {f:6d}: {row[0]:5d} {row[1]:5d} {row[2]:5d} {row[3]:4d}")
+    assert [r[0] for r in got] == list(sizes)
+    assert all(m == live == csr and refused == 0 for m, live, csr, refused in got)
+    ticks = [f for f, _, _ in c["bursts"]]
+    if name == "bursts3k":
+        assert (np.diff(ticks) >= 300).all()
+        assert all(lo2 - f1 >= ec.CLEAR for (f1, _, _), (_, lo2, _) in zip(c["bursts"], c["bursts"][1:]))
+        assert ec.BURSTS[:10] == (16, 17, 128, 129, 256, 257, 512, 513, 1024, 1025) and ec.BURSTS[11] == 2100
+        assert 1700 <= ec.BURSTS[10] <= 1850
+    # every other pod carries a trickle: the short background pods that end in the (at most two) ticks
+    # since the bind before it were bound in a span of 13 ticks, every third pod of them
+    live, _ = ec.attached(b, c["run"])
+    carriers = [_carrier(name, f, ec.MODE, which) for f in ticks]
+    rest = np.delete(live[:-1], carriers)
+    assert rest.max() <= 5, rest.max()
+
+
+def test_a_background_pod_on_a_burst_tick_is_refused_by_the_builder():
+    """plant() moves such a pod's end away; one planted afterwards trips its own assertion."""
+    c = ec.case("bursts3k")
+    f, lo, hi = c["bursts"][3]
+    bg = lo - 7
+    run = c["run"].copy()
+    assert run[bg] != f - c["bt"][bg]
+    run[bg] = f - c["bt"][bg]
+    at = np.searchsorted(c["bt"], c["bt"] + run)
+    assert (at == f - 1).sum() == hi - lo + 1   # what the builder's last assertion counts
+
+
+def test_refused_bursts_stand_on_their_side_of_every_edge():
+    name = "bursts3k_refused"
+    assert _ran_to_end(name, ec.LITERAL)
+    c = ec.case(name)
+    got = ec.burst_counts(name, ec.LITERAL)
+    print(name, "burst tick: planned / live / in the CSR / refused / edge")
+    for (f, _, _), row, edge in zip(c["bursts"], got, ec.REFUSED_EDGE):
+        print(f"  {f:6d}: {row[0]:5d} {row[1]:5d} {row[2]:5d} {row[3]:4d} {edge:5d}")
+    assert sorted(set(ec.REFUSED_EDGE) - {0}) == sorted(ec.EDGES)
+    for (m, live, csr, refused), side, edge in zip(got, ec.REFUSED_SIDE, ec.REFUSED_EDGE):
+        assert csr == m and live == m - refused
+        assert refused >= 0.10 * m and csr > live, (m, live, refused)
+        if side < 0:
+            assert live <= edge and m == edge
+        elif side > 0:
+            assert live > edge
+    for edge in ec.EDGES[:-1]:   # both sides of every edge but the last (a count past it alone)
+        assert {s for s, e in zip(ec.REFUSED_SIDE, ec.REFUSED_EDGE) if e == edge} == {-1, +1}
+    assert ec.REFUSED_SIDE[ec.REFUSED_EDGE.index(ec.E_MAX)] == +1
+
+
+# ---- windows -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["bursts3k", "small"])
+@pytest.mark.parametrize("batch", [128, 192, 256])
+def test_windows_at_the_128_and_512_edges(name, batch):
+    c, b = ec.case(name), ec.all_binds(name)
+    live, csr = ec.attached(b, c["run"])
+    np.testing.assert_array_equal(live, csr)
+    win = ec.window_sums(csr, batch)
+    by_size = {hi - lo: _carrier(name, f) for f, lo, hi in c["bursts"]}
+    holds = lambda at: np.arange(max(at - batch + 1, 0), at)   # the batch starts whose window holds pod `at`
+    for edge in (ec.SMALL_MAX_EXP, ec.WIN_SLOTS):
+        if edge not in by_size:
+            continue
+        below, past = win[holds(by_size[edge])], win[holds(by_size[edge + 1])]
+        print(f"{name} B={batch} edge {edge}: windows with the {edge} burst {below.min()}..{below.max()}, "
+              f"with the {edge + 1} burst {past.min()}..{past.max()}")
+        assert (below == edge).all()        # the burst whole and nothing else: the batch goes through
+        assert (past == edge + 1).all()     # past the edge only because of the burst
+    # every window that touches no burst pod holds a trickle
+    touched = np.zeros(len(win), bool)
+    for at in by_size.values():
+        touched[holds(at)] = True
+    print(f"{name} B={batch}: windows off the bursts hold up to {win[~touched].max()}; "
+          f"{int((win > ec.WIN_SLOTS).sum())} windows hold more than {ec.WIN_SLOTS}")
+    assert win[~touched].max() <= batch
+    if name == "bursts3k":
+        assert (win > ec.WIN_SLOTS).sum() >= 5 * (batch - 1)   # the 513, 1,024, 1,025, NEAR and 2,100 bursts
+
+
+# ---- plans ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which,pos", [("head", 1), ("mid", ec.MID)])
+def test_plans_put_the_burst_pod_where_they_say(which, pos):
+    c = ec.case("bursts3k")
+    steps = ec.reference("bursts3k", ec.MODE, which)
+    assert sum(s["k"] for s in steps) == c["ticks"] and _ran_to_end("bursts3k", ec.MODE, which)
+    first = {int(s["binds"]["pod"][0]): s for s in steps if len(s["binds"]["pod"])}
+    for f, lo, hi in c["bursts"]:
+        burst_pod = f - 1
+        assert burst_pod - (pos - 1) in first, (which, f)
+        s = first[burst_pod - (pos - 1)]
+        assert s["binds"]["pod"][pos - 1] == burst_pod and s["binds"]["tick"][pos - 1] == f
+        if which == "mid":
+            assert s["k"] == 192 == len(s["binds"]["pod"])   # one default batch of the chunk resolver
+    # the plans change no bind
+    whole = ec.all_binds("bursts3k")
+    got = ec.all_binds("bursts3k", ec.MODE, which)
+    for fld in whole:
+        np.testing.assert_array_equal(got[fld], whole[fld])
+
+
+def test_ticks_plan_steps_one_tick_around_the_small_bursts():
+    c = ec.case("bursts3k")
+    steps = ec.reference("bursts3k", ec.MODE, "ticks")
+    ends = np.cumsum([s["k"] for s in steps])
+    for f, lo, hi in c["bursts"]:
+        ones = [int(e) for e, s in zip(ends, steps) if s["k"] == 1 and abs(int(e) - f) <= 3]
+        assert ones == (list(range(f - 3, f + 4)) if hi - lo in ec.TICKS_BURSTS else []), f
+    assert sum(s["k"] == 1 for s in steps) == 7 * len(ec.TICKS_BURSTS)
+    # after the step that ends at F - 1 the next pod is the burst pod (what the GPU test probes)
+    for s in steps:
+        for f, lo, hi in c["bursts"]:
+            if hi - lo in (16, 17) and s["tick"] == f - 1:
+                assert s["probe"][0] == f - 1
+
+
+def test_gap_bursts_end_inside_a_pause():
+    c, b = ec.case("gap"), ec.all_binds("gap")
+    ticks = set(b["tick"].tolist())
+    live, _ = ec.attached(b, c["run"])
+    assert len(c["pauses"]) == len(ec.GAP_BURSTS)
+    for (f, lo, hi), (p_lo, p_hi) in zip(c["bursts"], c["pauses"]):
+        assert p_hi - p_lo + 1 >= ec.GAP_PAUSE and p_lo < f < p_hi
+        assert not any(t in ticks for t in range(p_lo, p_hi + 1))   # no bind in the pause
+        at = int(np.searchsorted(b["tick"], p_hi + 1))               # the first bind after it
+        assert b["tick"][at] == p_hi + 1 and b["tick"][at - 1] == p_lo - 1
+        assert live[at] == hi - lo
+    # outside the pauses the queue runs empty now and then, as the stream arrivals do
+    assert (np.diff(b["tick"]) == 2).sum() >= 50
+    # plan `pause`: each step ends inside a pause after the burst tick, the next pod is the carrier
+    steps = ec.reference("gap", ec.MODE, "pause")
+    for (f, lo, hi), s in zip(c["bursts"], steps):
+        assert s["tick"] == f + 50 and s["probe"][0] == int(np.searchsorted(b["tick"], f))
+
+
+@pytest.mark.parametrize("name,sizes", [("pending16", (16,)), ("pending17_600", (17, 600))])
+def test_pending_bursts_end_with_nothing_queued(name, sizes):
+    c = ec.case(name)
+    steps = ec.reference(name, ec.MODE, "parts")
+    assert len(steps) == len(sizes) + 1 == len(c["parts"])
+    for s, (f, lo, hi), (t_next, p_lo, _) in zip(steps, c["bursts"], c["parts"][1:]):
+        last = int(s["binds"]["tick"][-1])
+        assert s["queued"] == 0 and last < f < s["tick"] == t_next   # every submitted pod is bound at F
+        assert s["probe"][0] == p_lo                                   # the first pod of the next part
+    assert steps[-1]["probe"] is None
+
+
+# ---- the edges, restated ---------------------------------------------------------------------------
+def test_restated_edges_agree_with_the_sources():
+    dev, res, ker, cand = _src("ks_device.h"), _src("ks_resolve.hip"), _src("ks_kernels.hip"), _src("ks_cand.hip")
+    const = lambda text, name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
+    assert const(dev, "kTickMaxExp") == ec.TICK_MAX_EXP == 16
+    assert const(dev, "kWinSlots") == ec.WIN_SLOTS == 512
+    assert const(dev, "kWinMaxB") == ec.BIG_MAX_B == _lib.KS_WIN_MAX_B == 256
+    assert const(dev, "kEMax") == ec.E_MAX == 2048
+    assert const(cand, "kPrepThreads") == ec.PREP_THREADS == 1024
+    # RSmall = Cfg4<W, S, TMAX, MAXB, ...>, kMaxExp = kTMax - MAXB
+    m = re.search(r"using RSmall = Cfg4<\d+, \d+, (\d+), (\d+), \d+, \d+>;", res)
+    assert m and "kMaxExp = kTMax - MAXB" in res
+    assert int(m.group(1)) - int(m.group(2)) == ec.SMALL_MAX_EXP == 128 and int(m.group(2)) == 128
+    # RBig = RCfg<THREADS, TMAX, HASH_LOG2, MAXB, ...>, kMaxExp = TMAX - MAXB
+    m = re.search(r"using RBig = RCfg<\w+, (\d+), \d+, (\d+), \d+>;", ker)
+    assert m and "kMaxExp = TMAX - MAXB" in ker
+    assert (int(m.group(1)), int(m.group(2))) == (ec.BIG_TMAX, ec.BIG_MAX_B) == (768, 256)
+    assert ec.BIG_TMAX - ec.BIG_MAX_B == ec.WIN_SLOTS
+    # expire_head_kernel: its launch bound and its launch
+    assert re.search(r"__launch_bounds__\((\d+)\) void expire_head_kernel", ker).group(1) == str(ec.HEAD_THREADS)
+    assert re.search(r"expire_head_kernel, dim3\(S\), dim3\((\d+)\)", ker).group(1) == str(ec.HEAD_THREADS)
+    # the uses the table names
+    assert "myoff - e_base <= kWinSlots" in _src("ks_prep.h")
+    assert "a.n_exp == ks::kTickMaxExp" in _src("ks_step.cpp")
+    assert "(int)qs.size() > ks::kTickMaxExp" in _src("ks_engine.cpp")
+    assert "KS_ENGINE_SMALL_E) ? ks::kSmallE : ks::kEMax" in _src("ks_engine.cpp")
+    assert ec.EDGES == (16, 128, 256, 512, 1024, 2048)
+    assert ec.PIPE_NODES == 65_792

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import group_cases as gc
+from expiry_burst_cases import attached, window_sums
 from kubesim_amd import _lib
 
 
@@ -104,11 +105,8 @@ def _window_expiries(key, batch):
     at s — those attached to pods s + 1 .. s + batch - 1, i.e. finishing in (bind tick of s, bind
     tick of s + batch - 1] (ks_submit_pods attaches an expiry to the first pod bound at or after it)."""
     tr, _ = gc.trace_of(key)
-    b = gc.all_binds(key)
-    d = gc.durations(tr)[b["pod"]]
-    fin = np.where(d > 0, b["tick"] + d, np.iinfo(np.int64).max)
-    bt = b["tick"]
-    return np.array([((fin > bt[s]) & (fin <= bt[s + batch - 1])).sum() for s in range(len(bt) - batch + 1)])
+    _, csr = attached(gc.all_binds(key), gc.durations(tr))
+    return window_sums(csr, batch)
 
 
 def test_short_overflows_the_small_resolvers_expiry_window():
