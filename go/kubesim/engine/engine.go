@@ -609,6 +609,76 @@ func (e *Engine) RemovableAt(t int64, nodes []int32, rows bool) (*Removals, erro
 	return r, status(e, rc)
 }
 
+// Scale-up preview constants (include/ks_engine.h): the most options per ScaleUpAt call, the most
+// nodes an option may append, the words of ScaleUps.Info.
+const (
+	ScaleUpMaxOptions = 64
+	ScaleUpMaxNodes   = 65536
+	ScaleUpInfo       = 4
+)
+
+// ScaleOption is one node-group template (ks_scale_option, 56 bytes): Alloc as LoadNodes takes it
+// (cpu, memory, nvidia.com/gpu in milli-units, -1 absent, pods), the taint and label dictionary bits,
+// and how many copies may be appended.
+type ScaleOption struct {
+	Alloc        [4]int64
+	Taint, Label uint64
+	MaxNodes, _  int32
+}
+
+// ScaleResult is one option's summary (ks_scale_result, 32 bytes): the statuses of the k pods, the
+// pods bound Ok to an appended node, the appended nodes holding a pod, the first pod that was not
+// bound Ok (-1: none) and Path: 0 the batched kernel decided it, 1 the single path.
+type ScaleResult struct {
+	Ok, OverCapacity, NotFound int32
+	OnNew, NodesUsed           int32
+	FirstUnplaced, Path, _     int32
+}
+
+// ScaleUps is the result of ScaleUpAt: one ScaleResult per option, Rows (when asked for) the
+// options' Placement rows, option g's at Rows[g*k : (g+1)*k], and Info = options decided by the
+// batched kernel, options answered through the single path, options in which every pod was bound
+// Ok, distinct shapes.
+type ScaleUps struct {
+	Options []ScaleResult
+	Rows    []Placement
+	Info    [ScaleUpInfo]int64
+}
+
+// ScaleUpAt is where len(shapeOf) pending pods would be bound at tick t <= Tick() if up to
+// MaxNodes empty nodes of a template were appended to k.nodes (kubesim/kubesim.go:168-206 range
+// over it) at indices Nodes() .. Nodes()+MaxNodes-1, for each option on its own: by definition
+// PlaceAt on that extended cluster (ks_scale_up_at).  A Placement's Node >= Nodes() names appended
+// node Node-Nodes().  Options are independent; no engine state changes.
+func (e *Engine) ScaleUpAt(t int64, s *Shapes, shapeOf []int32, options []ScaleOption, rows bool) (*ScaleUps, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	ns, err := s.count()
+	if err != nil {
+		return nil, err
+	}
+	k := ns
+	if shapeOf != nil {
+		k = len(shapeOf)
+	}
+	if k < 1 || k > PlaceMaxPods {
+		return nil, strongerrors.InvalidArgument(errors.New("scale_up: 1..1024 pods"))
+	}
+	if len(options) < 1 || len(options) > ScaleUpMaxOptions {
+		return nil, strongerrors.InvalidArgument(errors.New("scale_up: 1..64 options"))
+	}
+	r := &ScaleUps{Options: make([]ScaleResult, len(options))}
+	var rp *C.ks_placement
+	if rows {
+		r.Rows = make([]Placement, len(options)*k)
+		rp = (*C.ks_placement)(unsafe.Pointer(&r.Rows[0]))
+	}
+	err = status(e, C.ks_scale_up_at(e.h, C.int64_t(t), C.int32_t(ns), i64p(s.Req), u8p(s.KeyMask), u64p(s.Tol),
+		u64p(s.Sel), C.int32_t(k), i32p(shapeOf), C.int32_t(len(options)),
+		(*C.ks_scale_option)(unsafe.Pointer(&options[0])), (*C.ks_scale_result)(unsafe.Pointer(&r.Options[0])), rp,
+		(*C.int64_t)(unsafe.Pointer(&r.Info[0]))))
+	return r, err
+}
+
 // Nodes is the node count of LoadNodes.
 func (e *Engine) Nodes() int { return e.n }
 

@@ -33,6 +33,8 @@
  *                                 (kubesim/kubesim.go:168-206 range over it): where they would go
  *   ks_removable_at ............. ks_drain_at's answer for each of m candidate nodes on its own:
  *                                 which of them could be taken out
+ *   ks_scale_up_at .............. ks_place_at's answer on the cluster plus up to max_nodes empty nodes
+ *                                 of a node-group template, for each of G templates on its own
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
  *   ks_pod_lookup / ks_node_pods  Node.GetPod / GetPodStatus / GetPodList (kubesim/node/node.go:62-93)
  *   ks_group_* .................. one KubeSim.Run per what-if scenario, stepped together
@@ -475,6 +477,62 @@ typedef struct {
 ks_status ks_removable_at(ks_engine* eng, int64_t t, int32_t m, const int32_t* nodes /* [m] */,
                           ks_removal* out /* [m] */, ks_eviction* rows_out /* [cap] or NULL */,
                           int64_t cap, int64_t* n_rows, int64_t* info_out /* [KS_REMOVABLE_INFO] or NULL */);
+
+/* Scale-up preview: where k pending pods would be bound if up to max_nodes nodes of a node-group
+ * template were added, at any past tick ("at tick t" as above), for n_options templates, each on its
+ * own.  No engine state changes.
+ *
+ * Shapes, shape_of, k and the per-pod fields are exactly ks_place_at's.  The answer for option g is
+ * by definition that of ks_place_at on a cluster that is the engine's cluster plus options[g].max_nodes
+ * empty nodes of option g's template: the appended nodes come after the n real ones, at indices
+ * n .. n + max_nodes - 1 — in effect k.nodes is extended before the Filter loop
+ * (kubesim/kubesim.go:168-206 range over k.nodes); each has the template's alloc (as ks_load_nodes
+ * takes it: cpu, memory, nvidia.com/gpu in milli-units, -1 absent, and the pods capacity), taint and
+ * label, no requested quantities and no running pods (kubesim/node/node.go:36-60 on a fresh node).
+ * The same filter mode, filters and scorers apply; the highest aggregated score wins, the lowest
+ * index among equals (kubesim.go:208-222), so a real node beats an equal appended node.
+ * Node.CreatePod's admission test (kubesim/node/node.go:44-47) and the KS_PLACE_NOT_FOUND rule apply
+ * as in ks_place_at; candidates counts appended nodes too; a row's node >= n names appended node
+ * node - n.  A template capacity need not be a multiple of anything the engine holds.  Options are
+ * independent: none sees another's nodes or placements.
+ *
+ * out[g]: the statuses of option g's k pods, on_new (pods bound KS_POD_OK to an appended node),
+ * nodes_used (appended nodes holding at least one Ok pod), first_unplaced (the first pod whose status
+ * is not KS_POD_OK, -1 if none) and path: 0 when the batched kernel decided the option from the one
+ * shared scan, 1 when it was answered by ks_place_at's own rounds on the extended cluster (the
+ * batched kernel stops at a pod whose snapshot list is used up; the result is the same by
+ * definition).  rows_out (may be NULL): [n_options][k] ks_placement.  info_out (may be NULL):
+ * {options decided by the batched kernel, options answered through the single path, options in
+ * which every pod was bound Ok, distinct shapes (n_shapes)}.  With n = 0 the call still works: the
+ * appended nodes are the whole cluster.
+ * KS_EINVAL with nothing written: ks_place_at's argument errors (a NULL engine, req, keymask, tol or
+ * sel before the handle is read), a NULL options or out (likewise), n_options outside
+ * 1..KS_SCALEUP_MAX_OPTIONS, max_nodes outside 0..KS_SCALEUP_MAX_NODES, an alloc below -1 or
+ * >= 2^59, a pods count < 0 or >= 2^59, a non-zero pad.  It answers after an aborted run, on sharded
+ * engines and on scenario-group members, as ks_place_at does. */
+#define KS_SCALEUP_MAX_OPTIONS 64
+#define KS_SCALEUP_MAX_NODES 65536
+#define KS_SCALEUP_INFO 4
+typedef struct {
+    int64_t alloc[4];      /* cpu, memory, nvidia.com/gpu in milli-units (-1 absent), pods: as ks_load_nodes */
+    uint64_t taint, label; /* dictionary bits, as ks_load_nodes */
+    int32_t max_nodes;     /* 0..KS_SCALEUP_MAX_NODES copies may be appended */
+    int32_t pad;           /* 0 */
+} ks_scale_option;         /* 56 bytes */
+typedef struct {
+    int32_t ok, over_capacity, not_found; /* statuses of the k pods */
+    int32_t on_new;         /* pods bound KS_POD_OK to an appended node */
+    int32_t nodes_used;     /* appended nodes holding >= 1 Ok pod */
+    int32_t first_unplaced; /* first pod whose status is not KS_POD_OK, -1 if none */
+    int32_t path;           /* 0 batched kernel, 1 single path */
+    int32_t pad;
+} ks_scale_result;          /* 32 bytes */
+ks_status ks_scale_up_at(ks_engine* eng, int64_t t, int32_t n_shapes, const int64_t* req /* [n_shapes][3] */,
+                         const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel, int32_t k,
+                         const int32_t* shape_of /* [k], or NULL: k == n_shapes, pod j is shape j */,
+                         int32_t n_options, const ks_scale_option* options /* [n_options] */,
+                         ks_scale_result* out /* [n_options] */, ks_placement* rows_out /* [n_options][k] or NULL */,
+                         int64_t* info_out /* [KS_SCALEUP_INFO] or NULL */);
 
 /* Name-keyed queries over the binds made so far (Node.GetPod / GetPodStatus / GetPodList,
  * kubesim/node/node.go:62-93).  ks_pod_lookup: the FIFO index of the pod stored on `node` under

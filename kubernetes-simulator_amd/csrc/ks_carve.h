@@ -3,7 +3,7 @@
 // A layout is written once, as a sequence of Carve::take() calls, and run twice: with a null base
 // the cursor only counts and `at` is the size to reserve; with the real base the same calls give
 // the pointers.  The reserved size and the ranges therefore cannot disagree.  The layouts of the
-// placement and drain previews and of the removal scan live here too, so a stand-alone host program
+// placement, drain and scale-up previews and of the removal scan live here too, so a stand-alone host program
 // can check them.
 #pragma once
 #include <cstdint>
@@ -126,6 +126,36 @@ inline RemovableScratch carve_removable(Carve& qs, int64_t np, int64_t nblk, int
     s.r.cands = qs.take<ks::RemovalCand>(s.cand_cap);
     s.r.rows = qs.take<ks::Eviction>(n_ev);
     s.r.out = qs.take<ks::Removal>(s.cand_cap);
+    return s;
+}
+
+// ks_scale_up_at: the shared lists' buffers on the base state (b: n real nodes, k pods' shape_of, no
+// placements of its own), the batched resolver's options, rows [n_options][k] and summaries, and
+// the single path's extended cluster for the largest option: n + max_ext rows padded to 64 (np_ext),
+// its six constant fields (ext_node, field f at ext_node + f * np_ext), and its own round buffers x
+// (state [4][np_ext], lists over nblk_ext blocks, out [k])
+struct ScaleScratch {
+    ks::PlaceBufs b;
+    ks::ScaleBufs sb;
+    int64_t n_ext, np_ext, nblk_ext;
+    int64_t* ext_node;
+    ks::PlaceBufs x;
+};
+inline ScaleScratch carve_scale_up(Carve& qs, Carve& qi, int64_t n, int64_t np, int64_t nblk, int64_t k,
+                                   int64_t n_options, int64_t max_ext) {
+    ScaleScratch s{};
+    s.b = carve_place(qs, np, nblk, k, 0);
+    s.b.cnt = qi.take<int32_t>(ks::kPlaceMaxShapes * nblk);
+    s.sb.opts = qs.take<ks::ScaleOption>(n_options);
+    s.sb.rows = qs.take<ks::Placement>(n_options * k);
+    s.sb.out = qs.take<ks::ScaleResult>(n_options);
+    s.n_ext = n + max_ext;
+    s.np_ext = (s.n_ext + 63) / 64 * 64;
+    if (s.np_ext < 64) s.np_ext = 64;
+    s.nblk_ext = (s.n_ext + 255) / 256;
+    s.ext_node = qs.take<int64_t>(6 * s.np_ext);
+    s.x = carve_place(qs, s.np_ext, s.nblk_ext, k, k);
+    s.x.cnt = qi.take<int32_t>(ks::kPlaceMaxShapes * s.nblk_ext);
     return s;
 }
 

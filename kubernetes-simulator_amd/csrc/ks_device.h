@@ -1711,4 +1711,113 @@ struct RemovableBufs {
 hipError_t launch_removable_resolve(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, const RemovableBufs& r,
                                     const PodRec* shapes, int64_t cand0, int64_t n_cand, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------
+// Scale-up preview (ks_scale_up_at, ks_scaleup.hip): for each of G options on its own, the answer of
+// the placement preview above on the cluster plus max_nodes empty nodes of the option's template,
+// appended at indices n .. n + max_nodes - 1 (k.nodes extended before the Filter loop,
+// kubesim/kubesim.go:168-206).  Options are independent: every one starts from the same state at t,
+// only the appended nodes differ.
+//
+// Exactness of one shared scan.  The snapshot top-L lists and the candidate counts are built once,
+// on the base state at t over the n real nodes (launch_place_lists).  An appended node is in no
+// list.  For option g the resolver keeps
+//   - the invariant that the appended nodes in its changed set are a prefix n .. n + u - 1.  Every
+//     other appended node is the empty template record: identical but for the index.  Among
+//     identical nodes the key make_key(total + 1, node) is largest at the lowest index, so node
+//     n + u stands for all of them: its key F (scaleup_fresh_key; 0 when u = max_nodes or the
+//     template has no entry in the pod's score map) is the maximum over the unchanged appended nodes;
+//   - D' = max(D, F) in D's place, D the largest key over the changed nodes, real and appended;
+//   - running candidate counts that start at the base count plus max_nodes times
+//     place_is_cand(shape, empty template) (scaleup_count_start) and move by place_cand_delta like
+//     any other bind.
+// Read the argument above place_decide over the real nodes, with the appended nodes on D's side:
+// "entries above S are changed, everything below S or outside the list is smaller and unchanged"
+// still covers every unchanged real node, because appended nodes are outside every list and never
+// S.  The extended cluster's argmax is the maximum of the real nodes' argmax and the appended
+// nodes' argmax max(D over appended changed nodes, F); cases (1)-(3) of place_decide give the
+// former from S and D over the real changed nodes, and the maximum is monotone, so
+// place_decide(S, last, D') is the extended argmax in each of them: (1) max(S, D'); (2) the list is
+// complete, every unchanged real node has key 0: D' or none; (3) every unchanged real node is below
+// the list's last key < D'.  When n + u wins it joins the changed set and u grows by one
+// (scaleup_takes_fresh): the prefix holds.  A real node beats an equal appended node, and n + u
+// beats n + u + 1, by the index half of the key alone.
+//
+// Case (4), kPlaceStop: an unchanged real node outside the list may win.  The resolver commits
+// nothing, so it cannot rescan: it marks the option stopped and the host answers that option from
+// pod 0 on its extended cluster built on the device (the single path: place_rounds on n + max_nodes
+// nodes), which is the definition itself.  A stop needs all L entries of one list flagged, so at
+// least L earlier pods bound to distinct real list nodes.
+// ---------------------------------------------------------------------------------------------
+constexpr int kScaleMaxOptions = 64;      // KS_SCALEUP_MAX_OPTIONS
+constexpr int kScaleMaxNodes = 65536;     // KS_SCALEUP_MAX_NODES
+enum : int32_t { kScaleBatched = 0, kScaleSingle = 1, kScaleStopped = -1 };
+
+struct ScaleOption {  // an option on the device: the empty template node in the call's units
+    NodeV tmpl;
+    int32_t max_nodes, pad;
+};
+static_assert(sizeof(ScaleOption) == 88, "ScaleOption layout");
+
+struct ScaleResult {  // = ks_scale_result
+    int32_t ok, over_capacity, not_found, on_new, nodes_used, first_unplaced, path, pad;
+};
+static_assert(sizeof(ScaleResult) == 32, "ks_scale_result layout");
+
+// The empty node of a template: alloc[4] in milli-units (-1 absent), divided by `unit` (the engine's
+// scale when the call runs in device units, 1 when it runs in milli-units).
+__host__ __device__ __forceinline__ NodeV scaleup_template(const int64_t* alloc, uint64_t taint, uint64_t label,
+                                                           const QScale& unit) {
+    NodeV v{};
+    v.ac = alloc[0] > 0 ? alloc[0] / unit.f[0] : alloc[0];
+    v.am = alloc[1] > 0 ? alloc[1] / unit.f[1] : alloc[1];
+    v.ag = alloc[2] > 0 ? alloc[2] / unit.f[2] : alloc[2];
+    v.ap = alloc[3];
+    v.taint = taint; v.label = label;
+    return v;
+}
+
+// place_whole_units' sibling: also every present template capacity is a whole multiple of sc
+__host__ __device__ __forceinline__ bool scaleup_whole_units(const PodRec* shapes, int n_shapes, const int64_t* alloc,
+                                                             int n_options, int64_t alloc_stride, const QScale& sc) {
+    bool whole = place_whole_units(shapes, n_shapes, sc);
+    for (int g = 0; g < n_options; ++g)
+        for (int c = 0; c < 3; ++c)
+            if (alloc[g * alloc_stride + c] > 0 && alloc[g * alloc_stride + c] % sc.f[c] != 0) whole = false;
+    return whole;
+}
+
+// F: the key of appended node n + u on the empty template record, the largest over the appended
+// nodes outside the changed set; 0 when there is none left
+__host__ __device__ __forceinline__ uint64_t scaleup_fresh_key(const Cfg& c, const PodRec& p, const NodeV& tmpl,
+                                                               int32_t n, int32_t u, int32_t max_nodes) {
+    return u < max_nodes ? place_key(c, p, tmpl, (uint32_t)n + (uint32_t)u) : 0ull;
+}
+
+// a shape's running candidate count before the first pod: every appended node is the empty template
+__host__ __device__ __forceinline__ long long scaleup_count_start(const Cfg& c, const PodRec& shape, const NodeV& tmpl,
+                                                                  long long base, int32_t max_nodes) {
+    return base + (place_is_cand(c, shape, tmpl) ? (long long)max_nodes : 0);
+}
+
+// the prefix rule: the winner X is the first appended node outside the changed set, so it joins it
+__host__ __device__ __forceinline__ bool scaleup_takes_fresh(uint32_t X, int32_t n, int32_t u, int32_t max_nodes) {
+    return u < max_nodes && X == (uint32_t)n + (uint32_t)u;
+}
+
+// Scratch of the batched resolver (device): opts [n_options]; rows [n_options][k]; out [n_options].
+struct ScaleBufs {
+    const ScaleOption* opts;
+    Placement* rows;
+    ScaleResult* out;
+};
+// every option against the lists b.top / b.ccount of pc.n_shapes shapes (after launch_place_lists on
+// the same shapes and state); b.state is read only
+hipError_t launch_scaleup_resolve(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, const ScaleBufs& sb,
+                                  int32_t n_options, hipStream_t st);
+// An option's extended cluster (the single path): the six constant fields of n_ext = n + max_nodes
+// rows at dst (field f at dst + f * np_ext: ac am ag ap taint label), rows < n the cluster's times sc,
+// rows n .. n_ext - 1 the template, the padding rows absent (-1, pods 0)
+hipError_t launch_scaleup_extend(const NodeSoA& s, int32_t n, const QScale& sc, const ScaleOption& opt, int64_t np_ext,
+                                 int64_t* dst, hipStream_t st);
+
 }  // namespace ks

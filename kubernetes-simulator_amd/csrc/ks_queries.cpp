@@ -1,6 +1,6 @@
 // ks_queries.cpp — the entry points of include/ks_engine.h that answer about a run after the fact:
 // filter / score of a pod, usage, the past-tick state queries, headroom, the placement and drain
-// previews, the removal scan and the name-keyed lookups.  They read the engine (ks_host.h) and write nothing a later
+// previews, the removal scan, the scale-up preview and the name-keyed lookups.  They read the engine (ks_host.h) and write nothing a later
 // ks_step reads; their device scratch is the grow-only d_qs / d_qi, carved by ks_carve.h.
 #include <cstring>
 
@@ -433,15 +433,17 @@ static ks_status upload_shapes(ks_engine* e, const ks::PlaceBufs& b, std::vector
 }
 
 // The rounds that decide pods [0, pc.k) of the uploaded shapes: each launches scan + merge + resolver
-// from the first undecided pod and reads back 16 bytes.  what and pod_base name the pod in the message
+// from the first undecided pod and reads back 16 bytes.  nodes: the cluster's constants (e->s, or an
+// extended cluster of ks_scale_up_at).  what and pod_base name the pod in the message
 // of a round that decided none; *rounds grows by the rounds run.
-static ks_status place_rounds(ks_engine* e, const ks::PlaceCfg& pc, const ks::PlaceBufs& b, const int32_t* so,
-                              const uint32_t* cordon, const char* what, int64_t pod_base, int64_t* rounds) {
+static ks_status place_rounds(ks_engine* e, const ks::NodeSoA& nodes, const ks::PlaceCfg& pc, const ks::PlaceBufs& b,
+                              const int32_t* so, const uint32_t* cordon, const char* what, int64_t pod_base,
+                              int64_t* rounds) {
     int32_t first = 0;
     for (int64_t r = 1; first < pc.k; r++) {
         uint64_t active = 0;
         for (int32_t j = first; j < pc.k; j++) active |= 1ull << so[j];
-        HIPCHK(e, ks::launch_place_round(e->s, pc, b, first, active, e->st, cordon));
+        HIPCHK(e, ks::launch_place_round(nodes, pc, b, first, active, e->st, cordon));
         int32_t rb[4] = {0, 1, 0, 0};
         HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
         HIPCHK(e, hipStreamSynchronize(e->st));
@@ -495,7 +497,7 @@ ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* 
     std::vector<unsigned long long> h_up;
     if (ks_status r = upload_shapes(e, b, h_up, e->h_shapes.data(), n_shapes, so.data(), k); r != KS_OK) return r;
     const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, k, n_shapes, (int32_t)nblk};
-    if (ks_status r = place_rounds(e, pc, b, so.data(), nullptr, "place: the round from pod", 0, &info[0]); r != KS_OK)
+    if (ks_status r = place_rounds(e, e->s, pc, b, so.data(), nullptr, "place: the round from pod", 0, &info[0]); r != KS_OK)
         return r;
     // rb[4], then out[k]: one range, read once
     constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
@@ -631,7 +633,7 @@ ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* n
             if (ks_status r = upload_shapes(e, b, h_up, seg_shapes, ns, so.data(), k); r != KS_OK) return r;
             b.out = s.b.out + start;
             const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n, k, ns, (int32_t)nblk};
-            if (ks_status r = place_rounds(e, pc, b, so.data(), d.cordon, "drain: the round from evicted pod", start, &info[0]);
+            if (ks_status r = place_rounds(e, e->s, pc, b, so.data(), d.cordon, "drain: the round from evicted pod", start, &info[0]);
                 r != KS_OK)
                 return r;
             info[4]++;
@@ -810,6 +812,169 @@ ks_status ks_removable_at(ks_engine* e, int64_t t, int32_t m, const int32_t* nod
     std::memcpy(out, h_out.data(), sizeof(ks_removal) * m);
     if (rows_out && n_ev) std::memcpy(rows_out, h_rows.data(), sizeof(ks_eviction) * n_ev);
     if (info_out) std::copy(info, info + KS_REMOVABLE_INFO, info_out);
+    return KS_OK;
+}
+
+// ---- scale-up preview (ks_scaleup.hip) -----------------------------------------------------------
+// ks_place_at's question on n_options extended clusters: the engine's cluster plus up to max_nodes
+// empty nodes of a template.  One rebuild of the state at t and one scan + merge over the real nodes
+// serve every option (ks::launch_place_lists); one workgroup per option decides the pods from those
+// lists (ks::launch_scaleup_resolve) and the host reads the summaries back once.  An option the
+// resolver stopped at — a snapshot list used up — is answered from pod 0 through the single path:
+// its extended cluster is built in the scratch (ks::launch_scaleup_extend, the state rebuilt at the
+// new stride) and ks_place_at's own rounds run on it, which is the definition itself.  With no real
+// node every option takes the single path.
+// Units: the call runs in device units when every masked request and every present template
+// capacity is a whole multiple of the engine's unit (ks::scaleup_whole_units), else in milli-units.
+static_assert(KS_SCALEUP_MAX_OPTIONS == ks::kScaleMaxOptions && KS_SCALEUP_MAX_NODES == ks::kScaleMaxNodes &&
+              KS_SCALEUP_INFO == 4 && sizeof(ks_scale_option) == 56 && sizeof(ks_scale_result) == sizeof(ks::ScaleResult) &&
+              offsetof(ks_scale_option, alloc) == 0 && offsetof(ks_scale_result, ok) == offsetof(ks::ScaleResult, ok) &&
+              offsetof(ks_scale_result, on_new) == offsetof(ks::ScaleResult, on_new) &&
+              offsetof(ks_scale_result, nodes_used) == offsetof(ks::ScaleResult, nodes_used) &&
+              offsetof(ks_scale_result, first_unplaced) == offsetof(ks::ScaleResult, first_unplaced) &&
+              offsetof(ks_scale_result, path) == offsetof(ks::ScaleResult, path),
+              "ks_scale_up_at constants and records");
+
+// an option's summary from its k rows on a cluster of n real nodes (the single path; the batched
+// kernel counts the same on the device)
+static ks::ScaleResult scale_summary(const ks::Placement* rows, int32_t k, int64_t n) {
+    ks::ScaleResult r{0, 0, 0, 0, 0, -1, ks::kScaleSingle, 0};
+    std::vector<int32_t> used;
+    for (int32_t i = 0; i < k; i++) {
+        const ks::Placement& v = rows[i];
+        if (v.status == KS_POD_OK) {
+            r.ok++;
+            if (v.node >= n) {
+                r.on_new++;
+                used.push_back(v.node);
+            }
+            continue;
+        }
+        (v.status == KS_POD_OVER_CAPACITY ? r.over_capacity : r.not_found)++;
+        if (r.first_unplaced < 0) r.first_unplaced = i;
+    }
+    std::sort(used.begin(), used.end());
+    r.nodes_used = (int32_t)(std::unique(used.begin(), used.end()) - used.begin());
+    return r;
+}
+
+ks_status ks_scale_up_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* req, const uint8_t* keymask,
+                         const uint64_t* tol, const uint64_t* sel, int32_t k, const int32_t* shape_of, int32_t n_options,
+                         const ks_scale_option* options, ks_scale_result* out, ks_placement* rows_out, int64_t* info_out) {
+    if (!e || !req || !keymask || !tol || !sel || !options || !out) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "scale_up"); r != KS_OK) return r;
+    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "scale_up: %d pods outside [1, %d]", (int)k, KS_PLACE_MAX_PODS);
+    if (!shape_of && k != n_shapes)
+        return fail(e, KS_EINVAL, "scale_up: %d pods without shape_of need %d shapes, not %d", (int)k, (int)k, (int)n_shapes);
+    std::vector<int32_t> so(k);
+    for (int32_t j = 0; j < k; j++) {
+        so[j] = shape_of ? shape_of[j] : j;
+        if (so[j] < 0 || so[j] >= n_shapes)
+            return fail(e, KS_EINVAL, "scale_up: pod %d has shape %d outside [0, %d)", (int)j, (int)so[j], (int)n_shapes);
+    }
+    if (n_options < 1 || n_options > KS_SCALEUP_MAX_OPTIONS)
+        return fail(e, KS_EINVAL, "scale_up: %d options outside [1, %d]", (int)n_options, KS_SCALEUP_MAX_OPTIONS);
+    int64_t max_ext = 0;
+    for (int32_t g = 0; g < n_options; g++) {
+        const ks_scale_option& o = options[g];
+        if (o.max_nodes < 0 || o.max_nodes > KS_SCALEUP_MAX_NODES)
+            return fail(e, KS_EINVAL, "scale_up option %d: max_nodes %d outside [0, %d]", (int)g, (int)o.max_nodes, KS_SCALEUP_MAX_NODES);
+        for (int c = 0; c < 3; c++)
+            if (o.alloc[c] < -1 || o.alloc[c] >= kMaxValue)
+                return fail(e, KS_EINVAL, "scale_up option %d: capacity %d out of range", (int)g, c);
+        if (o.alloc[3] < 0 || o.alloc[3] >= kMaxValue) return fail(e, KS_EINVAL, "scale_up option %d: pods capacity out of range", (int)g);
+        if (o.pad != 0) return fail(e, KS_EINVAL, "scale_up option %d: pad is %d, not 0", (int)g, (int)o.pad);
+        max_ext = std::max<int64_t>(max_ext, o.max_nodes);
+    }
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    // the call's units: device units when every request and template capacity is whole, else milli-units
+    const ks::QScale milli = milli_scale(e);
+    static_assert(sizeof(ks_scale_option) % sizeof(int64_t) == 0, "alloc stride in words");
+    const bool whole = ks::scaleup_whole_units(e->h_shapes.data(), n_shapes, options[0].alloc, n_options,
+                                               sizeof(ks_scale_option) / sizeof(int64_t), milli);
+    const ks::QScale sc = whole ? kDeviceUnits : milli;
+    if (whole)
+        for (ks::PodRec& r : e->h_shapes)
+            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
+    std::vector<ks::ScaleOption> h_opts(n_options);
+    for (int32_t g = 0; g < n_options; g++)
+        h_opts[g] = ks::ScaleOption{ks::scaleup_template(options[g].alloc, options[g].taint, options[g].label,
+                                                         whole ? milli : kDeviceUnits),
+                                    options[g].max_nodes, 0};
+    std::vector<ks::ScaleResult> h_out(n_options);
+    std::vector<ks::Placement> h_rows((size_t)n_options * k);
+    std::vector<int32_t> single;  // the options the single path answers
+    int64_t info[KS_SCALEUP_INFO] = {0, 0, 0, n_shapes};
+    const int64_t q_hi = bound_by(e, t);
+    int64_t nb = 0;
+    if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+    ScaleScratch s;
+    CARVE_SCRATCH(e, s = carve_scale_up(qs, qi, n, np, nblk, k, n_options, max_ext));
+    std::vector<unsigned long long> h_up;
+    if (n > 0) {
+        // ---- one state, one set of lists, every option's workgroup, one read-back ----
+        if (ks_status r = rebuild_state(e, nb, q_hi, t, sc, 1, np, (unsigned long long*)s.b.state); r != KS_OK) return r;
+        if (ks_status r = upload_shapes(e, s.b, h_up, e->h_shapes.data(), n_shapes, so.data(), k); r != KS_OK) return r;
+        HIPCHK(e, hipMemcpyAsync((void*)s.sb.opts, h_opts.data(), sizeof(ks::ScaleOption) * n_options, hipMemcpyHostToDevice, e->st));
+        const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, k, n_shapes, (int32_t)nblk};
+        const uint64_t active = n_shapes >= 64 ? ~0ull : (1ull << n_shapes) - 1ull;
+        HIPCHK(e, ks::launch_place_lists(e->s, pc, s.b, active, e->st));
+        HIPCHK(e, ks::launch_scaleup_resolve(e->s, pc, s.b, s.sb, n_options, e->st));
+        HIPCHK(e, hipMemcpyAsync(h_out.data(), s.sb.out, sizeof(ks::ScaleResult) * n_options, hipMemcpyDeviceToHost, e->st));
+        if (rows_out)
+            HIPCHK(e, hipMemcpyAsync(h_rows.data(), s.sb.rows, sizeof(ks::Placement) * h_rows.size(), hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        for (int32_t g = 0; g < n_options; g++) {
+            const ks::ScaleResult& v = h_out[g];
+            if (v.path == ks::kScaleStopped) single.push_back(g);
+            else if (v.path != ks::kScaleBatched || v.ok + v.over_capacity + v.not_found != k)
+                return fail(e, KS_EDEVICE, "scale_up: option %d was not decided", (int)g);
+        }
+    } else {
+        for (int32_t g = 0; g < n_options; g++) single.push_back(g);
+    }
+    // ---- the single path: ks_place_at's rounds on the option's extended cluster ----
+    for (int32_t g : single) {
+        ks::Placement* rows = h_rows.data() + (size_t)g * k;
+        const int64_t n_ext = n + h_opts[g].max_nodes;
+        if (n_ext == 0) {  // no node at all
+            for (int32_t j = 0; j < k; j++) rows[j] = ks::Placement{-1, ks::kPlaceNotFound, -1, 0};
+            h_out[g] = scale_summary(rows, k, n);
+            continue;
+        }
+        const int64_t np_g = std::max<int64_t>(64, (n_ext + 63) / 64 * 64), nblk_g = (n_ext + 255) / 256;
+        if (np_g > s.np_ext || nblk_g > s.nblk_ext) return fail(e, KS_EDEVICE, "scale_up: option %d outgrows the scratch", (int)g);
+        HIPCHK(e, ks::launch_scaleup_extend(e->s, (int32_t)n, sc, h_opts[g], np_g, s.ext_node, e->st));
+        ks::PlaceBufs x = s.x;
+        x.n_pad = np_g;
+        // the state at the new stride: rows >= n are written by no bind, so the appended nodes start empty
+        if (n > 0) {
+            if (ks_status r = rebuild_state(e, nb, q_hi, t, sc, 1, np_g, (unsigned long long*)x.state); r != KS_OK) return r;
+        } else {
+            HIPCHK(e, hipMemsetAsync(x.state, 0, sizeof(int64_t) * 4 * np_g, e->st));
+        }
+        if (ks_status r = upload_shapes(e, x, h_up, e->h_shapes.data(), n_shapes, so.data(), k); r != KS_OK) return r;
+        ks::NodeSoA sx{};
+        sx.ac = s.ext_node; sx.am = s.ext_node + np_g; sx.ag = s.ext_node + 2 * np_g; sx.ap = s.ext_node + 3 * np_g;
+        sx.taint = (uint64_t*)(s.ext_node + 4 * np_g); sx.label = (uint64_t*)(s.ext_node + 5 * np_g);
+        sx.rc = x.state; sx.rm = x.state + np_g; sx.rg = x.state + 2 * np_g; sx.nr = x.state + 3 * np_g;
+        // (the extended constants are in the call's units already: scale 1)
+        const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n_ext, k, n_shapes, (int32_t)nblk_g};
+        int64_t rounds = 0;
+        if (ks_status r = place_rounds(e, sx, pc, x, so.data(), nullptr, "scale_up: the round from pod", 0, &rounds); r != KS_OK)
+            return r;
+        HIPCHK(e, hipMemcpyAsync(rows, x.out, sizeof(ks::Placement) * k, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        h_out[g] = scale_summary(rows, k, n);
+    }
+    info[1] = (int64_t)single.size();
+    info[0] = n_options - info[1];
+    for (int32_t g = 0; g < n_options; g++) info[2] += h_out[g].ok == k;
+    std::memcpy(out, h_out.data(), sizeof(ks_scale_result) * n_options);
+    if (rows_out) std::memcpy(rows_out, h_rows.data(), sizeof(ks_placement) * h_rows.size());
+    if (info_out) std::copy(info, info + KS_SCALEUP_INFO, info_out);
     return KS_OK;
 }
 

@@ -63,6 +63,13 @@ KS_DRAIN_INFO = 6
 # (csrc/ks_device.h kRemovableMaxPods = KS_PLACE_L - 1)
 KS_REMOVABLE_INFO = 6
 KS_REMOVABLE_MAX_BATCHED = 31
+# ks_scale_up_at: options per call, appended nodes per option, the info words (options decided by the
+# batched kernel, options answered through the single path, options in which every pod was bound Ok,
+# distinct shapes); ks_scale_result.path
+KS_SCALEUP_MAX_OPTIONS = 64
+KS_SCALEUP_MAX_NODES = 65536
+KS_SCALEUP_INFO = 4
+KS_SCALEUP_PATH_BATCHED, KS_SCALEUP_PATH_SINGLE = 0, 1
 
 STATUS_NAMES = {KS_OK: "OK", KS_EINVAL: "InvalidArgument", KS_ENOTFOUND: "NotFound",
                 KS_EDEVICE: "DeviceError", KS_ENOMEM: "OutOfMemory", KS_ERANGE: "OutOfDomain"}
@@ -77,7 +84,7 @@ EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods"
                     "ks_shard_layout", "ks_merge_candidates",
                     "ks_requested_at", "ks_filter_at", "ks_score_at", "ks_cluster_series", "ks_node_peaks",
                     "ks_headroom_at", "ks_headroom_series", "ks_place_at", "ks_drain_at",
-                    "ks_removable_at",
+                    "ks_removable_at", "ks_scale_up_at",
                     # include/ks_ingest.h
                     "ks_parse_quantity", "ks_parse_simspec", "ks_cluster_parse", "ks_cluster_free",
                     "ks_cluster_nodes", "ks_cluster_tick", "ks_cluster_start_clock", "ks_cluster_arrays",
@@ -244,10 +251,11 @@ def load():
     L.ks_place_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, p, p, p]
     L.ks_drain_at.argtypes = [p, C.c_int64, C.c_int32, p, p, C.c_int64, C.POINTER(C.c_int64), p, p]
     L.ks_removable_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, C.c_int64, C.POINTER(C.c_int64), p]
+    L.ks_scale_up_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, C.c_int32, p, p, p, p]
     for f in ("ks_load_nodes", "ks_submit_pods", "ks_step", "ks_filter", "ks_score", "ks_usage", "ks_usage_at",
               "ks_usage_digest", "ks_pod_lookup", "ks_node_pods", "ks_requested_at", "ks_filter_at", "ks_score_at",
               "ks_cluster_series", "ks_node_peaks", "ks_headroom_at", "ks_headroom_series", "ks_place_at",
-              "ks_drain_at", "ks_removable_at"):
+              "ks_drain_at", "ks_removable_at", "ks_scale_up_at"):
         getattr(L, f).restype = C.c_int
     L.ks_current_tick.argtypes = [p]
     L.ks_current_tick.restype = C.c_int64

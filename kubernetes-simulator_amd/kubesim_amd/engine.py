@@ -20,7 +20,9 @@ scheduleOne, what-if   ``place_at``: where k more pods would be bound at a past 
                        private copy of the state (kubesim/kubesim.go:143-225);
                        ``drain_at``: where the pods running on a node set would go if the
                        set left k.nodes (kubesim/kubesim.go:168-206); ``removable_at``: that
-                       answer for each of m candidate nodes on its own
+                       answer for each of m candidate nodes on its own; ``scale_up_at``:
+                       ``place_at`` on the cluster plus up to M empty nodes of a node-group
+                       template, for each of G templates on its own
 =====================  ==============================================================
 
 Errors come back as :class:`KsError` with the reference's kind (``InvalidArgument`` /
@@ -63,6 +65,13 @@ assert EVICTION_DTYPE.itemsize == 40
 REMOVAL_DTYPE = np.dtype([("node", np.int32), ("evicted", np.int32), ("ok", np.int32), ("over_capacity", np.int32),
                           ("not_found", np.int32), ("removable", np.int32), ("first_row", np.int64)])
 assert REMOVAL_DTYPE.itemsize == 32
+# ks_scale_option, ks_scale_result (include/ks_engine.h)
+SCALE_OPTION_DTYPE = np.dtype([("alloc", np.int64, (4,)), ("taint", np.uint64), ("label", np.uint64),
+                               ("max_nodes", np.int32), ("pad", np.int32)])
+SCALE_RESULT_DTYPE = np.dtype([("ok", np.int32), ("over_capacity", np.int32), ("not_found", np.int32),
+                               ("on_new", np.int32), ("nodes_used", np.int32), ("first_unplaced", np.int32),
+                               ("path", np.int32), ("pad", np.int32)])
+assert SCALE_OPTION_DTYPE.itemsize == 56 and SCALE_RESULT_DTYPE.itemsize == 32
 
 
 def _config(tick_seconds, filter_mode, filters, scorers, device, batch_pods, engine_flags):
@@ -374,6 +383,49 @@ class Engine:
             res["rows"] = dict(pod=rec["pod"].copy(), from_node=rec["from"].copy(), node=rec["node"].copy(),
                                status=rec["status"].copy(), score=rec["score"].copy(),
                                candidates=rec["candidates"].copy())
+        return res
+
+    # -- scale-up preview (include/ks_engine.h, ks_scale_up_at) ---------------------------------
+    def scale_up_at(self, t: int, shapes: dict, options, shape_of=None, rows: bool = False):
+        """Where the pending pods would be bound at tick t if up to ``max_nodes`` empty nodes of a
+        node-group template were appended to the cluster (at indices n .. n + max_nodes - 1), for each
+        option on its own: by definition ``place_at`` on that extended cluster — options are
+        independent, no engine state changes.  ``shapes`` / ``shape_of`` as for ``place_at``;
+        ``options``: dicts (or a SCALE_OPTION_DTYPE array) with ``alloc`` [4] as ``load_nodes`` takes
+        it, ``taint``, ``label`` and ``max_nodes``.  Returns a dict of arrays over the options —
+        ``ok`` / ``over_capacity`` / ``not_found``, ``on_new`` (pods bound Ok to an appended node),
+        ``nodes_used`` (appended nodes holding a pod), ``first_unplaced`` (-1: every pod bound Ok),
+        ``path`` (0 batched kernel, 1 single path) — plus ``info`` (options decided by the batched
+        kernel, options answered through the single path, options in which every pod was bound Ok,
+        distinct shapes) and ``rows``: with ``rows=True`` ``place_at``'s arrays (``node``, ``status``,
+        ``score``, ``candidates``), each [options][k]; a ``node`` >= n names appended node
+        ``node - n``; else None."""
+        ns, req, km, tol, sel = self._shapes(shapes)
+        so = None if shape_of is None else _c(shape_of, np.int32)
+        k = ns if so is None else len(so)
+        if isinstance(options, np.ndarray) and options.dtype == SCALE_OPTION_DTYPE:
+            opt = np.ascontiguousarray(options).reshape(-1)
+        else:
+            opt = np.zeros(len(options), SCALE_OPTION_DTYPE)
+            for g, o in enumerate(options):
+                opt[g]["alloc"] = _c(o["alloc"], np.int64).reshape(4)
+                opt[g]["taint"], opt[g]["label"] = int(o.get("taint", 0)), int(o.get("label", 0))
+                opt[g]["max_nodes"] = int(o["max_nodes"])
+        m = len(opt)
+        out = np.zeros(max(m, 1), SCALE_RESULT_DTYPE)
+        rec = np.zeros(max(m * k, 1), PLACEMENT_DTYPE) if rows else None
+        info = np.zeros(_lib.KS_SCALEUP_INFO, np.int64)
+        self._check(self._L.ks_scale_up_at(self.h, t, ns, _p(req), _p(km), _p(tol), _p(sel), k,
+                                           None if so is None else _p(so), m, _p(opt), _p(out),
+                                           _p(rec) if rows else None, _p(info)))
+        out = out[:m]
+        res = {f: out[f].copy() for f in ("ok", "over_capacity", "not_found", "on_new", "nodes_used", "first_unplaced",
+                                          "path")}
+        res["info"] = info
+        res["rows"] = None
+        if rows:
+            rec = rec[:m * k].reshape(m, k)
+            res["rows"] = {f: rec[f].copy() for f in ("node", "status", "score", "candidates")}
         return res
 
     def pod_lookup(self, node: int, key_id: int):
