@@ -1477,9 +1477,11 @@ struct PlaceBufs {
 // above holds verbatim over the non-cordoned nodes.
 hipError_t launch_place_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, int32_t first, uint64_t active,
                               hipStream_t st, const uint32_t* cordon = nullptr);
-// the lists alone (ks_removable_at): scan + merge for the shapes in `active` on the state as it is,
-// without a cordon — b.top and b.ccount of pc.n_shapes shapes; no resolver, nothing is committed
-hipError_t launch_place_lists(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, uint64_t active, hipStream_t st);
+// the lists alone (ks_removable_at, ks_scale_up_at; a round's first half): scan + merge for the shapes
+// in `active` on the state as it is — b.top and b.ccount of pc.n_shapes shapes; no resolver, nothing
+// is committed
+hipError_t launch_place_lists(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, uint64_t active, hipStream_t st,
+                              const uint32_t* cordon = nullptr);
 // after[n][4] from state [4][n_pad], the three quantities times sc
 hipError_t launch_place_after(const int64_t* state, int64_t n_pad, int32_t n_nodes, const QScale& sc, long long* after,
                               hipStream_t st);

@@ -89,7 +89,7 @@ static ks_status rebuild_state(ks_engine* e, int64_t nb, int64_t q_hi, int64_t t
     return KS_OK;
 }
 
-// the tail of ks_filter / ks_score (_at): copy the n-node result out once the evaluation is queued
+// the tail of a query over n > 0 nodes: copy the result out once its kernels are queued (rc: theirs)
 static ks_status copy_result(ks_engine* e, ks_status rc, void* dst, const void* src, size_t bytes) {
     if (rc != KS_OK) return rc;
     if (e->n) HIPCHK(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->st));
@@ -193,9 +193,7 @@ ks_status ks_requested_at(ks_engine* e, int64_t t, int64_t* out) {
     unsigned long long* state;  // [n][4], milli-units
     CARVE_SCRATCH(e, state = qs.take<unsigned long long>(4 * e->n));
     if (ks_status r = rebuild_state(e, nb, q_hi, t, milli_scale(e), 4, 1, state); r != KS_OK) return r;
-    HIPCHK(e, hipMemcpyAsync(out, state, sizeof(int64_t) * 4 * e->n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
+    return copy_result(e, KS_OK, out, state, sizeof(int64_t) * 4 * e->n);
 }
 
 // Filter mask and score of an already-bound pod as scheduleOne saw them: the evaluator of
@@ -293,9 +291,7 @@ ks_status ks_node_peaks(ks_engine* e, int64_t t_lo, int64_t t_hi, int64_t* out) 
     HIPCHK(e, ks::launch_node_peaks(e->d_blk.p, nb, q_hi, t_lo, (int32_t)n, e->b_node.p, e->b_status.p, e->t0.p,
                                     e->dur.p, e->pods.p, milli_scale(e), l.cnt, l.off, l.cur, l.list, (int32_t)cap, peaks,
                                     e->st));
-    HIPCHK(e, hipMemcpyAsync(out, peaks, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
+    return copy_result(e, KS_OK, out, peaks, sizeof(int64_t) * 4 * n);
 }
 
 // ---- headroom queries (ks_query.hip) -----------------------------------------------------------
@@ -401,9 +397,7 @@ ks_status ks_headroom_series(ks_engine* e, int64_t t_lo, int64_t t_hi, int32_t k
                                          e->cfg.filters, milli_scale(e), shapes, k, e->b_node.p, e->b_status.p,
                                          e->t0.p, e->dur.p, e->pods.p, l.cnt, l.off, l.cur, l.list, (int32_t)cap, diff,
                                          res, e->st));
-    HIPCHK(e, hipMemcpyAsync(out, res, sizeof(int64_t) * C2 * T, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return KS_OK;
+    return copy_result(e, KS_OK, out, res, sizeof(int64_t) * C2 * T);
 }
 
 // ---- placement preview (ks_place.hip) ----------------------------------------------------------
@@ -429,6 +423,41 @@ static ks_status upload_shapes(ks_engine* e, const ks::PlaceBufs& b, std::vector
     std::memcpy(h_up.data(), shapes, sizeof(ks::PodRec) * ns);
     std::memcpy(h_up.data() + kShapeWords, so, sizeof(int32_t) * k);
     HIPCHK(e, hipMemcpyAsync((void*)b.shapes, h_up.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, e->st));
+    return KS_OK;
+}
+
+// k pods' shapes, checked: so[j] = shape_of[j], or j without shape_of (then k = n_shapes)
+static ks_status pod_shapes(ks_engine* e, const char* what, int32_t k, const int32_t* shape_of, int32_t n_shapes,
+                            std::vector<int32_t>* so) {
+    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "%s: %d pods outside [1, %d]", what, (int)k, KS_PLACE_MAX_PODS);
+    if (!shape_of && k != n_shapes)
+        return fail(e, KS_EINVAL, "%s: %d pods without shape_of need %d shapes, not %d", what, (int)k, (int)k, (int)n_shapes);
+    so->resize(k);
+    for (int32_t j = 0; j < k; j++) {
+        const int32_t sh = (*so)[j] = shape_of ? shape_of[j] : j;
+        if (sh < 0 || sh >= n_shapes)
+            return fail(e, KS_EINVAL, "%s: pod %d has shape %d outside [0, %d)", what, (int)j, (int)sh, (int)n_shapes);
+    }
+    return KS_OK;
+}
+
+// the call's units: device units when `whole` (e->h_shapes are divided into them), else milli-units
+static ks::QScale call_units(ks_engine* e, bool whole, const ks::QScale& milli) {
+    if (whole)
+        for (ks::PodRec& r : e->h_shapes)
+            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
+    return whole ? kDeviceUnits : milli;
+}
+// `active` for the lists of all ns shapes; info[1..3] by a pod's status: bound Ok, bound OverCapacity, not found
+static uint64_t all_shapes(int32_t ns) { return ns >= 64 ? ~0ull : (1ull << ns) - 1ull; }
+static void tally(int64_t* info, int32_t status) { info[status == KS_POD_OK ? 1 : status == KS_POD_OVER_CAPACITY ? 2 : 3]++; }
+// a preview's last step: after_out (null: none) is the scratch state times sc as [n][4] rows; the stream's end
+static ks_status finish_after(ks_engine* e, const ks::PlaceBufs& b, const ks::QScale& sc, long long* after, int64_t* after_out) {
+    if (after_out) {
+        HIPCHK(e, ks::launch_place_after(b.state, b.n_pad, (int32_t)e->n, sc, after, e->st));
+        HIPCHK(e, hipMemcpyAsync(after_out, after, sizeof(int64_t) * 4 * e->n, hipMemcpyDeviceToHost, e->st));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
     return KS_OK;
 }
 
@@ -462,15 +491,8 @@ ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* 
     if (!e || !req || !keymask || !tol || !sel || !out) return KS_EINVAL;
     if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
     if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "place"); r != KS_OK) return r;
-    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "place: %d pods outside [1, %d]", (int)k, KS_PLACE_MAX_PODS);
-    if (!shape_of && k != n_shapes)
-        return fail(e, KS_EINVAL, "place: %d pods without shape_of need %d shapes, not %d", (int)k, (int)k, (int)n_shapes);
-    std::vector<int32_t> so(k);
-    for (int32_t j = 0; j < k; j++) {
-        so[j] = shape_of ? shape_of[j] : j;
-        if (so[j] < 0 || so[j] >= n_shapes)
-            return fail(e, KS_EINVAL, "place: pod %d has shape %d outside [0, %d)", (int)j, (int)so[j], (int)n_shapes);
-    }
+    std::vector<int32_t> so;
+    if (ks_status r = pod_shapes(e, "place", k, shape_of, n_shapes, &so); r != KS_OK) return r;
     if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
     int64_t info[KS_PLACE_INFO] = {0, 0, 0, 0};
     if (e->n == 0) {
@@ -489,10 +511,7 @@ ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* 
     // whole-unit requests: the call runs in device units (same placements, 64-bit BalancedAllocation)
     const ks::QScale milli = milli_scale(e);
     const bool whole = ks::place_whole_units(e->h_shapes.data(), n_shapes, milli);
-    const ks::QScale sc = whole ? kDeviceUnits : milli;
-    if (whole)
-        for (ks::PodRec& r : e->h_shapes)
-            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
+    const ks::QScale sc = call_units(e, whole, milli);
     if (ks_status r = rebuild_state(e, nb, q_hi, t, sc, 1, np, (unsigned long long*)b.state); r != KS_OK) return r;
     std::vector<unsigned long long> h_up;
     if (ks_status r = upload_shapes(e, b, h_up, e->h_shapes.data(), n_shapes, so.data(), k); r != KS_OK) return r;
@@ -503,13 +522,9 @@ ks_status ks_place_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* 
     constexpr int64_t PW = sizeof(ks::Placement) / sizeof(unsigned long long);
     std::vector<unsigned long long> h_down(2 + PW * k, 0ull);
     HIPCHK(e, hipMemcpyAsync(h_down.data(), b.rb, sizeof(unsigned long long) * h_down.size(), hipMemcpyDeviceToHost, e->st));
-    if (after_out) {
-        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, whole ? milli : kDeviceUnits, s.after, e->st));
-        HIPCHK(e, hipMemcpyAsync(after_out, s.after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
-    }
-    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (ks_status r = finish_after(e, b, whole ? milli : kDeviceUnits, s.after, after_out); r != KS_OK) return r;
     std::memcpy(out, h_down.data() + 2, sizeof(ks_placement) * k);
-    for (int32_t j = 0; j < k; j++) info[out[j].status == KS_POD_OK ? 1 : out[j].status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
+    for (int32_t j = 0; j < k; j++) tally(info, out[j].status);
     if (info_out) std::copy(info, info + KS_PLACE_INFO, info_out);
     return KS_OK;
 }
@@ -642,16 +657,12 @@ ks_status ks_drain_at(ks_engine* e, int64_t t, int32_t n_drain, const int32_t* n
         HIPCHK(e, ks::launch_drain_pack(d.ev_pod, d.ev_from, s.b.out, n_ev, s.evict, e->st));
         HIPCHK(e, hipMemcpyAsync(h_ev.data(), s.evict, sizeof(ks::Eviction) * n_ev, hipMemcpyDeviceToHost, e->st));
     }
-    if (after_out) {
-        HIPCHK(e, ks::launch_place_after(b.state, np, (int32_t)n, milli_scale(e), s.after, e->st));
-        HIPCHK(e, hipMemcpyAsync(after_out, s.after, sizeof(int64_t) * 4 * n, hipMemcpyDeviceToHost, e->st));
-    }
-    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (ks_status r = finish_after(e, b, milli_scale(e), s.after, after_out); r != KS_OK) return r;
     std::vector<uint32_t> seen(CW, 0u);
     int64_t busy = 0;
     for (int64_t i = 0; i < n_ev; i++) {
         const ks::Eviction& v = h_ev[i];
-        info[v.status == KS_POD_OK ? 1 : v.status == KS_POD_OVER_CAPACITY ? 2 : 3]++;
+        tally(info, v.status);
         if ((uint32_t)v.from < (uint32_t)n && !(seen[v.from >> 5] >> (v.from & 31) & 1u)) {
             seen[v.from >> 5] |= 1u << (v.from & 31);
             busy++;
@@ -770,8 +781,7 @@ ks_status ks_removable_at(ks_engine* e, int64_t t, int32_t m, const int32_t* nod
             for (size_t g = 0; g < segs.size(); g++) {
                 const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n, 0, segs[g].ns, (int32_t)nblk};
                 b.shapes = s.r.seg_shapes + g * KS_PLACE_MAX_SHAPES;
-                const uint64_t active = segs[g].ns >= 64 ? ~0ull : (1ull << segs[g].ns) - 1ull;
-                HIPCHK(e, ks::launch_place_lists(e->s, pc, b, active, e->st));
+                HIPCHK(e, ks::launch_place_lists(e->s, pc, b, all_shapes(segs[g].ns), e->st));
                 HIPCHK(e, ks::launch_removable_resolve(e->s, pc, b, s.r, b.shapes, segs[g].cand0, segs[g].n_cand, e->st));
             }
             std::vector<ks::Removal> got(n_cand);
@@ -864,15 +874,8 @@ ks_status ks_scale_up_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_
     if (!e || !req || !keymask || !tol || !sel || !options || !out) return KS_EINVAL;
     if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
     if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "scale_up"); r != KS_OK) return r;
-    if (k < 1 || k > KS_PLACE_MAX_PODS) return fail(e, KS_EINVAL, "scale_up: %d pods outside [1, %d]", (int)k, KS_PLACE_MAX_PODS);
-    if (!shape_of && k != n_shapes)
-        return fail(e, KS_EINVAL, "scale_up: %d pods without shape_of need %d shapes, not %d", (int)k, (int)k, (int)n_shapes);
-    std::vector<int32_t> so(k);
-    for (int32_t j = 0; j < k; j++) {
-        so[j] = shape_of ? shape_of[j] : j;
-        if (so[j] < 0 || so[j] >= n_shapes)
-            return fail(e, KS_EINVAL, "scale_up: pod %d has shape %d outside [0, %d)", (int)j, (int)so[j], (int)n_shapes);
-    }
+    std::vector<int32_t> so;
+    if (ks_status r = pod_shapes(e, "scale_up", k, shape_of, n_shapes, &so); r != KS_OK) return r;
     if (n_options < 1 || n_options > KS_SCALEUP_MAX_OPTIONS)
         return fail(e, KS_EINVAL, "scale_up: %d options outside [1, %d]", (int)n_options, KS_SCALEUP_MAX_OPTIONS);
     int64_t max_ext = 0;
@@ -894,10 +897,7 @@ ks_status ks_scale_up_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_
     static_assert(sizeof(ks_scale_option) % sizeof(int64_t) == 0, "alloc stride in words");
     const bool whole = ks::scaleup_whole_units(e->h_shapes.data(), n_shapes, options[0].alloc, n_options,
                                                sizeof(ks_scale_option) / sizeof(int64_t), milli);
-    const ks::QScale sc = whole ? kDeviceUnits : milli;
-    if (whole)
-        for (ks::PodRec& r : e->h_shapes)
-            for (int c = 0; c < 3; c++) r.req[c] /= milli.f[c];
+    const ks::QScale sc = call_units(e, whole, milli);
     std::vector<ks::ScaleOption> h_opts(n_options);
     for (int32_t g = 0; g < n_options; g++)
         h_opts[g] = ks::ScaleOption{ks::scaleup_template(options[g].alloc, options[g].taint, options[g].label,
@@ -919,8 +919,7 @@ ks_status ks_scale_up_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_
         if (ks_status r = upload_shapes(e, s.b, h_up, e->h_shapes.data(), n_shapes, so.data(), k); r != KS_OK) return r;
         HIPCHK(e, hipMemcpyAsync((void*)s.sb.opts, h_opts.data(), sizeof(ks::ScaleOption) * n_options, hipMemcpyHostToDevice, e->st));
         const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, k, n_shapes, (int32_t)nblk};
-        const uint64_t active = n_shapes >= 64 ? ~0ull : (1ull << n_shapes) - 1ull;
-        HIPCHK(e, ks::launch_place_lists(e->s, pc, s.b, active, e->st));
+        HIPCHK(e, ks::launch_place_lists(e->s, pc, s.b, all_shapes(n_shapes), e->st));
         HIPCHK(e, ks::launch_scaleup_resolve(e->s, pc, s.b, s.sb, n_options, e->st));
         HIPCHK(e, hipMemcpyAsync(h_out.data(), s.sb.out, sizeof(ks::ScaleResult) * n_options, hipMemcpyDeviceToHost, e->st));
         if (rows_out)

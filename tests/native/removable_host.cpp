@@ -2,77 +2,29 @@
 // removable_entries_on, removable_segment and the placement functions; ks_carve.h: carve_removable),
 // for CPU tests only.
 //   ks_host_removable          a serial restatement of removable_resolve_kernel (ks_removable.hip) for
-//                              one candidate: the shapes' top-L lists and candidate counts of the base
-//                              state with no cordon, the candidate's own entries flagged from the
-//                              start, its counts corrected, its pods decided from that one set of lists;
+//                              one candidate, on place_serial.h's list builder and pod loop: the lists
+//                              and counts of the base state with no cordon, the candidate's own entries
+//                              flagged from the start, its counts corrected, its pods decided from that
+//                              one set of lists, a veto on the candidate itself;
 //   ks_host_removable_brute    the plain sequential argmax over the nodes other than the candidate;
 //   ks_host_removable_segments ks_removable_at's candidate-aligned segment walk;
 //   ks_host_removable_route    the split between the batched resolver and the single-drain path;
 //   ks_host_removable_carve    carve_removable run twice, as ks_removable_at does.
 // Not part of the product.
-#include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <vector>
 
 #include "../../kubernetes-simulator_amd/csrc/ks_carve.h"
+#include "place_serial.h"
 
-namespace {
+using namespace place_serial;
 
-constexpr int L = ks::kPlaceL;
-constexpr int kBlk = 256;
-
-struct Case {
-    int32_t n;
-    std::vector<ks::NodeV> node;
-    ks::Cfg c{};
-    std::vector<ks::PodRec> shapes;
-};
-
-// cfg[6]: filter_feeds, filters, has_scorers, w_lr, w_ba, const_total
-Case make_case(int32_t n, const int64_t* alloc_dev, const int64_t* scale, const int64_t* state_m, const uint64_t* taint,
-               const uint64_t* label, const int32_t* cfg, int32_t n_shapes, const int64_t* req, const uint32_t* keymask,
-               const uint64_t* tol, const uint64_t* sel) {
-    Case s;
-    s.n = n;
-    const ks::QScale sc{{scale[0], scale[1], scale[2]}};
-    for (int32_t i = 0; i < n; i++) {
-        ks::NodeV v{};
-        v.ac = alloc_dev[i * 4 + 0]; v.am = alloc_dev[i * 4 + 1]; v.ag = alloc_dev[i * 4 + 2]; v.ap = alloc_dev[i * 4 + 3];
-        ks::place_scale_alloc(v, sc);
-        v.rc = state_m[i * 4 + 0]; v.rm = state_m[i * 4 + 1]; v.rg = state_m[i * 4 + 2]; v.nr = state_m[i * 4 + 3];
-        v.taint = taint[i]; v.label = label[i];
-        s.node.push_back(v);
-    }
-    s.c.n_nodes = n;
-    s.c.filter_feeds = cfg[0]; s.c.filters = (uint32_t)cfg[1]; s.c.has_scorers = cfg[2];
-    s.c.w_lr = cfg[3]; s.c.w_ba = cfg[4]; s.c.const_total = cfg[5];
-    for (int32_t j = 0; j < n_shapes; j++) {
-        ks::PodRec p{};
-        for (int c = 0; c < 3; c++)
-            if (keymask[j] >> c & 1) p.req[c] = req[j * 3 + c];
-        p.tol = tol[j]; p.sel = sel[j]; p.keymask = keymask[j];
-        s.shapes.push_back(p);
-    }
-    return s;
-}
-
-void count(const ks::Placement* out, int32_t k, int64_t* info) {
-    info[1] = info[2] = info[3] = 0;
-    for (int32_t i = 0; i < k; i++) info[out[i].status == ks::kPlaceOk ? 1 : out[i].status == ks::kPlaceOverCapacity ? 2 : 3]++;
-}
-
-}  // namespace
-
-#define CASE_ARGS                                                                                                  \
-    int32_t n, const int64_t *alloc_dev, const int64_t *scale, const int64_t *state_m, const uint64_t *taint,     \
-        const uint64_t *label, const int32_t *cfg, int32_t n_shapes, const int64_t *req, const uint32_t *keymask,   \
-        const uint64_t *tol, const uint64_t *sel, int32_t k, const int32_t *shape_of, int32_t cand
-#define CASE_PASS n, alloc_dev, scale, state_m, taint, label, cfg, n_shapes, req, keymask, tol, sel
+#define CASE_ARGS CLUSTER_ARGS, int32_t k, const int32_t *shape_of, int32_t cand
+#define CASE_PASS CLUSTER_PASS
 
 // scheduleOne as written, over the nodes other than the candidate (whose own state is never read)
 extern "C" int ks_host_removable_brute(CASE_ARGS, ks::Placement* out, int64_t* info) {
-    Case s = make_case(CASE_PASS);
+    Cluster s = make_cluster(CASE_PASS);
     for (int32_t i = 0; i < k; i++) {
         const ks::PodRec& p = s.shapes[shape_of[i]];
         uint64_t best = 0;
@@ -91,7 +43,7 @@ extern "C" int ks_host_removable_brute(CASE_ARGS, ks::Placement* out, int64_t* i
         const int32_t st = ks::place_bind(p, s.node[X]);
         out[i] = ks::Placement{(int32_t)X, st, (int64_t)(best >> 32) - 1, cnd};
     }
-    count(out, k, info);
+    tally(out, k, info);
     return 0;
 }
 
@@ -101,77 +53,27 @@ extern "C" int ks_host_removable_brute(CASE_ARGS, ks::Placement* out, int64_t* i
 // stats[0]: pods decided from a changed node, stats[1]: the most flagged entries of a list at the end,
 // stats[2]: lists the candidate's own node is in.
 extern "C" int ks_host_removable(CASE_ARGS, int32_t mode, ks::Placement* out, int64_t* info, int64_t* stats) {
-    Case s = make_case(CASE_PASS);
-    const int32_t nblk = (n + kBlk - 1) / kBlk;
-    // launch_place_lists: every shape, the base state, no cordon
-    std::vector<uint64_t> top((size_t)n_shapes * L, 0ull);
-    std::vector<uint32_t> flag(n_shapes, 0u);
-    std::vector<int> len(n_shapes, 0);
-    std::vector<int64_t> cc(n_shapes, 0);
+    const Cluster s = make_cluster(CASE_PASS);
+    // launch_place_lists: every shape, the base state, no cordon; then the candidate's two corrections
+    Lists l = build_lists(s, nullptr, node_key(s));
     stats[0] = stats[1] = stats[2] = 0;
     for (int32_t j = 0; j < n_shapes; j++) {
-        uint64_t t[L] = {};
-        for (int32_t b = 0; b < nblk; b++) {
-            std::vector<uint64_t> keys;
-            for (int32_t nd = b * kBlk; nd < std::min(n, (b + 1) * kBlk); nd++)
-                keys.push_back(ks::place_key(s.c, s.shapes[j], s.node[nd], (uint32_t)nd));
-            std::sort(keys.begin(), keys.end(), [](uint64_t a, uint64_t b2) { return a > b2; });
-            uint64_t lv[L] = {};
-            for (int e = 0; e < L && e < (int)keys.size(); e++) lv[e] = keys[e];
-            for (uint64_t key : keys) cc[j] += key != 0;
-            ks::topl_insert<L>(t, lv);
-        }
-        std::copy(t, t + L, top.begin() + (size_t)j * L);
-        len[j] = ks::place_list_len<L>(t);
-        // the candidate's two corrections
-        const uint32_t own = ks::removable_entries_on<L>(t, (uint32_t)cand);
+        const uint32_t own = ks::removable_entries_on<L>(&l.top[(size_t)j * L], (uint32_t)cand);
         stats[2] += own != 0;
-        if (mode != 1) flag[j] = own;
-        if (mode != 2) cc[j] -= ks::place_is_cand(s.c, s.shapes[j], s.node[cand]);
+        if (mode != 1) l.flag[j] = own;
+        if (mode != 2) l.cc[j] -= ks::place_is_cand(s.c, s.shapes[j], s.node[cand]);
     }
-    struct Chg { int32_t node; ks::NodeV v; };
+    struct Self : Hooks {
+        int32_t cand, mode;
+        int veto(uint32_t X) const { return (int32_t)X == cand && mode == 0 ? -2 : 0; }
+    } h{{}, cand, mode};
     std::vector<Chg> chg;
-    for (int32_t i = 0; i < k; i++) {
-        const int sh = shape_of[i];
-        const ks::PodRec& p = s.shapes[sh];
-        uint64_t D = 0;
-        int32_t d_idx = -1;
-        for (size_t c = 0; c < chg.size(); c++) {
-            const uint64_t key = ks::place_key(s.c, p, chg[c].v, (uint32_t)chg[c].node);
-            if (key > D) { D = key; d_idx = (int32_t)c; }
-        }
-        const uint64_t* list = &top[(size_t)sh * L];
-        const int eS = ks::place_first_unchanged<L>(len[sh], flag[sh]);
-        const uint64_t S = eS < L ? list[eS] : 0ull;
-        uint64_t W;
-        const int dec = ks::place_decide(S, list[L - 1], D, &W);
-        if (dec == ks::kPlaceStop) return -1;
-        const int64_t cnd = cc[sh];
-        if (dec == ks::kPlaceNone) {
-            out[i] = ks::Placement{-1, ks::kPlaceNotFound, -1, cnd};
-            continue;
-        }
-        const uint32_t X = ks::place_key_node(W);
-        if ((int32_t)X == cand && mode == 0) return -2;
-        int32_t idx;
-        if (W == D) {
-            idx = d_idx;
-            stats[0]++;
-        } else {
-            idx = (int32_t)chg.size();
-            chg.push_back(Chg{(int32_t)X, s.node[X]});
-            for (int32_t j = 0; j < n_shapes; j++) flag[j] |= ks::removable_entries_on<L>(&top[(size_t)j * L], X);
-        }
-        const ks::NodeV before = chg[idx].v;
-        ks::NodeV aft = before;
-        const int32_t st = ks::place_bind(p, aft);
-        if (st == ks::kPlaceOk)
-            for (int32_t j = 0; j < n_shapes; j++) cc[j] += ks::place_cand_delta(s.c, s.shapes[j], before, aft);
-        out[i] = ks::Placement{(int32_t)X, st, (int64_t)(W >> 32) - 1, cnd};
-        if (st == ks::kPlaceOk) chg[idx].v = aft;
-    }
-    for (int32_t j = 0; j < n_shapes; j++) stats[1] = std::max<int64_t>(stats[1], __builtin_popcount(flag[j]));
-    count(out, k, info);
+    const Run r = decide_pods(s, l, shape_of, 0, k, chg, h, out);
+    stats[0] = r.from_changed;
+    if (r.stopped) return -1;
+    if (r.veto) return r.veto;
+    for (int32_t j = 0; j < n_shapes; j++) stats[1] = std::max<int64_t>(stats[1], __builtin_popcount(l.flag[j]));
+    tally(out, k, info);
     return 0;
 }
 

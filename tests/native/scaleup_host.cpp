@@ -1,80 +1,32 @@
 // Host build of the scale-up preview's helpers (ks_device.h: scaleup_template, scaleup_whole_units,
 // scaleup_fresh_key, scaleup_count_start, scaleup_takes_fresh, with the placement preview's
-// place_key / place_first_unchanged / place_decide / place_bind / place_cand_delta / topl_insert), for
-// CPU tests only.  ks_host_scaleup is a serial restatement of scaleup_resolve_kernel's pod loop for one
-// option: the snapshot lists and candidate counts of the n real nodes, the changed set, the fresh
-// appended node n + u standing for every unchanged one, no commit, a stop where the kernel stops.
-// ks_host_scaleup_brute is the plain sequential argmax over the n + max_nodes nodes of the extended
-// cluster it must equal.  ks_host_scaleup_carve checks carve_scale_up's layout (ks_carve.h).  Not
-// part of the product.
-#include <algorithm>
+// functions), for CPU tests only.  ks_host_scaleup is a serial restatement of
+// resolve_kernel<true>'s pod loop (ks_place.hip) for one option, on place_serial.h's list builder
+// and pod loop: the snapshot lists and candidate counts of the n real nodes, the count start, the fresh appended
+// node n + u standing for every unchanged one as the loop's extra candidate, no commit, a stop where
+// the kernel stops.  ks_host_scaleup_brute is the plain sequential argmax over the n + max_nodes
+// nodes of the extended cluster it must equal.  ks_host_scaleup_carve checks carve_scale_up's layout
+// (ks_carve.h).  Not part of the product.
 #include <cstdio>
 #include <cstring>
-#include <vector>
 
 #include "../../kubernetes-simulator_amd/csrc/ks_carve.h"
+#include "place_serial.h"
 
-namespace {
+using namespace place_serial;
 
-constexpr int L = ks::kPlaceL;
-constexpr int kBlk = 256;
+// tmpl[7]: alloc[4] in milli-units, taint, label, max_nodes
+#define CASE_ARGS CLUSTER_ARGS, int32_t k, const int32_t *shape_of, const int64_t *tmpl
+#define CASE_PASS CLUSTER_PASS
 
-struct Case {
-    int32_t n;
-    std::vector<ks::NodeV> node;  // milli-units
-    ks::Cfg c{};
-    std::vector<ks::PodRec> shapes;
-    int32_t k;
-    const int32_t* shape_of;
-    ks::NodeV tmpl{};
-    int32_t max_nodes;
-};
-
-// cfg[6]: filter_feeds, filters, has_scorers, w_lr, w_ba, const_total; tmpl[7]: alloc[4] in
-// milli-units, taint, label, max_nodes
-Case make_case(int32_t n, const int64_t* alloc_dev, const int64_t* scale, const int64_t* state_m, const uint64_t* taint,
-               const uint64_t* label, const int32_t* cfg, int32_t n_shapes, const int64_t* req, const uint32_t* keymask,
-               const uint64_t* tol, const uint64_t* sel, int32_t k, const int32_t* shape_of, const int64_t* tmpl) {
-    Case s;
-    s.n = n;
-    const ks::QScale sc{{scale[0], scale[1], scale[2]}};
-    for (int32_t i = 0; i < n; i++) {
-        ks::NodeV v{};
-        v.ac = alloc_dev[i * 4 + 0]; v.am = alloc_dev[i * 4 + 1]; v.ag = alloc_dev[i * 4 + 2]; v.ap = alloc_dev[i * 4 + 3];
-        ks::place_scale_alloc(v, sc);
-        v.rc = state_m[i * 4 + 0]; v.rm = state_m[i * 4 + 1]; v.rg = state_m[i * 4 + 2]; v.nr = state_m[i * 4 + 3];
-        v.taint = taint[i]; v.label = label[i];
-        s.node.push_back(v);
-    }
-    s.c.n_nodes = n;
-    s.c.filter_feeds = cfg[0]; s.c.filters = (uint32_t)cfg[1]; s.c.has_scorers = cfg[2];
-    s.c.w_lr = cfg[3]; s.c.w_ba = cfg[4]; s.c.const_total = cfg[5];
-    for (int32_t j = 0; j < n_shapes; j++) {
-        ks::PodRec p{};
-        for (int c = 0; c < 3; c++)
-            if (keymask[j] >> c & 1) p.req[c] = req[j * 3 + c];
-        p.tol = tol[j]; p.sel = sel[j]; p.keymask = keymask[j];
-        s.shapes.push_back(p);
-    }
-    s.k = k;
-    s.shape_of = shape_of;
-    s.tmpl = ks::scaleup_template(tmpl, (uint64_t)tmpl[4], (uint64_t)tmpl[5], ks::QScale{{1, 1, 1}});  // milli-units
-    s.max_nodes = (int32_t)tmpl[6];
-    return s;
+static ks::NodeV make_tmpl(const int64_t* tmpl) {  // milli-units
+    return ks::scaleup_template(tmpl, (uint64_t)tmpl[4], (uint64_t)tmpl[5], ks::QScale{{1, 1, 1}});
 }
-
-}  // namespace
-
-#define CASE_ARGS                                                                                                  \
-    int32_t n, const int64_t *alloc_dev, const int64_t *scale, const int64_t *state_m, const uint64_t *taint,     \
-        const uint64_t *label, const int32_t *cfg, int32_t n_shapes, const int64_t *req, const uint32_t *keymask,   \
-        const uint64_t *tol, const uint64_t *sel, int32_t k, const int32_t *shape_of, const int64_t *tmpl
-#define CASE_PASS n, alloc_dev, scale, state_m, taint, label, cfg, n_shapes, req, keymask, tol, sel, k, shape_of, tmpl
 
 // scheduleOne as written, on the extended cluster
 extern "C" int ks_host_scaleup_brute(CASE_ARGS, ks::Placement* out) {
-    Case s = make_case(CASE_PASS);
-    for (int32_t a = 0; a < s.max_nodes; a++) s.node.push_back(s.tmpl);
+    Cluster s = make_cluster(CASE_PASS);
+    for (int32_t a = 0; a < (int32_t)tmpl[6]; a++) s.node.push_back(make_tmpl(tmpl));
     const int32_t n_ext = (int32_t)s.node.size();
     for (int32_t i = 0; i < k; i++) {
         const ks::PodRec& p = s.shapes[shape_of[i]];
@@ -101,98 +53,43 @@ extern "C" int ks_host_scaleup_brute(CASE_ARGS, ks::Placement* out) {
 // node, stats[1]: pods won by a changed node (real or appended), stats[2]: the most flagged entries
 // a pod found in its list, stats[3]: the changed set's final size; res: ks_scale_result's eight words.
 extern "C" int ks_host_scaleup(CASE_ARGS, int32_t ablate, ks::Placement* out, int32_t* res, int64_t* stats) {
-    Case s = make_case(CASE_PASS);
-    const int32_t nblk = (n + kBlk - 1) / kBlk;
-    // ---- the shared lists and counts: the n real nodes on the base state ----
-    std::vector<uint64_t> top((size_t)n_shapes * L, 0ull);
-    std::vector<uint32_t> flag(n_shapes, 0u);
-    std::vector<int> len(n_shapes, 0);
-    std::vector<long long> cc(n_shapes, 0);
-    for (int32_t j = 0; j < n_shapes; j++) {
-        uint64_t t[L] = {};
-        long long base = 0;
-        for (int32_t b = 0; b < nblk; b++) {
-            std::vector<uint64_t> keys;
-            for (int32_t nd = b * kBlk; nd < std::min(n, (b + 1) * kBlk); nd++)
-                keys.push_back(ks::place_key(s.c, s.shapes[j], s.node[nd], (uint32_t)nd));
-            std::sort(keys.begin(), keys.end(), [](uint64_t a, uint64_t b2) { return a > b2; });
-            uint64_t lv[L] = {};
-            for (int e = 0; e < L && e < (int)keys.size(); e++) lv[e] = keys[e];
-            for (uint64_t key : keys) base += key != 0;
-            ks::topl_insert<L>(t, lv);
-        }
-        std::copy(t, t + L, top.begin() + (size_t)j * L);
-        len[j] = ks::place_list_len<L>(t);
-        cc[j] = (ablate & 2) ? base : ks::scaleup_count_start(s.c, s.shapes[j], s.tmpl, base, s.max_nodes);
-    }
-    // ---- the pod loop ----
-    struct Chg { int32_t node; ks::NodeV v; };
-    std::vector<Chg> chg;
-    int32_t u = 0, i = 0;
-    ks::ScaleResult r{0, 0, 0, 0, 0, -1, ks::kScaleBatched, 0};
+    const Cluster s = make_cluster(CASE_PASS);
     stats[0] = stats[1] = stats[2] = stats[3] = 0;
-    for (; i < k; i++) {
-        const int sh = shape_of[i];
-        const ks::PodRec& p = s.shapes[sh];
-        uint64_t D = 0;
-        int32_t d_idx = -1;
-        for (size_t c = 0; c < chg.size(); c++) {
-            const uint64_t key = ks::place_key(s.c, p, chg[c].v, (uint32_t)chg[c].node);
-            if (key > D) { D = key; d_idx = (int32_t)c; }
+    // the fresh node n + u as the loop's extra candidate (thread nchg of the kernel)
+    struct Fresh : Hooks {
+        const Cluster& s;
+        ks::NodeV tmpl;
+        int32_t max_nodes, u;
+        bool off;
+        uint64_t extra_key(const ks::PodRec& p) const {
+            return off ? 0ull : ks::scaleup_fresh_key(s.c, p, tmpl, s.n, u, max_nodes);
         }
-        const uint64_t F = (ablate & 1) ? 0ull : ks::scaleup_fresh_key(s.c, p, s.tmpl, n, u, s.max_nodes);
-        if (F > D) { D = F; d_idx = (int32_t)chg.size(); }  // (slot nchg: the fresh node's, if it wins)
-        const uint64_t* list = &top[(size_t)sh * L];
-        stats[2] = std::max<int64_t>(stats[2], __builtin_popcount(flag[sh]));
-        const int eS = ks::place_first_unchanged<L>(len[sh], flag[sh]);
-        const uint64_t S = eS < L ? list[eS] : 0ull;
-        uint64_t W;
-        const int dec = ks::place_decide(S, list[L - 1], D, &W);
-        if (dec == ks::kPlaceStop) {
-            r.path = ks::kScaleStopped;
-            break;
+        bool extra_joins(uint32_t X, ks::NodeV* v) {
+            if (off || !ks::scaleup_takes_fresh(X, s.n, u, max_nodes)) return false;
+            *v = tmpl;
+            ++u;
+            return true;
         }
-        const int64_t cand = cc[sh];
-        if (dec == ks::kPlaceNone) {
-            out[i] = ks::Placement{-1, ks::kPlaceNotFound, -1, cand};
-            r.not_found++;
-            if (r.first_unplaced < 0) r.first_unplaced = i;
+    } h{{}, s, make_tmpl(tmpl), (int32_t)tmpl[6], 0, (ablate & 1) != 0};
+    // ---- the shared lists and counts: the n real nodes on the base state; the count start ----
+    Lists l = build_lists(s, nullptr, node_key(s));
+    if (!(ablate & 2))
+        for (int32_t j = 0; j < n_shapes; j++) l.cc[j] = ks::scaleup_count_start(s.c, s.shapes[j], h.tmpl, l.cc[j], h.max_nodes);
+    std::vector<Chg> chg;
+    const Run run = decide_pods(s, l, shape_of, 0, k, chg, h, out);
+    stats[0] = run.from_extra; stats[1] = run.from_changed; stats[2] = run.most_flagged;
+    if ((int64_t)chg.size() > ks::kPlaceMaxPods) return -2;
+    // ---- the option's summary, from its rows and the final changed set ----
+    ks::ScaleResult r{0, 0, 0, 0, 0, -1, run.stopped ? ks::kScaleStopped : ks::kScaleBatched, 0};
+    for (int32_t i = 0; i < run.next; i++) {
+        if (out[i].status == ks::kPlaceOk) {
+            r.ok++;
+            r.on_new += out[i].node >= n;
             continue;
         }
-        const uint32_t X = ks::place_key_node(W);
-        const bool from_d = W == D;
-        const bool fresh = from_d && !(ablate & 1) && ks::scaleup_takes_fresh(X, n, u, s.max_nodes);
-        int32_t idx;
-        if (from_d) {
-            idx = d_idx;
-            if (fresh) {
-                chg.push_back(Chg{(int32_t)X, s.tmpl});
-                ++u;
-                stats[0]++;
-            } else {
-                stats[1]++;
-            }
-        } else {
-            idx = (int32_t)chg.size();
-            chg.push_back(Chg{(int32_t)X, s.node[X]});
-            for (size_t e = 0; e < top.size(); e++)
-                if (top[e] && ks::place_key_node(top[e]) == X) flag[e / L] |= 1u << (e % L);
-        }
-        const ks::NodeV before = chg[idx].v;
-        ks::NodeV aft = before;
-        const int32_t st = ks::place_bind(p, aft);
-        if (st == ks::kPlaceOk) {
-            for (int32_t j = 0; j < n_shapes; j++) cc[j] += ks::place_cand_delta(s.c, s.shapes[j], before, aft);
-            chg[idx].v = aft;
-            r.ok++;
-            r.on_new += X >= (uint32_t)n;
-        } else {
-            r.over_capacity++;
-            if (r.first_unplaced < 0) r.first_unplaced = i;
-        }
-        out[i] = ks::Placement{(int32_t)X, st, (int64_t)(W >> 32) - 1, cand};
+        (out[i].status == ks::kPlaceOverCapacity ? r.over_capacity : r.not_found)++;
+        if (r.first_unplaced < 0) r.first_unplaced = i;
     }
-    if ((int64_t)chg.size() > ks::kPlaceMaxPods) return -2;
     // the prefix invariant, checked on the final changed set
     int32_t seen = 0;
     for (const Chg& c : chg)
@@ -201,10 +98,10 @@ extern "C" int ks_host_scaleup(CASE_ARGS, int32_t ablate, ks::Placement* out, in
             ++seen;
             r.nodes_used += c.v.nr > 0;
         }
-    if (seen != u) return -3;
+    if (seen != h.u) return -3;
     stats[3] = (int64_t)chg.size();
     std::memcpy(res, &r, sizeof(r));
-    return i;
+    return run.next;
 }
 
 // scaleup_whole_units on n_options templates of ks_scale_option's layout (7 words each)
