@@ -609,6 +609,88 @@ func (e *Engine) RemovableAt(t int64, nodes []int32, rows bool) (*Removals, erro
 	return r, status(e, rc)
 }
 
+// Consolidation outcomes (include/ks_engine.h, KS_CONSOLIDATE_*) and the words of
+// Consolidations.Info (KS_CONSOLIDATE_INFO).
+const (
+	ConsolidateBlocked     = 0
+	ConsolidateRemoved     = 1
+	ConsolidateDestination = 2
+	ConsolidateInfo        = 6
+)
+
+// Consolidation is one candidate's answer (ks_consolidation, 32 bytes): the pods running on it at
+// t, its outcome, the rows written for it (all of a removed candidate's pods, a blocked one's up to
+// and including the blocking pod, none of a destination's), the blocking pod's status, and the
+// index of its first row in Consolidations.Rows.
+type Consolidation struct {
+	Node, Evicted int32
+	Outcome, Rows int32
+	BlockStatus   int32
+	Pad           int32
+	FirstRow      int64
+}
+
+// Consolidations is the result of ConsolidateAt: one Consolidation per candidate in the caller's
+// order, Evicted the pods running on all candidates, Rows (when asked for) the Eviction rows
+// concatenated in that order, FIFO within a candidate, After (when asked for) [Nodes()][4] the
+// final private state, and Info = rounds of the device algorithm, removed, blocked, destinations,
+// candidates decided through the single path, pods moved.
+type Consolidations struct {
+	Nodes   []Consolidation
+	Evicted int64
+	Rows    []Eviction
+	After   []int64
+	Info    [ConsolidateInfo]int64
+}
+
+// ConsolidateAt says which of `nodes` a scale-down pass would remove at tick t <= Tick() when it
+// handles them in the given order on one private state (ks_consolidate_at): a candidate that
+// received a moved pod is a destination and nothing is tried; any other leaves k.nodes together
+// with the nodes removed before it (kubesim/kubesim.go:168-206 range over k.nodes) and its running
+// pods go in FIFO order through scheduleOne (kubesim.go:143-225) until one is not bound Ok; all Ok
+// (or no pod): removed, the placements stay; otherwise blocked, and everything is as it was before
+// the candidate.  nodes are distinct indices in [0, Nodes()).  No engine state changes.  With rows
+// it sizes the row buffer itself; more than DrainMaxPods pods on the candidates are ErrOutOfDomain.
+func (e *Engine) ConsolidateAt(t int64, nodes []int32, rows, after bool) (*Consolidations, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	if len(nodes) == 0 && e.n > 0 {
+		return nil, strongerrors.InvalidArgument(errors.New("consolidate: no nodes given"))
+	}
+	nd := nodes
+	if len(nd) == 0 {
+		nd = make([]int32, 1) // n = 0: the pointer must not be NULL, the count is 0
+	}
+	r := &Consolidations{Nodes: make([]Consolidation, len(nodes)+1)}
+	if after {
+		r.After = make([]int64, 4*e.n+1)
+	}
+	out := (*C.ks_consolidation)(unsafe.Pointer(&r.Nodes[0]))
+	info := (*C.int64_t)(unsafe.Pointer(&r.Info[0]))
+	m := C.int32_t(len(nodes))
+	var ev, k C.int64_t
+	var rc C.ks_status
+	if !rows {
+		rc = C.ks_consolidate_at(e.h, C.int64_t(t), m, i32p(nd), out, nil, 0, &ev, &k, i64p(r.After), info)
+	} else {
+		// a one-row buffer first: KS_ERANGE comes back with the count as soon as the gather has it
+		r.Rows = make([]Eviction, 1)
+		rc = C.ks_consolidate_at(e.h, C.int64_t(t), m, i32p(nd), out, (*C.ks_eviction)(unsafe.Pointer(&r.Rows[0])), 1, &ev, &k, i64p(r.After), info)
+		if rc == C.KS_ERANGE && ev > 1 && ev <= DrainMaxPods {
+			r.Rows = make([]Eviction, int(ev))
+			rc = C.ks_consolidate_at(e.h, C.int64_t(t), m, i32p(nd), out, (*C.ks_eviction)(unsafe.Pointer(&r.Rows[0])), ev, &ev, &k, i64p(r.After), info)
+		}
+		if rc == C.KS_OK {
+			r.Rows = r.Rows[:int(k)]
+		}
+	}
+	r.Evicted = int64(ev)
+	r.Nodes = r.Nodes[:len(nodes)]
+	if after {
+		r.After = r.After[:4*e.n]
+	}
+	return r, status(e, rc)
+}
+
 // Scale-up preview constants (include/ks_engine.h): the most options per ScaleUpAt call, the most
 // nodes an option may append, the words of ScaleUps.Info.
 const (

@@ -33,6 +33,8 @@
  *                                 (kubesim/kubesim.go:168-206 range over it): where they would go
  *   ks_removable_at ............. ks_drain_at's answer for each of m candidate nodes on its own:
  *                                 which of them could be taken out
+ *   ks_consolidate_at ........... the same candidates handled one after another, as a scale-down pass
+ *                                 does: a removal's placements stay, a failed attempt is rolled back
  *   ks_scale_up_at .............. ks_place_at's answer on the cluster plus up to max_nodes empty nodes
  *                                 of a node-group template, for each of G templates on its own
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
@@ -477,6 +479,57 @@ typedef struct {
 ks_status ks_removable_at(ks_engine* eng, int64_t t, int32_t m, const int32_t* nodes /* [m] */,
                           ks_removal* out /* [m] */, ks_eviction* rows_out /* [cap] or NULL */,
                           int64_t cap, int64_t* n_rows, int64_t* info_out /* [KS_REMOVABLE_INFO] or NULL */);
+
+/* Consolidation preview: which of m candidate nodes a scale-down pass would remove when it handles
+ * them one after another, at any past tick ("at tick t" as above).  No engine state changes.
+ *
+ * nodes[m] are distinct node indices in [0, n), 1 <= m <= n (with n = 0: m = 0).  The call keeps a
+ * private copy of ks_requested_at(t), a set R of removed nodes and a set V of destination nodes, both
+ * empty at the start, and handles the candidates in the caller's order.  For candidate c:
+ *   - c in V: KS_CONSOLIDATE_DESTINATION.  Nothing is tried, no rows are written, nothing changes.
+ *   - otherwise c leaves k.nodes together with R (kubesim/kubesim.go:168-206 range over k.nodes).  The
+ *     pods running on c at t — exactly those ks_drain_at would evict from c (Pod.IsRunning,
+ *     kubesim/pod/pod.go:67-69) — are handed in FIFO order to scheduleOne (kubesim/kubesim.go:143-225,
+ *     kubesim/node/node.go:36-60) on the private state with c's row emptied.  Filter mode, filters,
+ *     scorers, score, candidates and the lowest-index tie-break are ks_place_at's and ks_drain_at's;
+ *     candidates counts nodes outside R and c.  The attempt ends at the first pod whose status is not
+ *     KS_POD_OK; later pods of c are not tried.
+ *   - every pod bound Ok, or none runs on c: KS_CONSOLIDATE_REMOVED.  c joins R, its row stays zero,
+ *     the placements stay and every node that received a pod joins V.
+ *   - otherwise KS_CONSOLIDATE_BLOCKED: the private state, V and R are exactly what they were before
+ *     c; c stays in k.nodes with its pods and may still become a destination of a later candidate.
+ * A removed node is never in V and a node in V is never removed.
+ *
+ * out[j] answers nodes[j].  *n_evicted = the pods running on all candidates, the upper bound of the
+ * rows, always written.  If it exceeds KS_DRAIN_MAX_PODS, or rows_out is given and cap is smaller:
+ * KS_ERANGE and nothing else is written.  rows_out (may be NULL with cap = 0: summaries only; rows and
+ * first_row are filled all the same): ks_eviction rows concatenated in the caller's order, FIFO within
+ * a candidate — all of a removed candidate's pods, a blocked candidate's up to and including the
+ * blocking pod, none of a destination's.  *n_rows = the rows written.  after_out (may be NULL): [n][4]
+ * milli-units and running pods, the final private state: removed nodes' rows zero, plus every kept
+ * placement.  info_out (may be NULL): {rounds of the device algorithm, removed, blocked, destinations,
+ * candidates decided through the single path (more pods than one set of lists decides: KS_PLACE_L - 1,
+ * and no destination), pods moved = the rows of removed candidates}.
+ * KS_EINVAL: a NULL engine, nodes, out, n_evicted or n_rows (before the handle is read); rows_out NULL
+ * with cap > 0; cap < 0; a node out of range or listed twice; m out of range; t out of range; no nodes
+ * loaded.  It answers after an aborted run, on sharded engines and on scenario-group members, like
+ * ks_drain_at. */
+enum { KS_CONSOLIDATE_BLOCKED = 0, KS_CONSOLIDATE_REMOVED = 1, KS_CONSOLIDATE_DESTINATION = 2 };
+#define KS_CONSOLIDATE_INFO 6
+typedef struct {
+    int32_t node;          /* the candidate */
+    int32_t evicted;       /* pods running on it at t (also when nothing was tried) */
+    int32_t outcome;       /* KS_CONSOLIDATE_* */
+    int32_t rows;          /* rows written for it: evicted when removed; up to and including the
+                              blocking pod when blocked; 0 for a destination */
+    int32_t block_status;  /* blocked: the blocking pod's status (KS_POD_OVER_CAPACITY / KS_PLACE_NOT_FOUND); else 0 */
+    int32_t pad;
+    int64_t first_row;     /* index of its first row in rows_out */
+} ks_consolidation;        /* 32 bytes */
+ks_status ks_consolidate_at(ks_engine* eng, int64_t t, int32_t m, const int32_t* nodes /* [m] */,
+                            ks_consolidation* out /* [m] */, ks_eviction* rows_out /* [cap] or NULL */,
+                            int64_t cap, int64_t* n_evicted, int64_t* n_rows,
+                            int64_t* after_out /* [n][4] or NULL */, int64_t* info_out /* [KS_CONSOLIDATE_INFO] or NULL */);
 
 /* Scale-up preview: where k pending pods would be bound if up to max_nodes nodes of a node-group
  * template were added, at any past tick ("at tick t" as above), for n_options templates, each on its

@@ -3,8 +3,8 @@
 // A layout is written once, as a sequence of Carve::take() calls, and run twice: with a null base
 // the cursor only counts and `at` is the size to reserve; with the real base the same calls give
 // the pointers.  The reserved size and the ranges therefore cannot disagree.  The layouts of the
-// placement, drain and scale-up previews and of the removal scan live here too, so a stand-alone host program
-// can check them.
+// placement, drain, scale-up and consolidation previews and of the removal scan live here too, so a
+// stand-alone host program can check them.
 #pragma once
 #include <cstdint>
 
@@ -126,6 +126,37 @@ inline RemovableScratch carve_removable(Carve& qs, int64_t np, int64_t nblk, int
     s.r.cands = qs.take<ks::RemovalCand>(s.cand_cap);
     s.r.rows = qs.take<ks::Eviction>(n_ev);
     s.r.out = qs.take<ks::Removal>(s.cand_cap);
+    return s;
+}
+
+// ks_consolidate_at, once n_ev is known (the gather's int32 scratch is carve_drain_gather's): the
+// rounds' buffers on the chain's state (b.shape_of: a round's KS_PLACE_MAX_PODS; b.out: every row's
+// placement at its caller-ordered row, a round's at its first row), the gathered rows (into d), the
+// single path's second state copy and its cordon, the bitmaps of the removed nodes (cordon) and of
+// the destinations (received) [cw words each], the candidate table and the answers [m]
+struct ConsolidateScratch {
+    ks::PlaceBufs b;
+    int64_t* state2;  // [4][np]
+    uint32_t *cordon, *received, *cordon2;
+    ks::RemovalCand* cands;
+    ks::Consolidation* out;
+    long long* after;  // [n][4]
+};
+inline ConsolidateScratch carve_consolidate(Carve& qs, int64_t n, int64_t np, int64_t nblk, int64_t n_ev, int64_t m,
+                                            int64_t cw, ks::DrainBufs* d) {
+    ConsolidateScratch s{};
+    s.b = carve_place(qs, np, nblk, ks::kPlaceMaxPods, n_ev);
+    d->ev_pod = qs.take<long long>(n_ev);
+    d->ev_from = qs.take<int32_t>(n_ev);
+    d->ev_rec = qs.take<ks::PodRec>(n_ev, 2);
+    d->cap = n_ev;
+    s.state2 = qs.take<int64_t>(4 * np);
+    s.cordon = qs.take<uint32_t>(cw);
+    s.received = qs.take<uint32_t>(cw);
+    s.cordon2 = qs.take<uint32_t>(cw);
+    s.cands = qs.take<ks::RemovalCand>(m, 2);
+    s.out = qs.take<ks::Consolidation>(m);
+    s.after = qs.take<long long>(4 * n);
     return s;
 }
 

@@ -1822,4 +1822,124 @@ hipError_t launch_scaleup_resolve(const NodeSoA& s, const PlaceCfg& pc, const Pl
 hipError_t launch_scaleup_extend(const NodeSoA& s, int32_t n, const QScale& sc, const ScaleOption& opt, int64_t np_ext,
                                  int64_t* dst, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------
+// Consolidation preview (ks_consolidate_at, ks_consolidate.hip): m candidate nodes handled in the
+// caller's order as a chain of transactions on one private state.  R: the nodes removed so far; V:
+// the nodes that received a moved pod.  A candidate in V is a destination and nothing is tried; any
+// other candidate c leaves k.nodes together with R and its pods go to scheduleOne in FIFO order
+// until one is not bound Ok; all Ok (or no pod): c joins R, the placements stay, their nodes join V;
+// otherwise everything is as it was before c.
+//
+// Exactness of a round.  A round scans the committed scratch state with R as the cordon (the
+// argument above launch_place_round: the lists and the counts are those of the cluster without R)
+// and then walks candidates in order with one changed set, one set of flags and one set of running
+// counts.  Read "changed, removed in this round, or the open candidate" for "changed" in the
+// argument above place_decide: the resolver flags every list entry on the open candidate c before
+// c's first pod and corrects the counts by place_is_cand(shape, c's record) (the removal scan's
+// argument, above removable_route: c is never S, never a winner, never in the changed set, never in
+// D; c is in no changed set because a changed node is a destination and is not tried).  An
+// unflagged entry is a node no pod was placed on in this round, not removed and not c: it still has
+// its snapshot key, so place_decide's three cases hold verbatim over the nodes outside R and c.
+//   accept  c's flags and its count correction stay: for the rest of the round c is a removed
+//           node.  Its row of the scratch is zeroed and its cordon bit set for the next scan.
+//   block   the state must be exactly the state before c.  The attempt changed four things: the
+//           changed nodes' records (place_bind adds the masked requests and one pod on Ok and
+//           nothing else, so subtracting them per Ok pod restores a slot that existed before c;
+//           slots appended by the attempt lie at [nchg before c, nchg) and are dropped), the flag
+//           words, the running counts (both restored from the copies taken before c's own flags
+//           were set) and nchg.  A dropped slot's node is unchanged again and its entries are
+//           unflagged again: it has its snapshot key, as the argument needs.
+// A removed node is never in V (a destination is not tried) and a node in V is never removed, so
+// the round's commit — the changed nodes' records, the `received` bits, the removed nodes' zero rows
+// and cordon bits — never writes one node twice.
+//
+// Progress.  A round's first candidate finds fresh lists with nothing flagged but its own entries,
+// so its pod i (1-based) finds at most (i - 1) + 1 flagged entries: with at most kConsMaxPods =
+// L - 1 pods it is decided in that round (the removal scan's argument).  kPlaceStop inside a later
+// candidate rolls that candidate back and ends the round; it opens the next one.  A candidate with
+// more pods (consolidate_route) is answered by the host's single path when it is the next to be
+// decided: a copy of the scratch state, the placement rounds with the cordon R + c, adopted iff
+// every pod was bound Ok.  The segment walk closes before such a candidate, so it always heads a
+// round of its own; whether it is a destination is read from `received` first.
+// ---------------------------------------------------------------------------------------------
+constexpr int kConsMaxPods = kPlaceL - 1;  // pods of a candidate the rounds decide
+enum : int32_t { kConsBlocked = 0, kConsRemoved = 1, kConsDestination = 2 };  // KS_CONSOLIDATE_*
+enum : int { kConsRound = 0, kConsSingle = 1 };
+
+struct Consolidation {  // = ks_consolidation
+    int32_t node, evicted, outcome, rows, block_status, pad;
+    int64_t first_row;
+};
+static_assert(sizeof(Consolidation) == 32, "ks_consolidation layout");
+
+// who decides a candidate with `pods` running pods (when it is not a destination)
+__host__ __device__ __forceinline__ int consolidate_route(int64_t pods) {
+    return pods <= kConsMaxPods ? kConsRound : kConsSingle;
+}
+
+// The round that starts at candidate `start` of cands[m] (rows of recs, each candidate's
+// contiguous, in the caller's order): it closes before the candidate that would bring its
+// (kPlaceMaxShapes + 1)-th distinct shape or its (kPlaceMaxPods + 1)-th pod, and before a candidate
+// of the single path.  Returns its end (exclusive; > start when cands[start] is of the round path: such
+// a candidate has at most kConsMaxPods pods and shapes), its distinct shapes in shapes[0, *n_shapes)
+// in order of first appearance (masked requests, flags 0), shape_of[row - cands[start].first] for
+// its rows and their number in *n_pods.
+inline int64_t consolidate_segment(const PodRec* recs, const RemovalCand* cands, int64_t m, int64_t start,
+                                   PodRec* shapes, int32_t* n_shapes, int32_t* shape_of, int32_t* n_pods) {
+    int32_t ns = 0, np = 0;
+    int64_t a = start;
+    const int64_t row0 = start < m ? cands[start].first : 0;
+    for (; a < m; ++a) {
+        if (consolidate_route(cands[a].count) != kConsRound || np + cands[a].count > kPlaceMaxPods) break;
+        const int32_t before = ns;
+        bool fits_in = true;
+        for (int64_t row = cands[a].first; row < cands[a].first + cands[a].count; ++row) {
+            int32_t j = 0;
+            while (j < ns && !drain_same_shape(shapes[j], recs[row])) ++j;
+            if (j == ns) {
+                if (ns == kPlaceMaxShapes) {
+                    fits_in = false;
+                    break;
+                }
+                PodRec r{};
+                for (int c = 0; c < 3; ++c) r.req[c] = (recs[row].keymask >> c & 1) ? recs[row].req[c] : 0;
+                r.tol = recs[row].tol; r.sel = recs[row].sel; r.keymask = recs[row].keymask;
+                shapes[ns++] = r;
+            }
+            shape_of[row - row0] = j;
+        }
+        if (!fits_in) {
+            ns = before;  // (the next round numbers this candidate's rows again)
+            break;
+        }
+        np += cands[a].count;
+    }
+    *n_shapes = ns;
+    *n_pods = np;
+    return a;
+}
+
+// One round on the device: cands [m], every candidate in the caller's order (rows [first, first +
+// count) of the caller-ordered rows); the round's candidates [c0, c1) and row0 = cands[c0].first;
+// cordon / received [ceil(n / 32)], the bitmaps of R and V; out [m], the answers.
+struct ConsRound {
+    const RemovalCand* cands;
+    int32_t c0, c1;
+    int64_t row0;
+    uint32_t* cordon;
+    uint32_t* received;
+    Consolidation* out;
+};
+// scan + merge of pc.n_shapes shapes on b.state with cr.cordon (none when the round has no pod:
+// pc.k = pc.n_shapes = 0), then the resolver: pods [0, pc.k) are rows [row0, row0 + pc.k), their
+// placements go to b.out[0, pc.k), b.rb gets {the next candidate, 1 if none was decided, the changed
+// nodes committed, the pods before the next candidate}
+hipError_t launch_consolidate_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, const ConsRound& cr,
+                                    hipStream_t st);
+// the single path: node leaves (its cordon bit set, its row of state [4][n_pad] zeroed) ...
+hipError_t launch_consolidate_take(uint32_t* cordon, int64_t* state, int64_t n_pad, int32_t n_nodes, int32_t node,
+                                   hipStream_t st);
+// ... and, once adopted, the nodes of its k placements join `received`
+hipError_t launch_consolidate_mark(const Placement* placed, int64_t k, int32_t n_nodes, uint32_t* received, hipStream_t st);
+
 }  // namespace ks

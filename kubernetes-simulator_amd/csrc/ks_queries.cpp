@@ -825,6 +825,211 @@ ks_status ks_removable_at(ks_engine* e, int64_t t, int32_t m, const int32_t* nod
     return KS_OK;
 }
 
+// ---- consolidation preview (ks_consolidate.hip) --------------------------------------------------
+// The removal scan's candidates as a chain.  One gather with the candidates as the node set, rows
+// grouped by candidate as in ks_removable_at; then the candidates in order: a round (scan + merge with
+// the removed nodes cordoned, then the resolver's transactions: ks::launch_consolidate_round) takes
+// candidates up to KS_PLACE_MAX_SHAPES distinct shapes and KS_PLACE_MAX_PODS pods
+// (ks::consolidate_segment) and reports where it ended in 16 bytes; a candidate with more pods than
+// one set of lists decides (ks::consolidate_route) heads no round: the host asks `received` whether
+// it is a destination and otherwise runs ks_drain_at's rounds for it on a copy of the state, which is
+// adopted iff every pod was bound Ok.  Answers, placements and pod indices are read back once, at
+// the end, and the rows are packed in the caller's order.
+static_assert(KS_CONSOLIDATE_INFO == 6 && sizeof(ks_consolidation) == sizeof(ks::Consolidation) &&
+              offsetof(ks_consolidation, node) == offsetof(ks::Consolidation, node) &&
+              offsetof(ks_consolidation, evicted) == offsetof(ks::Consolidation, evicted) &&
+              offsetof(ks_consolidation, outcome) == offsetof(ks::Consolidation, outcome) &&
+              offsetof(ks_consolidation, rows) == offsetof(ks::Consolidation, rows) &&
+              offsetof(ks_consolidation, block_status) == offsetof(ks::Consolidation, block_status) &&
+              offsetof(ks_consolidation, first_row) == offsetof(ks::Consolidation, first_row) &&
+              KS_CONSOLIDATE_BLOCKED == ks::kConsBlocked && KS_CONSOLIDATE_REMOVED == ks::kConsRemoved &&
+              KS_CONSOLIDATE_DESTINATION == ks::kConsDestination,
+              "ks_consolidate_at constants and record");
+
+ks_status ks_consolidate_at(ks_engine* e, int64_t t, int32_t m, const int32_t* nodes, ks_consolidation* out,
+                            ks_eviction* rows_out, int64_t cap, int64_t* n_evicted, int64_t* n_rows, int64_t* after_out,
+                            int64_t* info_out) {
+    if (!e || !nodes || !out || !n_evicted || !n_rows || cap < 0 || (cap > 0 && !rows_out)) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    std::vector<uint32_t> h_set;
+    if (ks_status r = node_set(e, "consolidate", m, nodes, &h_set); r != KS_OK) return r;
+    const int64_t CW = (int64_t)h_set.size();
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    int64_t info[KS_CONSOLIDATE_INFO] = {0, 0, 0, 0, 0, 0};
+    if (n == 0) {
+        *n_evicted = 0;
+        *n_rows = 0;
+        if (info_out) std::copy(info, info + KS_CONSOLIDATE_INFO, info_out);
+        return KS_OK;
+    }
+    // ---- one gather for every candidate ----
+    DrainCount gc;
+    if (ks_status r = drain_count(e, "consolidate", t, h_set, &gc); r != KS_OK) return r;
+    const int64_t n_ev = gc.n_ev;
+    *n_evicted = n_ev;
+    if (n_ev > KS_DRAIN_MAX_PODS || (rows_out && n_ev > cap))
+        return fail(e, KS_ERANGE, "consolidate: %lld evicted pods, room for %lld (at most %d per call)", (long long)n_ev,
+                    (long long)(rows_out ? std::min<int64_t>(cap, KS_DRAIN_MAX_PODS) : (int64_t)KS_DRAIN_MAX_PODS),
+                    KS_DRAIN_MAX_PODS);
+    ks::DrainBufs d = gc.g.d;
+    ConsolidateScratch s;
+    CARVE_SCRATCH(e, s = carve_consolidate(qs, n, np, nblk, n_ev, m, CW, &d));
+    ks::PlaceBufs b = s.b;
+    b.cnt = gc.g.cnt;
+    if (ks_status r = rebuild_state(e, gc.nb, gc.q_hi, t, kDeviceUnits, 1, np, (unsigned long long*)b.state); r != KS_OK)
+        return r;
+    std::vector<ks::PodRec> fifo;
+    std::vector<int32_t> from;
+    if (n_ev)
+        if (ks_status r = drain_rows(e, t, gc, d, &fifo, &from); r != KS_OK) return r;
+    // ---- group by candidate: rows in the caller's order, FIFO within a candidate ----
+    std::vector<ks::Consolidation> h_out(m);
+    std::vector<ks::RemovalCand> cands(m);
+    std::vector<int32_t> pos(n, -1), perm(n_ev), fill(m, 0);
+    for (int32_t j = 0; j < m; j++) {
+        h_out[j] = ks::Consolidation{nodes[j], 0, -1, 0, 0, 0, 0};
+        pos[nodes[j]] = j;
+    }
+    for (int64_t i = 0; i < n_ev; i++) {
+        if ((uint32_t)from[i] >= (uint32_t)n || pos[from[i]] < 0)
+            return fail(e, KS_EDEVICE, "consolidate: evicted pod %lld runs on node %d, no candidate", (long long)i, (int)from[i]);
+        h_out[pos[from[i]]].evicted++;
+    }
+    for (int32_t j = 1; j < m; j++) h_out[j].first_row = h_out[j - 1].first_row + h_out[j - 1].evicted;
+    std::vector<ks::PodRec> recs(n_ev);
+    for (int64_t i = 0; i < n_ev; i++) {
+        const int32_t j = pos[from[i]];
+        const int64_t row = h_out[j].first_row + fill[j]++;
+        perm[row] = (int32_t)i;
+        recs[row] = fifo[i];
+    }
+    for (int32_t j = 0; j < m; j++) cands[j] = ks::RemovalCand{h_out[j].first_row, nodes[j], h_out[j].evicted};
+    HIPCHK(e, hipMemcpyAsync((void*)s.cands, cands.data(), sizeof(ks::RemovalCand) * m, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipMemcpyAsync((void*)s.out, h_out.data(), sizeof(ks::Consolidation) * m, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipMemsetAsync(s.cordon, 0, sizeof(uint32_t) * CW, e->st));
+    HIPCHK(e, hipMemsetAsync(s.received, 0, sizeof(uint32_t) * CW, e->st));
+    // ---- the chain ----
+    std::vector<unsigned long long> h_up;
+    std::vector<int32_t> so(KS_PLACE_MAX_PODS);
+    std::vector<char> by_host(m, 0);  // answered here: the single path, and its destinations
+    std::vector<ks::Placement> seg_rows;
+    ks::PodRec seg_shapes[KS_PLACE_MAX_SHAPES];
+    for (int32_t cur = 0; cur < m;) {
+        const ks::RemovalCand& cd = cands[cur];
+        if (ks::consolidate_route(cd.count) == ks::kConsSingle) {
+            ks::Consolidation& o = h_out[cur];
+            by_host[cur] = 1;
+            uint32_t word = 0;
+            HIPCHK(e, hipMemcpyAsync(&word, s.received + (cd.node >> 5), sizeof(word), hipMemcpyDeviceToHost, e->st));
+            HIPCHK(e, hipStreamSynchronize(e->st));
+            cur++;
+            if (word >> (cd.node & 31) & 1u) {
+                o.outcome = KS_CONSOLIDATE_DESTINATION;
+                continue;
+            }
+            // the single path: the chain's state and cordon copied, c taken out, ks_drain_at's rounds
+            HIPCHK(e, hipMemcpyAsync(s.state2, b.state, sizeof(int64_t) * 4 * np, hipMemcpyDeviceToDevice, e->st));
+            HIPCHK(e, hipMemcpyAsync(s.cordon2, s.cordon, sizeof(uint32_t) * CW, hipMemcpyDeviceToDevice, e->st));
+            HIPCHK(e, ks::launch_consolidate_take(s.cordon2, s.state2, np, (int32_t)n, cd.node, e->st));
+            ks::PlaceBufs x = b;
+            x.state = s.state2;
+            o.outcome = KS_CONSOLIDATE_REMOVED;
+            o.rows = cd.count;
+            for (int64_t start = 0; start < cd.count && o.outcome == KS_CONSOLIDATE_REMOVED;) {
+                int32_t ns = 0;
+                const int64_t end = ks::drain_segment(recs.data() + cd.first, cd.count, start, seg_shapes, &ns, so.data());
+                const int32_t k = (int32_t)(end - start);
+                if (k < 1 || ns < 1) return fail(e, KS_EDEVICE, "consolidate: empty segment at evicted pod %lld", (long long)(cd.first + start));
+                if (ks_status r = upload_shapes(e, x, h_up, seg_shapes, ns, so.data(), k); r != KS_OK) return r;
+                x.out = s.b.out + cd.first + start;
+                const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n, k, ns, (int32_t)nblk};
+                if (ks_status r = place_rounds(e, e->s, pc, x, so.data(), s.cordon2, "consolidate: the round from evicted pod",
+                                               cd.first + start, &info[0]);
+                    r != KS_OK)
+                    return r;
+                seg_rows.resize(k);
+                HIPCHK(e, hipMemcpyAsync(seg_rows.data(), x.out, sizeof(ks::Placement) * k, hipMemcpyDeviceToHost, e->st));
+                HIPCHK(e, hipStreamSynchronize(e->st));
+                for (int32_t i = 0; i < k; i++)
+                    if (seg_rows[i].status != KS_POD_OK) {  // the attempt ends here; the copy is dropped
+                        o.outcome = KS_CONSOLIDATE_BLOCKED;
+                        o.rows = (int32_t)(start + i + 1);
+                        o.block_status = seg_rows[i].status;
+                        break;
+                    }
+                start = end;
+            }
+            if (o.outcome == KS_CONSOLIDATE_REMOVED) {  // adopted: state, cordon, and the destinations
+                HIPCHK(e, hipMemcpyAsync(b.state, s.state2, sizeof(int64_t) * 4 * np, hipMemcpyDeviceToDevice, e->st));
+                HIPCHK(e, hipMemcpyAsync(s.cordon, s.cordon2, sizeof(uint32_t) * CW, hipMemcpyDeviceToDevice, e->st));
+                HIPCHK(e, ks::launch_consolidate_mark(s.b.out + cd.first, cd.count, (int32_t)n, s.received, e->st));
+            }
+            info[4]++;
+            continue;
+        }
+        int32_t ns = 0, k = 0;
+        const int64_t end = ks::consolidate_segment(recs.data(), cands.data(), m, cur, seg_shapes, &ns, so.data(), &k);
+        if (end <= cur) return fail(e, KS_EDEVICE, "consolidate: empty round at candidate %d", (int)cur);
+        if (k)
+            if (ks_status r = upload_shapes(e, b, h_up, seg_shapes, ns, so.data(), k); r != KS_OK) return r;
+        b.out = s.b.out + cd.first;
+        const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)n, k, ns, (int32_t)nblk};
+        const ks::ConsRound cr{s.cands, cur, (int32_t)end, cd.first, s.cordon, s.received, s.out};
+        HIPCHK(e, ks::launch_consolidate_round(e->s, pc, b, cr, e->st));
+        int32_t rb[4] = {0, 1, 0, 0};
+        HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        // a round decides its first candidate at the least (ks_device.h, Progress): anything else is a fault
+        if (rb[1] != 0 || rb[0] <= cur || rb[0] > end)
+            return fail(e, KS_EDEVICE, "consolidate: the round from candidate %d decided none", (int)cur);
+        cur = rb[0];
+        info[0]++;
+    }
+    // ---- one read-back: the answers, every row's placement and pod ----
+    std::vector<ks::Consolidation> got(m);
+    std::vector<ks::Placement> placed(n_ev);
+    std::vector<long long> ev_pod(n_ev);
+    HIPCHK(e, hipMemcpyAsync(got.data(), s.out, sizeof(ks::Consolidation) * m, hipMemcpyDeviceToHost, e->st));
+    if (n_ev) {
+        HIPCHK(e, hipMemcpyAsync(placed.data(), s.b.out, sizeof(ks::Placement) * n_ev, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipMemcpyAsync(ev_pod.data(), d.ev_pod, sizeof(long long) * n_ev, hipMemcpyDeviceToHost, e->st));
+    }
+    if (ks_status r = finish_after(e, b, milli_scale(e), s.after, after_out); r != KS_OK) return r;
+    int64_t row = 0;
+    for (int32_t j = 0; j < m; j++) {
+        ks::Consolidation& o = h_out[j];
+        if (!by_host[j]) {
+            const ks::Consolidation& v = got[j];
+            const bool sane = v.outcome == KS_CONSOLIDATE_REMOVED ? v.rows == v.evicted && v.block_status == 0
+                              : v.outcome == KS_CONSOLIDATE_DESTINATION ? v.rows == 0 && v.block_status == 0
+                              : v.outcome == KS_CONSOLIDATE_BLOCKED
+                                  ? v.rows >= 1 && v.rows <= v.evicted &&
+                                        (v.block_status == KS_POD_OVER_CAPACITY || v.block_status == KS_PLACE_NOT_FOUND)
+                                  : false;
+            if (v.node != o.node || v.evicted != o.evicted || v.first_row != o.first_row || !sane)
+                return fail(e, KS_EDEVICE, "consolidate: candidate node %d was not decided", (int)o.node);
+            o.outcome = v.outcome;
+            o.rows = v.rows;
+            o.block_status = v.block_status;
+        }
+        const int64_t src = o.first_row;  // (its rows among all evicted pods')
+        o.first_row = row;
+        if (rows_out)
+            for (int32_t i = 0; i < o.rows; i++) {
+                const ks::Placement& p = placed[src + i];
+                rows_out[row + i] = ks_eviction{ev_pod[perm[src + i]], o.node, p.node, p.status, 0, p.score, p.candidates};
+            }
+        row += o.rows;
+        info[o.outcome == KS_CONSOLIDATE_REMOVED ? 1 : o.outcome == KS_CONSOLIDATE_BLOCKED ? 2 : 3]++;
+        if (o.outcome == KS_CONSOLIDATE_REMOVED) info[5] += o.rows;
+    }
+    *n_rows = row;
+    std::memcpy(out, h_out.data(), sizeof(ks_consolidation) * m);
+    if (info_out) std::copy(info, info + KS_CONSOLIDATE_INFO, info_out);
+    return KS_OK;
+}
+
 // ---- scale-up preview (ks_scaleup.hip) -----------------------------------------------------------
 // ks_place_at's question on n_options extended clusters: the engine's cluster plus up to max_nodes
 // empty nodes of a template.  One rebuild of the state at t and one scan + merge over the real nodes

@@ -63,6 +63,13 @@ KS_DRAIN_INFO = 6
 # (csrc/ks_device.h kRemovableMaxPods = KS_PLACE_L - 1)
 KS_REMOVABLE_INFO = 6
 KS_REMOVABLE_MAX_BATCHED = 31
+# ks_consolidate_at: a candidate's outcome, the info words (rounds, removed, blocked, destinations,
+# candidates decided through the single path, pods moved), sizeof(ks_consolidation);
+# KS_CONSOLIDATE_MAX_ROUND: the pods of a candidate the rounds decide (csrc/ks_device.h kConsMaxPods)
+KS_CONSOLIDATE_BLOCKED, KS_CONSOLIDATE_REMOVED, KS_CONSOLIDATE_DESTINATION = 0, 1, 2
+KS_CONSOLIDATE_INFO = 6
+KS_CONSOLIDATION_BYTES = 32
+KS_CONSOLIDATE_MAX_ROUND = 31
 # ks_scale_up_at: options per call, appended nodes per option, the info words (options decided by the
 # batched kernel, options answered through the single path, options in which every pod was bound Ok,
 # distinct shapes); ks_scale_result.path
@@ -84,7 +91,7 @@ EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods"
                     "ks_shard_layout", "ks_merge_candidates",
                     "ks_requested_at", "ks_filter_at", "ks_score_at", "ks_cluster_series", "ks_node_peaks",
                     "ks_headroom_at", "ks_headroom_series", "ks_place_at", "ks_drain_at",
-                    "ks_removable_at", "ks_scale_up_at",
+                    "ks_removable_at", "ks_scale_up_at", "ks_consolidate_at",
                     # include/ks_ingest.h
                     "ks_parse_quantity", "ks_parse_simspec", "ks_cluster_parse", "ks_cluster_free",
                     "ks_cluster_nodes", "ks_cluster_tick", "ks_cluster_start_clock", "ks_cluster_arrays",
@@ -251,11 +258,13 @@ def load():
     L.ks_place_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, p, p, p]
     L.ks_drain_at.argtypes = [p, C.c_int64, C.c_int32, p, p, C.c_int64, C.POINTER(C.c_int64), p, p]
     L.ks_removable_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, C.c_int64, C.POINTER(C.c_int64), p]
+    L.ks_consolidate_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, C.c_int64, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64), p, p]
     L.ks_scale_up_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, C.c_int32, p, p, p, p]
     for f in ("ks_load_nodes", "ks_submit_pods", "ks_step", "ks_filter", "ks_score", "ks_usage", "ks_usage_at",
               "ks_usage_digest", "ks_pod_lookup", "ks_node_pods", "ks_requested_at", "ks_filter_at", "ks_score_at",
               "ks_cluster_series", "ks_node_peaks", "ks_headroom_at", "ks_headroom_series", "ks_place_at",
-              "ks_drain_at", "ks_removable_at", "ks_scale_up_at"):
+              "ks_drain_at", "ks_removable_at", "ks_scale_up_at", "ks_consolidate_at"):
         getattr(L, f).restype = C.c_int
     L.ks_current_tick.argtypes = [p]
     L.ks_current_tick.restype = C.c_int64

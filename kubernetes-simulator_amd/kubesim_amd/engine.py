@@ -20,7 +20,10 @@ scheduleOne, what-if   ``place_at``: where k more pods would be bound at a past 
                        private copy of the state (kubesim/kubesim.go:143-225);
                        ``drain_at``: where the pods running on a node set would go if the
                        set left k.nodes (kubesim/kubesim.go:168-206); ``removable_at``: that
-                       answer for each of m candidate nodes on its own; ``scale_up_at``:
+                       answer for each of m candidate nodes on its own;
+                       ``consolidate_at``: the candidates one after another as a scale-down
+                       pass handles them, removals kept, failed attempts rolled back;
+                       ``scale_up_at``:
                        ``place_at`` on the cluster plus up to M empty nodes of a node-group
                        template, for each of G templates on its own
 =====================  ==============================================================
@@ -65,6 +68,10 @@ assert EVICTION_DTYPE.itemsize == 40
 REMOVAL_DTYPE = np.dtype([("node", np.int32), ("evicted", np.int32), ("ok", np.int32), ("over_capacity", np.int32),
                           ("not_found", np.int32), ("removable", np.int32), ("first_row", np.int64)])
 assert REMOVAL_DTYPE.itemsize == 32
+# ks_consolidation (include/ks_engine.h)
+CONSOLIDATION_DTYPE = np.dtype([("node", np.int32), ("evicted", np.int32), ("outcome", np.int32), ("rows", np.int32),
+                                ("block_status", np.int32), ("pad", np.int32), ("first_row", np.int64)])
+assert CONSOLIDATION_DTYPE.itemsize == _lib.KS_CONSOLIDATION_BYTES
 # ks_scale_option, ks_scale_result (include/ks_engine.h)
 SCALE_OPTION_DTYPE = np.dtype([("alloc", np.int64, (4,)), ("taint", np.uint64), ("label", np.uint64),
                                ("max_nodes", np.int32), ("pad", np.int32)])
@@ -377,6 +384,54 @@ class Engine:
         res = {f: out[f].copy() for f in ("node", "evicted", "ok", "over_capacity", "not_found", "first_row")}
         res["removable"] = out["removable"] != 0
         res["info"] = info
+        res["rows"] = None
+        if rows:
+            rec = rec[:n_rows.value]
+            res["rows"] = dict(pod=rec["pod"].copy(), from_node=rec["from"].copy(), node=rec["node"].copy(),
+                               status=rec["status"].copy(), score=rec["score"].copy(),
+                               candidates=rec["candidates"].copy())
+        return res
+
+    # -- consolidation preview (include/ks_engine.h, ks_consolidate_at) --------------------------
+    def consolidate_at(self, t: int, nodes, rows: bool = True, after: bool = False):
+        """Which of ``nodes`` a scale-down pass would remove at tick t when it handles them in the
+        given order on one private state: a candidate whose running pods are all re-bound Ok is
+        removed and its placements stay; an attempt that meets a pod not bound Ok is rolled back;
+        a node that received a moved pod is not tried — no engine state changes.  ``nodes``: distinct
+        node indices.  Returns a dict of arrays over the candidates, in the caller's order — ``node``,
+        ``evicted`` (pods running on it), ``outcome`` (KS_CONSOLIDATE_BLOCKED / _REMOVED /
+        _DESTINATION), ``n_rows`` (rows written for it), ``block_status``, ``first_row`` — plus
+        ``evicted_total``, ``info`` (rounds, removed, blocked, destinations, candidates decided
+        through the single path, pods moved), ``rows``: with ``rows=True`` ``drain_at``'s arrays over
+        the rows (a removed candidate's pods, a blocked one's up to the blocking pod), candidate j's
+        at ``first_row[j]``, else None; and ``after``: with ``after=True`` the [n][4] final private
+        state, else None.  It makes the sizing call itself."""
+        nd = _c(nodes, np.int32).reshape(-1)
+        m = len(nd)
+        out = np.zeros(max(m, 1), CONSOLIDATION_DTYPE)
+        n_ev, n_rows = C.c_int64(0), C.c_int64(0)
+        aft = np.zeros((self.n, 4), np.int64) if after else None
+        info = np.zeros(_lib.KS_CONSOLIDATE_INFO, np.int64)
+        pa = _p(aft) if after else None
+        if rows:
+            # a one-row buffer first: KS_ERANGE comes back with the count as soon as the gather has it
+            rec = np.zeros(1, EVICTION_DTYPE)
+            rc = self._L.ks_consolidate_at(self.h, t, m, _p(nd), _p(out), _p(rec), 1, C.byref(n_ev), C.byref(n_rows),
+                                           pa, _p(info))
+            if rc == _lib.KS_ERANGE and 1 < n_ev.value <= _lib.KS_DRAIN_MAX_PODS:
+                rec = np.zeros(n_ev.value, EVICTION_DTYPE)
+                rc = self._L.ks_consolidate_at(self.h, t, m, _p(nd), _p(out), _p(rec), n_ev.value, C.byref(n_ev),
+                                               C.byref(n_rows), pa, _p(info))
+        else:
+            rc = self._L.ks_consolidate_at(self.h, t, m, _p(nd), _p(out), None, 0, C.byref(n_ev), C.byref(n_rows), pa,
+                                           _p(info))
+        self._check(rc)
+        out = out[:m]
+        res = {f: out[f].copy() for f in ("node", "evicted", "outcome", "block_status", "first_row")}
+        res["n_rows"] = out["rows"].copy()
+        res["evicted_total"] = n_ev.value
+        res["info"] = info
+        res["after"] = aft
         res["rows"] = None
         if rows:
             rec = rec[:n_rows.value]

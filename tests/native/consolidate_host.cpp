@@ -1,0 +1,334 @@
+// Host build of the consolidation preview's host-side pieces (ks_device.h: consolidate_route,
+// consolidate_segment and the placement functions; ks_carve.h: carve_consolidate), for CPU tests only.
+//   ks_host_consolidate          a serial restatement of ks_consolidate_at's rounds on place_serial.h's
+//                                list builder and pod loop: the lists of the committed state with the
+//                                removed nodes cordoned, the candidates of a round walked as
+//                                transactions (the open candidate's entries flagged, its counts
+//                                corrected, roll-back of the changed set, the flags, the counts and
+//                                nchg on a block or a stop), the single path for a candidate of
+//                                kPlaceL pods or more;
+//   ks_host_consolidate_brute    the chain as written: the plain sequential argmax over the nodes that
+//                                remain, a copy of the cluster restored on a block;
+//   ks_host_consolidate_segments the round walk (consolidate_segment);
+//   ks_host_consolidate_route    who decides a candidate;
+//   ks_host_consolidate_carve    carve_consolidate run twice, as ks_consolidate_at does.
+// A candidate's pods are rows [first, first + cnt) of shape_of / out, candidates in the caller's
+// order.  Not part of the product.
+#include <cstdio>
+#include <cstring>
+
+#include "../../kubernetes-simulator_amd/csrc/ks_carve.h"
+#include "place_serial.h"
+
+using namespace place_serial;
+
+#define CASE_ARGS CLUSTER_ARGS, int32_t k, const int32_t *shape_of, int32_t m, const int32_t *cand_node, const int32_t *cand_cnt
+#define CASE_PASS CLUSTER_PASS
+
+static void empty_row(ks::NodeV& v) { v.rc = v.rm = v.rg = v.nr = 0; }
+
+// The chain as the header states it.
+extern "C" int ks_host_consolidate_brute(CASE_ARGS, ks::Placement* out, ks::Consolidation* res, int64_t* after) {
+    Cluster s = make_cluster(CASE_PASS);
+    std::vector<char> R(n, 0), V(n, 0);
+    int64_t first = 0;
+    for (int32_t a = 0; a < m; first += cand_cnt[a], a++) {
+        const int32_t c = cand_node[a], cnt = cand_cnt[a];
+        res[a] = ks::Consolidation{c, cnt, ks::kConsDestination, 0, 0, 0, first};
+        if (V[c]) continue;
+        const Cluster saved = s;
+        empty_row(s.node[c]);
+        std::vector<int32_t> got;
+        int32_t status = ks::kPlaceOk, rows = 0;
+        for (int32_t i = 0; i < cnt && status == ks::kPlaceOk; i++, rows++) {
+            const ks::PodRec& p = s.shapes[shape_of[first + i]];
+            uint64_t best = 0;
+            int64_t cnd = 0;
+            for (int32_t nd = 0; nd < n; nd++) {
+                if (R[nd] || nd == c) continue;
+                const uint64_t key = ks::place_key(s.c, p, s.node[nd], (uint32_t)nd);
+                cnd += key != 0;
+                best = key > best ? key : best;
+            }
+            if (!best) {
+                status = ks::kPlaceNotFound;
+                out[first + i] = ks::Placement{-1, status, -1, cnd};
+                continue;
+            }
+            const uint32_t X = ks::place_key_node(best);
+            status = ks::place_bind(p, s.node[X]);
+            out[first + i] = ks::Placement{(int32_t)X, status, (int64_t)(best >> 32) - 1, cnd};
+            got.push_back((int32_t)X);
+        }
+        if (status == ks::kPlaceOk) {
+            res[a].outcome = ks::kConsRemoved;
+            res[a].rows = cnt;
+            R[c] = 1;
+            for (int32_t x : got) V[x] = 1;
+        } else {
+            res[a].outcome = ks::kConsBlocked;
+            res[a].rows = rows;
+            res[a].block_status = status;
+            s = saved;
+        }
+    }
+    state_out(s, after);
+    return 0;
+}
+
+// The rounds.  `mode` takes one part of the roll-back out, to show that the tests see it: 1: the flag
+// words are not restored, 2: the running counts are not restored, 3: nchg is not restored (the slots
+// the attempt appended stay).  info[0]: rounds of the chain, info[1]: candidates of the single path;
+// stats[0]: roll-backs after at least one Ok pod, [1]: rounds ended by kPlaceStop inside a candidate,
+// [2]: Ok pods taken back out of a slot that existed before the attempt, [3]: pods decided from the
+// changed set.  Returns 0, -1: a round decided no candidate, -2: a removed node or the open candidate
+// won a pod, -3: the single path's rounds failed.
+extern "C" int ks_host_consolidate(CASE_ARGS, int32_t mode, ks::Placement* out, ks::Consolidation* res, int64_t* after,
+                                   int64_t* info, int64_t* stats) {
+    Cluster s = make_cluster(CASE_PASS);
+    std::vector<char> R(n, 0), V(n, 0);
+    std::vector<ks::RemovalCand> cands(m);
+    int64_t rows_all = 0;
+    for (int32_t a = 0; a < m; a++) {
+        cands[a] = ks::RemovalCand{rows_all, cand_node[a], cand_cnt[a]};
+        res[a] = ks::Consolidation{cand_node[a], cand_cnt[a], -1, 0, 0, 0, rows_all};
+        rows_all += cand_cnt[a];
+    }
+    std::vector<ks::PodRec> recs(rows_all);
+    for (int64_t i = 0; i < rows_all; i++) recs[i] = s.shapes[shape_of[i]];
+    info[0] = info[1] = 0;
+    stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    std::vector<int32_t> so(ks::kPlaceMaxPods);
+    for (int32_t cur = 0; cur < m;) {
+        const ks::RemovalCand cd = cands[cur];
+        const auto cordoned_key = [&](const Cluster& cl, int32_t extra) {
+            return [&cl, &R, extra](const ks::PodRec& p, int32_t nd) {
+                return R[nd] || nd == extra ? 0ull : ks::place_key(cl.c, p, cl.node[nd], (uint32_t)nd);
+            };
+        };
+        if (ks::consolidate_route(cd.count) == ks::kConsSingle) {
+            cur++;
+            if (V[cd.node]) {
+                res[cur - 1].outcome = ks::kConsDestination;
+                continue;
+            }
+            // the single path: a copy, the candidate cordoned and emptied, the placement rounds
+            Cluster x = s;
+            empty_row(x.node[cd.node]);
+            struct Gone : Hooks {
+                const std::vector<char>* R;
+                int32_t c;
+                int veto(uint32_t X) const { return (*R)[X] || (int32_t)X == c ? -4 : 0; }
+            } h{{}, &R, cd.node};
+            int64_t rinfo[4] = {0, 0, 0, 0};
+            const int rc = run_rounds(x, shape_of + cd.first, cd.count, cordoned_key(x, cd.node), h, out + cd.first, rinfo, nullptr);
+            if (rc) return rc == -4 ? -2 : -3;
+            info[0] += rinfo[0];
+            info[1]++;
+            ks::Consolidation& o = res[cur - 1];
+            o.outcome = ks::kConsRemoved;
+            o.rows = cd.count;
+            for (int32_t i = 0; i < cd.count; i++)
+                if (out[cd.first + i].status != ks::kPlaceOk) {
+                    o.outcome = ks::kConsBlocked;
+                    o.rows = i + 1;
+                    o.block_status = out[cd.first + i].status;
+                    break;
+                }
+            if (o.outcome == ks::kConsRemoved) {
+                s = x;
+                R[cd.node] = 1;
+                for (int32_t i = 0; i < cd.count; i++) V[out[cd.first + i].node] = 1;
+            }
+            continue;
+        }
+        // ---- one round: the segment, its lists on the committed state, the transactions ----
+        Cluster seg = s;
+        seg.shapes.assign(ks::kPlaceMaxShapes, ks::PodRec{});
+        int32_t ns = 0, k_seg = 0;
+        const int64_t end = ks::consolidate_segment(recs.data(), cands.data(), m, cur, seg.shapes.data(), &ns, so.data(), &k_seg);
+        if (end <= cur) return -1;
+        seg.shapes.resize(ns);
+        Lists l = build_lists(seg, nullptr, cordoned_key(seg, -1));
+        std::vector<Chg> chg;
+        std::vector<ks::Placement> got(std::max(k_seg, 1));
+        struct Gone : Hooks {
+            const std::vector<char>* R;
+            int32_t c = -1;
+            int veto(uint32_t X) const { return (*R)[X] || (int32_t)X == c ? -4 : 0; }
+        } h;
+        h.R = &R;
+        bool stopped = false;
+        int32_t a = cur;
+        for (; a < end && !stopped; a++) {
+            const ks::RemovalCand c = cands[a];
+            bool dest = V[c.node];
+            for (const Chg& x : chg) dest |= x.node == c.node;
+            if (dest) {
+                res[a].outcome = ks::kConsDestination;
+                continue;
+            }
+            const size_t nchg_s = chg.size();
+            const std::vector<uint32_t> flag_s = l.flag;
+            const std::vector<long long> cc_s = l.cc;
+            for (int32_t j = 0; j < ns; j++) {
+                l.flag[j] |= ks::removable_entries_on<L>(&l.top[(size_t)j * L], (uint32_t)c.node);
+                l.cc[j] -= ks::place_is_cand(seg.c, seg.shapes[j], seg.node[c.node]);
+            }
+            h.c = c.node;
+            const int32_t beg = (int32_t)(c.first - cd.first);
+            int32_t i = beg, status = ks::kPlaceOk;
+            for (; i < beg + c.count; i++) {
+                const Run r = decide_pods(seg, l, so.data(), i, i + 1, chg, h, got.data());
+                if (r.veto) return -2;
+                stats[3] += r.from_changed;
+                if (r.stopped) {
+                    stopped = true;
+                    break;
+                }
+                status = got[i].status;
+                if (status != ks::kPlaceOk) break;
+            }
+            if (!stopped && status == ks::kPlaceOk) {  // accept: c is a removed node for the rest of the round
+                for (int32_t q = beg; q < beg + c.count; q++) out[cd.first + q] = got[q];
+                res[a].outcome = ks::kConsRemoved;
+                res[a].rows = c.count;
+                R[c.node] = 1;
+                empty_row(seg.node[c.node]);
+                empty_row(s.node[c.node]);
+                continue;
+            }
+            // roll back: pods [beg, i) were bound Ok
+            stats[0] += i > beg;
+            for (int32_t q = beg; q < i; q++) {
+                size_t slot = 0;
+                while (slot < chg.size() && chg[slot].node != got[q].node) slot++;
+                if (slot >= nchg_s) continue;  // (appended by the attempt: dropped below)
+                const ks::PodRec& p = seg.shapes[so[q]];
+                if (p.keymask & 1) chg[slot].v.rc -= p.req[0];
+                if (p.keymask & 2) chg[slot].v.rm -= p.req[1];
+                if (p.keymask & 4) chg[slot].v.rg -= p.req[2];
+                chg[slot].v.nr -= 1;
+                stats[2]++;
+            }
+            if (mode != 1) l.flag = flag_s;
+            if (mode != 2) l.cc = cc_s;
+            if (mode != 3) chg.resize(nchg_s);
+            if (stopped) {
+                stats[1]++;
+                break;  // (a is the candidate that opens the next round)
+            }
+            for (int32_t q = beg; q <= i; q++) out[cd.first + q] = got[q];
+            res[a].outcome = ks::kConsBlocked;
+            res[a].rows = i - beg + 1;
+            res[a].block_status = status;
+        }
+        if ((int64_t)chg.size() > ks::kPlaceMaxPods) return -1;
+        for (const Chg& x : chg) {  // commit
+            s.node[x.node] = x.v;
+            V[x.node] = 1;
+        }
+        if (a == cur) return -1;
+        cur = a;
+        info[0]++;
+    }
+    state_out(s, after);
+    return 0;
+}
+
+// consolidate_segment from candidate `start` over m candidates, candidate a's pods the next cnt[a]
+// rows, row i's shape the record of id ids[i].  Returns the end, the shapes in *n_shapes and
+// shapes_out, the pods in *n_pods and shape_of[row - first row of start].
+extern "C" int64_t ks_host_consolidate_segment(int64_t m, const int32_t* cnt, const int64_t* ids, int64_t start,
+                                               int32_t* n_shapes, int32_t* n_pods, int32_t* shape_of, ks::PodRec* shapes_out) {
+    std::vector<ks::RemovalCand> cands(m);
+    int64_t rows = 0;
+    for (int64_t a = 0; a < m; a++) {
+        cands[a] = ks::RemovalCand{rows, (int32_t)a, cnt[a]};
+        rows += cnt[a];
+    }
+    std::vector<ks::PodRec> recs(rows);
+    for (int64_t i = 0; i < rows; i++) {
+        recs[i] = ks::PodRec{};
+        recs[i].req[0] = 1000 + ids[i];
+        recs[i].req[1] = 77;  // (unmasked: ignored)
+        recs[i].keymask = 1;
+        recs[i].tol = (uint64_t)ids[i] * 0x9E3779B97F4A7C15ull;
+        recs[i].flags = (uint32_t)(ids[i] & 3);
+    }
+    return ks::consolidate_segment(recs.data(), cands.data(), m, start, shapes_out, n_shapes, shape_of, n_pods);
+}
+
+extern "C" int ks_host_consolidate_route(int64_t pods) { return ks::consolidate_route(pods); }
+
+extern "C" int ks_host_consolidate_limits(int32_t* out) {
+    out[0] = ks::kPlaceMaxShapes; out[1] = ks::kConsMaxPods; out[2] = L; out[3] = (int32_t)sizeof(ks::Consolidation);
+    out[4] = ks::kPlaceMaxPods; out[5] = ks::kConsRound; out[6] = ks::kConsSingle;
+    out[7] = ks::kConsBlocked; out[8] = ks::kConsRemoved; out[9] = ks::kConsDestination;
+    return 0;
+}
+
+// carve_consolidate at edge counts, twice as ks_consolidate_at runs it: every range inside the
+// reserved size, aligned for its element, overlapping no other, and written.  Returns the violated checks.
+extern "C" int64_t ks_host_consolidate_carve() {
+    using ks_host::Carve;
+    struct Range { const char* name; const void* p; int64_t bytes, align; };
+    int64_t bad = 0;
+    auto fail = [&](const char* what, const char* name, int64_t a, int64_t b) {
+        if (bad++ < 20) std::fprintf(stderr, "carve_consolidate: %s: %s (%lld, %lld)\n", name, what, (long long)a, (long long)b);
+    };
+    for (int64_t n : {1, 31, 32, 33, 255, 256, 257, 600})
+        for (int64_t n_ev : {0, 1, 3, 33, 1000, 1025, 65536})
+            for (int64_t m : {(int64_t)1, n}) {
+                const int64_t np = (n + 63) / 64 * 64, nblk = (n + 255) / 256, cw = (n + 31) / 32;
+                ks::DrainBufs d{};
+                Carve qs(8);
+                ks_host::carve_consolidate(qs, n, np, nblk, n_ev, m, cw, &d);
+                const int64_t words = qs.at;
+                std::vector<long double> mem((words * 8 + 15) / 16 + 1);
+                char* base = (char*)mem.data();
+                qs = Carve(8, base);
+                const ks_host::ConsolidateScratch s = ks_host::carve_consolidate(qs, n, np, nblk, n_ev, m, cw, &d);
+                if (qs.at != words) fail("the two passes differ", "d_qs", qs.at, words);
+                if (d.cap != n_ev || s.b.n_pad != np) fail("capacities", "consolidate", d.cap, s.b.n_pad);
+                const int64_t S = ks::kPlaceMaxShapes;
+                const std::vector<Range> rs = {
+                    {"state", s.b.state, 32 * np, 8},
+                    {"shapes", s.b.shapes, 48 * S, 16},
+                    {"shape_of", s.b.shape_of, 4 * ks::kPlaceMaxPods, 4},
+                    {"lists", s.b.lists, 8 * S * nblk * L, 8},
+                    {"top", s.b.top, 8 * S * L, 8},
+                    {"ccount", s.b.ccount, 8 * S, 8},
+                    {"rb", s.b.rb, 16, 4},
+                    {"placed", s.b.out, 24 * n_ev, 8},
+                    {"ev_pod", d.ev_pod, 8 * n_ev, 8},
+                    {"ev_from", d.ev_from, 4 * n_ev, 4},
+                    {"ev_rec", d.ev_rec, 48 * n_ev, 16},
+                    {"state2", s.state2, 32 * np, 8},
+                    {"cordon", s.cordon, 4 * cw, 4},
+                    {"received", s.received, 4 * cw, 4},
+                    {"cordon2", s.cordon2, 4 * cw, 4},
+                    {"cands", s.cands, 16 * m, 8},
+                    {"out", s.out, 32 * m, 8},
+                    {"after", s.after, 32 * n, 8}};
+                for (const Range& r : rs) {
+                    const int64_t off = (const char*)r.p - base;
+                    if (off < 0 || off + r.bytes > words * 8) fail("outside the reserved size", r.name, off, r.bytes);
+                    else std::memset(base + off, 0x5A, r.bytes);
+                    if (off % r.align) fail("misaligned", r.name, off, r.align);
+                    for (const Range& q : rs)
+                        if (&q != &r && r.bytes && q.bytes && (const char*)q.p < (const char*)r.p + r.bytes &&
+                            (const char*)r.p < (const char*)q.p + q.bytes)
+                            fail("overlaps", r.name, off, (const char*)q.p - base);
+                }
+            }
+    return bad;
+}
+
+#ifdef KS_CONSOLIDATE_MAIN
+int main() {
+    const int64_t bad = ks_host_consolidate_carve();
+    std::printf("carve_consolidate check: %lld violated\n", (long long)bad);
+    return bad != 0;
+}
+#endif
