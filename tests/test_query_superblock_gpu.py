@@ -8,14 +8,23 @@ end of the run: in blocks 3 and 40, at index 16,383 (the last pod of super block
 super block 0; on the twin trace without stragglers it must skip super block 0.  Binds come from the
 C oracle, states from tests/state_ref.py, counts and placements from tests/headroom_ref.py and
 tests/place_ref.py.  Everything is exact integer equality.
+
+The gather of the drain family (ks_drain.hip) walks the same candidate blocks: at every tick of AT the
+nodes the stragglers run on and two others are drained, scanned for removal and consolidated, on
+both traces, against tests/drain_ref.py, removable_ref.py and consolidate_ref.py.  On the twin those
+nodes run only pods of super block 1 once super block 0 has ended: a gather that kept a block of
+super block 0, or dropped one of super block 1, changes the eviction list.
 """
 import functools
 
 import numpy as np
 import pytest
 
+import consolidate_ref as cr
+import drain_ref as dr
 import headroom_ref as hr
 import place_ref as pr
+import removable_ref as rr
 import state_ref as sr
 import usage_digest as ud
 from harness import MODES, assert_same_binds, encoded, make_engine, small_trace
@@ -78,6 +87,34 @@ def _case(stragglers):
     return dict(tr=tr, enc=enc, ob=ob, ref=ref, shapes=shapes, elig=elig, cfg=pr.engine_cfg(MODES[MODE], enc))
 
 
+@functools.lru_cache(maxsize=None)
+def _drained():
+    """the nodes the stragglers run on plus the two others that run the most pods over the ticks of AT
+    on the twin (the same nodes on both traces)"""
+    on = sorted(set(int(x) for x in _case(True)["ob"]["node"][list(STRAGGLERS)]))
+    busy = sum(_case(False)["ref"].at(t)[:, 3] for t in AT)
+    return tuple(on + [int(x) for x in np.argsort(-busy, kind="stable") if x not in on][:2])
+
+
+@functools.lru_cache(maxsize=None)
+def _drain_refs(stragglers, t):
+    """(drain, removal scan, consolidation in the given and the reverse order) of _drained() at tick t"""
+    r = _case(stragglers)
+    tr, enc, ob, cfg, nodes = r["tr"], r["enc"], r["ob"], r["cfg"], _drained()
+    state = r["ref"].at(t)
+    ev, frm = dr.running_on(tr, enc, ob, t, nodes)
+    drain = dr.fast_drain(enc["alloc"], state, cfg, enc["pods"], ev, frm, nodes)
+    # -- on the reference alone -------------------------------------------------------------------
+    assert (np.diff(drain["pod"]) > 0).all()
+    if stragglers:
+        assert set(STRAGGLERS) <= set(drain["pod"].tolist()) or t < STRAGGLERS[-1] + 1
+    elif t >= 16_640:
+        assert len(ev) >= 1 and min(ev) >= SUP, "the twin's drained nodes run a pod of super block 0"
+    rem = rr.fast_removable(tr, enc, ob, cfg, t, nodes, state=state)
+    cons = [cr.fast_consolidate(tr, enc, ob, cfg, t, order, state=state) for order in (nodes, nodes[::-1])]
+    return drain, rem, cons
+
+
 def _check(stragglers):
     r = _case(stragglers)
     ref, enc, shapes = r["ref"], r["enc"], r["shapes"]
@@ -97,6 +134,12 @@ def _check(stragglers):
         np.testing.assert_array_equal(out, cols[0], err_msg=f"headroom at tick {t}")
         want = pr.fast_place(enc["alloc"], state, r["cfg"], shapes, shape_of)
         pr.assert_same(eng.place_at(t, shapes, shape_of, after=True), want, f"place at tick {t}")
+        nodes = _drained()
+        drain, rem, cons = _drain_refs(stragglers, t)
+        dr.assert_same(eng.drain_at(t, nodes, after=True), drain, f"drain at tick {t}")
+        rr.assert_same(eng.removable_at(t, nodes, rows=True), rem, f"removable at tick {t}")
+        for order, want in zip((nodes, nodes[::-1]), cons):
+            cr.assert_same(eng.consolidate_at(t, order, rows=True, after=True), want, f"consolidate at tick {t} from {order[0]}")
     for lo, hi in WINDOWS:
         w = ref.window(lo, hi)
         np.testing.assert_array_equal(eng.node_peaks(lo, hi), w.max(axis=0), err_msg=f"peaks [{lo}, {hi})")
@@ -110,5 +153,8 @@ def _check(stragglers):
 
 def test_queries_past_a_super_block_with_and_without_stragglers():
     _case(True), _case(False)       # both references and their conditions before any engine
+    assert 3 <= len(_drained()) <= 6
+    moved = [sum(len(_drain_refs(s, t)[0]["pod"]) for t in AT) for s in (True, False)]
+    assert min(moved) >= len(AT), moved    # on either trace the gather has a pod to find at most ticks
     _check(True)
     _check(False)                   # the twin: super block 0 is skipped whole at every tick past 16,500
