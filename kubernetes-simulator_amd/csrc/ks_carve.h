@@ -8,7 +8,7 @@
 #pragma once
 #include <cstdint>
 
-#include "ks_device.h"
+#include "ks_query.h"
 
 namespace ks_host {
 
@@ -31,7 +31,7 @@ struct Carve {
 constexpr int64_t kShapeWords = (int64_t)sizeof(ks::PodRec) / 8 * ks::kPlaceMaxShapes;
 static_assert(kShapeWords % 2 == 0, "shape_of follows the shape records on a 16-byte boundary");
 
-// The rounds' buffers in d_qs (ks_device.h PlaceBufs; cnt is the caller's, in d_qi): a round set
+// The rounds' buffers in d_qs (ks_query.h PlaceBufs; cnt is the caller's, in d_qi): a round set
 // uploads up to so_cap pods' shape_of, the call places n_placed pods in all.  ks_place_at: both k;
 // ks_drain_at: a segment's KS_PLACE_MAX_PODS and every evicted pod.
 inline ks::PlaceBufs carve_place(Carve& qs, int64_t np, int64_t nblk, int64_t so_cap, int64_t n_placed) {
@@ -188,6 +188,15 @@ inline ScaleScratch carve_scale_up(Carve& qs, Carve& qi, int64_t n, int64_t np, 
     s.x = carve_place(qs, s.np_ext, s.nblk_ext, k, k);
     s.x.cnt = qi.take<int32_t>(ks::kPlaceMaxShapes * s.nblk_ext);
     return s;
+}
+// an option's extended cluster as a node table at its own stride np_g <= np_ext: the constants of
+// ext_node, the state [4][np_g]
+inline ks::NodeSoA scale_up_nodes(int64_t* ext_node, int64_t* state, int64_t np_g) {
+    ks::NodeSoA sx{};
+    sx.ac = ext_node; sx.am = ext_node + np_g; sx.ag = ext_node + 2 * np_g; sx.ap = ext_node + 3 * np_g;
+    sx.taint = (uint64_t*)(ext_node + 4 * np_g); sx.label = (uint64_t*)(ext_node + 5 * np_g);
+    sx.rc = state; sx.rm = state + np_g; sx.rg = state + 2 * np_g; sx.nr = state + 3 * np_g;
+    return sx;
 }
 
 // ks_node_peaks / ks_headroom_series: per node the offset, cursor and count of its pods in list[cap]

@@ -11,9 +11,9 @@
 //   resolve_kernel<false, true> (ks_place_resolve.h) one workgroup walks the round's candidates with the
 //                              placement rounds' pod loop inside a transaction per candidate, commits
 //                              the kept placements and reports the next candidate.
-// The argument is in ks_device.h, above consolidate_route.  The two small kernels below serve the
+// The argument is in ks_query.h, above consolidate_route.  The two small kernels below serve the
 // host's single path for a candidate with more pods than one set of lists decides.
-#include "ks_device.h"
+#include "ks_query.h"
 #include "ks_place_resolve.h"
 
 namespace ks {

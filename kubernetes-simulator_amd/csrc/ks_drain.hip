@@ -9,13 +9,13 @@
 //   drain_scan_kernel    one workgroup: the exclusive scan of the block counts in chunks of 256 with a
 //                        carry, and the total;
 //   drain_fill_kernel    the same predicate; a pod's rank is its block's offset + the counts of the
-//                        waves before its own + the selected lanes below it (drain_rank, ks_device.h),
+//                        waves before its own + the selected lanes below it (drain_rank, ks_query.h),
 //                        and it writes its index, its node and its 48-byte record there;
 //   drain_clear_kernel   zeroes the cordoned nodes' rc rm rg nr in the 4 x N_pad scratch state;
 //   drain_pack_kernel    the ks_eviction rows from the gather and the rounds' placements.
 // The host lists the candidate blocks in ascending order, so ranks follow the pod index: the output
 // is the FIFO order by construction, with no atomics and whatever the order of execution.
-#include "ks_device.h"
+#include "ks_query.h"
 
 namespace ks {
 namespace {

@@ -2,8 +2,8 @@
 // submit, scenario groups' life cycle, node sharding, debug and statistics.  The engine record is in
 // ks_host.h, the owners that release its GPU resources in ks_own.h (engine_free only waits and deletes);
 // ks_step and ks_group_step are in ks_step.cpp; the entry points that answer about a run after the fact (filter / score, usage,
-// past-tick state, headroom, placement and drain previews, name-keyed lookups) are in
-// ks_queries.cpp, the device self-tests in ks_selftest.cpp.
+// past-tick state, headroom, name-keyed lookups) are in ks_queries.cpp, the five previews in
+// ks_previews.cpp, the device self-tests in ks_selftest.cpp.
 //
 // Host responsibilities (everything that is independent of placements):
 //  * FIFO + one-pod-per-tick: the bind tick of pod j is max(bind_tick[j-1] + 1, arrival_j)

@@ -1,6 +1,7 @@
 // ks_host.h — the engine record and the few host functions its translation units share
 // (internal: ks_engine.cpp owns the engine's life cycle and loads it, ks_step.cpp steps it,
-// ks_queries.cpp answers about it after the fact).  Every GPU resource of the engine and of a group
+// ks_queries.cpp and ks_previews.cpp answer about it after the fact; what those two share is
+// ks_queries.h).  Every GPU resource of the engine and of a group
 // is held by an owner of ks_own.h and released by the record's destructor; what is allocated on first
 // use is a bundle in an optional slot, whole or absent (ks_own::build).
 #pragma once

@@ -4,10 +4,10 @@
 // CreatePod (kubesim/kubesim.go:143-225, kubesim/node/node.go:36-60) on a private copy of the state
 // at tick t: the 4 x N_pad scratch requested_kernel (ks_query.hip) rebuilds from the binds, here in
 // milli-units (or, when every request is a whole multiple of the engine's unit, in device units:
-// place_whole_units, ks_device.h).  The engine's node table, its lists and its resolvers are not involved; the kernels
+// place_whole_units, ks_query.h).  The engine's node table, its lists and its resolvers are not involved; the kernels
 // read the cluster's constants (alloc, taints, labels) and write the scratch only.
 //
-// The call runs in rounds (the exactness argument is in ks_device.h, above place_decide):
+// The call runs in rounds (the exactness argument is in ks_query.h, above place_decide):
 //   place_scan_kernel     per 256-node block and active shape the block's exact top-L keys and its
 //                         candidate count;
 //   place_merge_kernel    per active shape the exact global top-L (topl_insert) and the count;
@@ -18,12 +18,12 @@
 // The scale-up preview (ks_scale_up_at, ks_scaleup.hip) runs the same pod loop on the same lists:
 //   resolve_kernel<true>  one workgroup per option decides the k pods in order, its changed set
 //                         private in LDS, the unchanged appended nodes stood for by the first of
-//                         them (the argument is in ks_device.h, above scaleup_fresh_key); it commits
+//                         them (the argument is in ks_query.h, above scaleup_fresh_key); it commits
 //                         nothing and reads top / ccount / state read-only.
 // Integers only, no global atomics, no communication between workgroups.  The resolver sets flag
 // bits with LDS atomics: the sets of one pod commute with each other, and barriers separate them
 // from every read of the flags, so the result does not depend on the order of execution.
-#include "ks_device.h"
+#include "ks_query.h"
 #include "ks_place_resolve.h"
 
 namespace ks {
@@ -40,7 +40,7 @@ static_assert(kPBlk == 4 * kWave, "the extraction reads four keys per lane");
 // keys are distinct, so exactly one lane does.  lists[(shape * nblk + block) * L ..] descending,
 // 0-padded; cnt[shape * nblk + block] the block's non-zero keys.
 // kCordon (ks_drain_at): a node whose bit is set in `cordon` gets key 0 for every shape — it is in
-// no list and no count (the argument is in ks_device.h, above launch_place_round).
+// no list and no count (the argument is in ks_query.h, above launch_place_round).
 // ---------------------------------------------------------------------------------------------
 template <bool kCordon>
 __global__ __launch_bounds__(kPBlk) void place_scan_kernel(NodeSoA s, const int64_t* __restrict__ state, int64_t n_pad,

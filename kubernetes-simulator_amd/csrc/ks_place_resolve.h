@@ -4,7 +4,7 @@
 // ks_consolidate.hip for the consolidation rounds.  Device code only; each translation unit gets its
 // own instantiations.
 #pragma once
-#include "ks_device.h"
+#include "ks_query.h"
 
 namespace ks {
 namespace {
@@ -57,7 +57,7 @@ __device__ __forceinline__ bool shape_active(uint64_t active, int sh) { return (
 // constants and leave no register behind.
 // kCons = true, the consolidation preview's rounds (ks_consolidate_at): one workgroup walks the
 // candidates [c0, c1) of ConsRound in order; pods [0, k) are their pods, candidate after candidate.
-// A candidate is a transaction around the same pod loop (the argument is in ks_device.h, above
+// A candidate is a transaction around the same pod loop (the argument is in ks_query.h, above
 // consolidate_route):
 //   open    (where the previous candidate ended; one loop closes a candidate and opens the next, so a
 //           candidate without pods is accepted by its next turn) a candidate that is a destination —
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
             wmax[par][wave] = 0ull;
         }
         __syncthreads();  // (A)
-        uint64_t D = 0ull;  // (scale-up: D' of ks_device.h)
+        uint64_t D = 0ull;  // (scale-up: D' of ks_query.h)
 #pragma unroll
         for (int w = 0; w < kPRes / kWave; ++w) D = wmax[par][w] > D ? wmax[par][w] : D;
         const int eS = place_first_unchanged<kPlaceL>(llen[sh], lflag[sh]);

@@ -13,7 +13,7 @@
 //
 // Grids follow the host's run-interval index (ks_engine.cpp usage_blocks): one workgroup per
 // candidate block of kQBlk pods, so the cost follows the pods that may run in the queried ticks.
-#include "ks_device.h"
+#include "ks_query.h"
 
 namespace ks {
 namespace {
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void peaks_kernel(const int32_t* __restrict__ 
 
 // ---------------------------------------------------------------------------------------------
 // ks_headroom_at: per shape the nine columns of include/ks_engine.h over the counts c(node, shape)
-// (headroom_count, ks_device.h) at the rebuilt state.  One thread per node: its six constants and
+// (headroom_count, ks_query.h) at the rebuilt state.  One thread per node: its six constants and
 // four state words stay in registers while the k shape records come through scalar loads.  A
 // workgroup reduces three words per shape — Σ c; the argmax key (c << 32 | ~node: the highest
 // count, then the lowest node); the six small counters (nodes with c >= 1, limiting cpu / memory /

@@ -7,11 +7,11 @@
 // most 64 distinct shapes on the un-cordoned base state (launch_place_lists, ks_place.hip) and
 //   removable_resolve_kernel   one wave per candidate decides its pods in FIFO order from those lists:
 //                              the candidate's own entries flagged from the start, its running counts
-//                              corrected for its own node (the argument is in ks_device.h, above
+//                              corrected for its own node (the argument is in ks_query.h, above
 //                              removable_route), its changed set private in LDS.
 // Integers only, no atomics, no communication between workgroups; nothing is written but the
 // candidate's own rows and its summary, so the scratch state stays the base state for every segment.
-#include "ks_device.h"
+#include "ks_query.h"
 
 namespace ks {
 namespace {

@@ -10,7 +10,7 @@
 //   scaleup_extend_kernel    the node constants of one option's extended cluster, for the options
 //                            the resolver stopped at (the host re-places them with ks_place_at's own
 //                            rounds on n + max_nodes nodes).
-#include "ks_device.h"
+#include "ks_query.h"
 
 namespace ks {
 namespace {

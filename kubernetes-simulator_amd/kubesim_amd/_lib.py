@@ -60,12 +60,12 @@ KS_DRAIN_INFO = 6
 # ks_removable_at: the info words (segments, candidates resolved by the batched kernel, candidates
 # answered through the single-drain path, candidates with no running pod, removable candidates,
 # evicted pods); KS_REMOVABLE_MAX_BATCHED: the pods of a candidate the batched kernel decides
-# (csrc/ks_device.h kRemovableMaxPods = KS_PLACE_L - 1)
+# (csrc/ks_query.h kRemovableMaxPods = KS_PLACE_L - 1)
 KS_REMOVABLE_INFO = 6
 KS_REMOVABLE_MAX_BATCHED = 31
 # ks_consolidate_at: a candidate's outcome, the info words (rounds, removed, blocked, destinations,
 # candidates decided through the single path, pods moved), sizeof(ks_consolidation);
-# KS_CONSOLIDATE_MAX_ROUND: the pods of a candidate the rounds decide (csrc/ks_device.h kConsMaxPods)
+# KS_CONSOLIDATE_MAX_ROUND: the pods of a candidate the rounds decide (csrc/ks_query.h kConsMaxPods)
 KS_CONSOLIDATE_BLOCKED, KS_CONSOLIDATE_REMOVED, KS_CONSOLIDATE_DESTINATION = 0, 1, 2
 KS_CONSOLIDATE_INFO = 6
 KS_CONSOLIDATION_BYTES = 32

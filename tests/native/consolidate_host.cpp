@@ -1,4 +1,4 @@
-// Host build of the consolidation preview's host-side pieces (ks_device.h: consolidate_route,
+// Host build of the consolidation preview's host-side pieces (ks_query.h: consolidate_route,
 // consolidate_segment and the placement functions; ks_carve.h: carve_consolidate), for CPU tests only.
 //   ks_host_consolidate          a serial restatement of ks_consolidate_at's rounds on place_serial.h's
 //                                list builder and pod loop: the lists of the committed state with the

@@ -1,4 +1,4 @@
-// Host build of the drain preview's host-side pieces (ks_device.h: drain_segment, drain_rank,
+// Host build of the drain preview's host-side pieces (ks_query.h: drain_segment, drain_rank,
 // drain_below, drain_cordoned and the placement functions), for CPU tests only.
 //   ks_host_drain_segments   ks_drain_at's segment walk over a sequence of pod records;
 //   ks_host_drain_ranks      a serial restatement of the gather (ks_drain.hip): per 256-pod block

@@ -1,7 +1,7 @@
-// Host build of the headroom count (ks_device.h headroom_count / head_div), for CPU tests only: the
+// Host build of the headroom count (ks_query.h headroom_count / head_div), for CPU tests only: the
 // same source the kernels inline, compiled for the host so its integer math can be checked against
 // Python integers without a GPU.  Not part of the product.
-#include "../../kubernetes-simulator_amd/csrc/ks_device.h"
+#include "../../kubernetes-simulator_amd/csrc/ks_query.h"
 
 static ks::NodeV node_of(const int64_t* alloc, const int64_t* run, int64_t i) {
     ks::NodeV v{};

@@ -1,4 +1,4 @@
-// Host build of the placement preview's decision and bookkeeping functions (ks_device.h:
+// Host build of the placement preview's decision and bookkeeping functions (ks_query.h:
 // place_key, place_first_unchanged, place_decide, place_bind, place_cand_delta, topl_insert), for
 // CPU tests only.  ks_host_place runs the whole rounds algorithm of ks_place.hip serially — the
 // shared restatement of place_serial.h with no hook: lists, pod loop, commit, rescan for the

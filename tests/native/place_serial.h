@@ -1,17 +1,17 @@
 // The one serial restatement of the previews' resolver (ks_place.hip: the scan, the merge and
 // resolve_kernel's pod loop), shared by place_host.cpp, drain_host.cpp, removable_host.cpp and
 // scaleup_host.cpp, for CPU tests only: the case a test hands over, the list builder, the pod loop
-// over a changed set, and the rounds around both.  Everything that decides is ks_device.h's own
+// over a changed set, and the rounds around both.  Everything that decides is ks_query.h's own
 // source (place_key, topl_insert, place_first_unchanged, place_decide, place_bind,
 // place_cand_delta).  Not part of the product.
-// The tests' libraries are rebuilt when their .cpp, ks_device.h or ks_carve.h is newer than the
-// library; this header is not in that list, so after an edit here alone touch the four .cpp files
+// The tests' libraries are rebuilt when their .cpp, ks_device.h, ks_query.h or ks_carve.h is newer
+// than the library; this header is not in that list, so after an edit here alone touch the four .cpp files
 // (or remove tests/native/libks_host*.so) before running tests/test_*_host.py.
 #pragma once
 #include <algorithm>
 #include <vector>
 
-#include "../../kubernetes-simulator_amd/csrc/ks_device.h"
+#include "../../kubernetes-simulator_amd/csrc/ks_query.h"
 
 namespace place_serial {
 
@@ -196,7 +196,7 @@ Run decide_pods(const Cluster& s, Lists& l, const int32_t* shape_of, int32_t fir
     return r;
 }
 
-// ks_place_at's rounds (place_rounds, ks_queries.cpp): lists for the shapes still to be placed, the
+// ks_place_at's rounds (place_rounds, ks_previews.cpp): lists for the shapes still to be placed, the
 // loop, the commit, again from the first undecided pod.  info[0] = rounds; stats (null: none)[0]:
 // pods decided from a changed node, [1]: the largest changed set of a round.  Returns 0, -1: a round
 // decided no pod, -2: the changed set overflowed, or the hook's veto.

@@ -1,6 +1,6 @@
-// Host build of the removal scan's host-side pieces (ks_device.h: removable_route,
-// removable_entries_on, removable_segment and the placement functions; ks_carve.h: carve_removable),
-// for CPU tests only.
+// Host build of the removal scan's host-side pieces (ks_query.h: removable_route,
+// removable_entries_on, removable_segment, group_rows and the placement functions; ks_carve.h:
+// carve_removable), for CPU tests only.
 //   ks_host_removable          a serial restatement of removable_resolve_kernel (ks_removable.hip) for
 //                              one candidate, on place_serial.h's list builder and pod loop: the lists
 //                              and counts of the base state with no cordon, the candidate's own entries
@@ -8,6 +8,7 @@
 //                              one set of lists, a veto on the candidate itself;
 //   ks_host_removable_brute    the plain sequential argmax over the nodes other than the candidate;
 //   ks_host_removable_segments ks_removable_at's candidate-aligned segment walk;
+//   ks_host_group_rows         the gather's rows grouped by candidate;
 //   ks_host_removable_route    the split between the batched resolver and the single-drain path;
 //   ks_host_removable_carve    carve_removable run twice, as ks_removable_at does.
 // Not part of the product.
@@ -110,6 +111,18 @@ extern "C" int64_t ks_host_removable_segments(int64_t n_cand, const int32_t* cnt
         start = end;
     }
     return ns;
+}
+
+// ks::group_rows as ks_removable_at and ks_consolidate_at call it: gathered row i runs on node from[i]
+// and its record carries ids[i] (in req[0]); rec_ids[row] is the id of the record grouped to `row`.
+extern "C" int64_t ks_host_group_rows(int32_t m, const int32_t* nodes, int64_t n, int64_t n_ev, const int32_t* from,
+                                      const int64_t* ids, int32_t* evicted, int64_t* first_row, int32_t* perm,
+                                      int64_t* rec_ids) {
+    std::vector<ks::PodRec> fifo(n_ev, ks::PodRec{}), recs(n_ev, ks::PodRec{});
+    for (int64_t i = 0; i < n_ev; i++) fifo[i].req[0] = ids[i];
+    const int64_t bad = ks::group_rows(nodes, m, n, from, fifo.data(), n_ev, evicted, first_row, perm, recs.data());
+    for (int64_t i = 0; i < n_ev; i++) rec_ids[i] = recs[i].req[0];
+    return bad;
 }
 
 extern "C" int ks_host_removable_route(int64_t pods) { return ks::removable_route(pods); }

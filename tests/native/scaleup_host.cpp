@@ -1,4 +1,4 @@
-// Host build of the scale-up preview's helpers (ks_device.h: scaleup_template, scaleup_whole_units,
+// Host build of the scale-up preview's helpers (ks_query.h: scaleup_template, scaleup_whole_units,
 // scaleup_fresh_key, scaleup_count_start, scaleup_takes_fresh, with the placement preview's
 // functions), for CPU tests only.  ks_host_scaleup is a serial restatement of
 // resolve_kernel<true>'s pod loop (ks_place.hip) for one option, on place_serial.h's list builder

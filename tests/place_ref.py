@@ -6,7 +6,7 @@
   it a copy (``copy.deepcopy``).
 * ``fast_place``: the same walk in plain Python integers on the encoded arrays, written from the
   header's semantics and pysim.py's LeastRequested / BalancedAllocation formulas — not from
-  ks_device.h.  It keeps one score vector per shape and re-evaluates only the node a placement
+  ks_query.h.  It keeps one score vector per shape and re-evaluates only the node a placement
   changed, so 1,024 pods on 600 nodes take seconds.
 
 Both return ``dict(node, status, score, candidates, after, info, reused)``: arrays over the pods,

@@ -10,7 +10,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "carve_host.cpp")
 CSRC = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h")]
+DEPS = [SRC, os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h"),
+        os.path.join(CSRC, "ks_query.h")]
 
 
 @functools.lru_cache(maxsize=None)

@@ -47,7 +47,7 @@ def test_constants_agree_with_the_header():
     assert m and [int(x) for x in m.groups()] == [_lib.KS_CONSOLIDATE_BLOCKED, _lib.KS_CONSOLIDATE_REMOVED,
                                                   _lib.KS_CONSOLIDATE_DESTINATION] == [0, 1, 2]
     # the rounds' limit is the device's list length less one
-    with open(os.path.join(os.path.dirname(HEADER), "..", "kubernetes-simulator_amd", "csrc", "ks_device.h")) as f:
+    with open(os.path.join(os.path.dirname(HEADER), "..", "kubernetes-simulator_amd", "csrc", "ks_query.h")) as f:
         dev = f.read()
     m = re.search(r"#define\s+KS_PLACE_L\s+(\d+)", dev)
     assert m and "kConsMaxPods = kPlaceL - 1" in dev and _lib.KS_CONSOLIDATE_MAX_ROUND == int(m.group(1)) - 1

@@ -1,4 +1,4 @@
-"""The consolidation preview's host-side pieces of ks_device.h and ks_carve.h, compiled for the host
+"""The consolidation preview's host-side pieces of ks_query.h and ks_carve.h, compiled for the host
 (tests/native/consolidate_host.cpp): a serial restatement of the rounds — lists of the committed state
 with the removed nodes cordoned, the candidates of a round walked as transactions, the single path —
 which must equal the chain as written, a copy of the cluster restored on every block; the roll-back's
@@ -18,7 +18,8 @@ import test_place_host as tph
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "consolidate_host.cpp")
 CSRC = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc")
-DEPS = [SRC, os.path.join(HERE, "native", "place_serial.h"), os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h")]
+DEPS = [SRC, os.path.join(HERE, "native", "place_serial.h"), os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h"),
+        os.path.join(CSRC, "ks_query.h")]
 PODREC = tdh.PODREC
 RES = np.dtype([("node", np.int32), ("evicted", np.int32), ("outcome", np.int32), ("rows", np.int32),
                 ("block_status", np.int32), ("pad", np.int32), ("first_row", np.int64)])

@@ -1,4 +1,4 @@
-"""The headroom count of ks_device.h (headroom_count / head_div: a float or double estimate with an
+"""The headroom count of ks_query.h (headroom_count / head_div: a float or double estimate with an
 exact step either way, an early clamp test, an exact 64-bit fallback), compiled for the host
 (tests/native/headroom_host.cpp) and checked against Python integers (tests/headroom_ref.py
 count_exact, written from the header's closed form) and against the literal loop that admits copies
@@ -15,7 +15,7 @@ from headroom_ref import NODE_MAX, count_exact
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "headroom_host.cpp")
-DEV_H = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc", "ks_device.h")
+DEV_H = [os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc", h) for h in ("ks_device.h", "ks_query.h")]
 LIB = os.path.join(HERE, "native", "libks_hosthead.so")
 
 TOP = (1 << 59) - 1          # the largest admitted quantity
@@ -24,8 +24,8 @@ LOOP_MAX = 10_000            # the literal loop runs on the cases whose count is
 
 @functools.lru_cache(maxsize=None)
 def host_lib():
-    """ks_device.h's headroom functions compiled for the host (rebuilt when a source is newer)."""
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(SRC), os.path.getmtime(DEV_H)):
+    """ks_query.h's headroom functions compiled for the host (rebuilt when a source is newer)."""
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(f) for f in [SRC, *DEV_H]):
         subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
     L = C.CDLL(LIB)
     p = C.c_void_p

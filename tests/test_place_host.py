@@ -1,4 +1,4 @@
-"""The placement preview's decision and bookkeeping functions of ks_device.h (place_decide,
+"""The placement preview's decision and bookkeeping functions of ks_query.h (place_decide,
 place_first_unchanged, place_bind, place_cand_delta, place_key, topl_insert), compiled for the host
 (tests/native/place_host.cpp).  A serial driver runs the whole rounds algorithm of ks_place.hip — per
 256-node block lists, the topl_insert merge, the resolver's pod loop, the commit, the rescan — and
@@ -17,7 +17,7 @@ import place_ref as pr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "place_host.cpp")
-DEV_H = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc", "ks_device.h")
+DEV_H = [os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc", h) for h in ("ks_device.h", "ks_query.h")]
 REC = np.dtype([("node", np.int32), ("status", np.int32), ("score", np.int64), ("candidates", np.int64)])
 TOP = (1 << 59) - 1
 N_FUZZ = 2400
@@ -25,10 +25,10 @@ N_FUZZ = 2400
 
 @functools.lru_cache(maxsize=None)
 def host_lib(L=None):
-    """ks_device.h's placement functions compiled for the host (rebuilt when a source is newer);
+    """ks_query.h's placement functions compiled for the host (rebuilt when a source is newer);
     L: another snapshot list length than the product's."""
     lib = os.path.join(HERE, "native", "libks_hostplace%s.so" % ("" if L is None else "_l%d" % L))
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(SRC), os.path.getmtime(DEV_H)):
+    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(f) for f in [SRC, *DEV_H]):
         defs = [] if L is None else ["-DKS_PLACE_L=%d" % L]
         subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", *defs, "-o", lib, SRC], check=True)
     lb = C.CDLL(lib)

@@ -36,10 +36,10 @@ def _src(name):
 
 
 def test_the_restated_constants_are_the_sources():
-    dev, place, drain = _src("ks_device.h"), _src("ks_place.hip"), _src("ks_drain.hip")
-    assert int(re.search(r"#define\s+KS_PLACE_L\s+(\d+)", dev).group(1)) == L == 32
+    dev, qry, place, drain = _src("ks_device.h"), _src("ks_query.h"), _src("ks_place.hip"), _src("ks_drain.hip")
+    assert int(re.search(r"#define\s+KS_PLACE_L\s+(\d+)", qry).group(1)) == L == 32
     assert int(re.search(r"constexpr int kPBlk = (\d+);", place).group(1)) == BLK
-    assert int(re.search(r"constexpr int kDrainBlk = (\d+);", dev).group(1)) == BLK
+    assert int(re.search(r"constexpr int kDrainBlk = (\d+);", qry).group(1)) == BLK
     assert "b += kWave" in place and re.search(r"constexpr int kWave = (\d+);", dev).group(1) == str(WAVE)
     assert "base += kDrainBlk" in drain, "the gather's scan no longer walks chunks of kDrainBlk counts"
     assert [wc.WIDE[c][0] for c in FEEDS_CASES] == [16_384, 16_385, 16_385, 32_770]

@@ -43,7 +43,7 @@ def test_constants_agree_with_the_header():
         m = re.search(r"#define\s+%s\s+\(?(-?\d+)\)?" % name, text)
         assert m and int(m.group(1)) == getattr(_lib, name), name
     # the batched kernel's limit is the device's list length less one
-    with open(os.path.join(os.path.dirname(HEADER), "..", "kubernetes-simulator_amd", "csrc", "ks_device.h")) as f:
+    with open(os.path.join(os.path.dirname(HEADER), "..", "kubernetes-simulator_amd", "csrc", "ks_query.h")) as f:
         dev = f.read()
     m = re.search(r"#define\s+KS_PLACE_L\s+(\d+)", dev)
     assert m and "kRemovableMaxPods = kPlaceL - 1" in dev and _lib.KS_REMOVABLE_MAX_BATCHED == int(m.group(1)) - 1

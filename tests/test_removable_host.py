@@ -1,4 +1,4 @@
-"""The removal scan's host-side pieces of ks_device.h and ks_carve.h, compiled for the host
+"""The removal scan's host-side pieces of ks_query.h and ks_carve.h, compiled for the host
 (tests/native/removable_host.cpp): a serial restatement of the per-candidate resolver — shared base
 lists with no cordon, the candidate's own entries flagged from the start, its candidate counts
 corrected — which must equal the plain sequential argmax over the other nodes; the split between the
@@ -18,7 +18,8 @@ import test_place_host as tph
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "removable_host.cpp")
 CSRC = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h")]
+DEPS = [SRC, os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h"),
+        os.path.join(CSRC, "ks_query.h")]
 PODREC = tdh.PODREC
 MAX_SHAPES = 64
 
@@ -36,6 +37,8 @@ def host_lib():
     lb.ks_host_removable.restype = lb.ks_host_removable_brute.restype = C.c_int
     lb.ks_host_removable_segments.argtypes = [C.c_int64, p, p, p, p, p, p, C.c_int64, p, p, p, p]
     lb.ks_host_removable_segments.restype = C.c_int64
+    lb.ks_host_group_rows.argtypes = [C.c_int32, p, C.c_int64, C.c_int64, p, p, p, p, p, p]
+    lb.ks_host_group_rows.restype = C.c_int64
     lb.ks_host_removable_route.argtypes = [C.c_int64]
     lb.ks_host_removable_route.restype = C.c_int
     lb.ks_host_removable_limits.argtypes = [p]
@@ -257,6 +260,60 @@ def test_segment_boundaries_at_the_sixty_fifth_shape():
     assert e.tolist() == [10] and m.tolist() == [31]
     check_segments([], [])
     check_segments([1], [7])
+
+
+# ---- the gather's rows grouped by candidate ------------------------------------------------------
+def group_rows(nodes, n, frm):
+    nodes, frm = np.asarray(nodes, np.int32), np.asarray(frm, np.int32)
+    m, n_ev = len(nodes), len(frm)
+    ids = (1000 + 7 * np.arange(n_ev)).astype(np.int64)
+    evicted, first_row = np.full(m, -9, np.int32), np.full(m, -9, np.int64)
+    perm, rec_ids = np.full(max(n_ev, 1), -9, np.int32), np.full(max(n_ev, 1), -9, np.int64)
+    bad = host_lib().ks_host_group_rows(m, _p(nodes), n, n_ev, _p(frm), _p(ids), _p(evicted), _p(first_row), _p(perm), _p(rec_ids))
+    return bad, evicted, first_row, perm[:n_ev], rec_ids[:n_ev], ids
+
+
+def check_group_rows(nodes, n, frm):
+    """the expected grouping in numpy: a stable sort of the rows on their candidate's position"""
+    nodes, frm = np.asarray(nodes, np.int64), np.asarray(frm, np.int64)
+    m = len(nodes)
+    pos = np.full(n, -1, np.int64)
+    pos[nodes] = np.arange(m)
+    assert (pos[frm] >= 0).all()
+    want_perm = np.argsort(pos[frm], kind="stable")
+    want_evicted = np.bincount(pos[frm], minlength=m)
+    want_first = np.cumsum(want_evicted) - want_evicted  # the exclusive prefix sum
+    bad, evicted, first_row, perm, rec_ids, ids = group_rows(nodes, n, frm)
+    assert bad == -1
+    assert evicted.tolist() == want_evicted.tolist() and first_row.tolist() == want_first.tolist()
+    assert perm.tolist() == want_perm.tolist() and rec_ids.tolist() == ids[want_perm].tolist()
+    return evicted.tolist(), first_row.tolist(), perm.tolist()
+
+
+def test_group_rows_is_a_stable_sort_on_the_candidates_position():
+    # one candidate: the rows as gathered
+    assert check_group_rows([5], 9, [5, 5, 5]) == ([3], [0], [0, 1, 2])
+    assert check_group_rows([0], 1, [0]) == ([1], [0], [0])
+    # candidates with no row at the front, in the middle and at the end: empty ranges at the next row
+    ev, first, _ = check_group_rows([7, 2, 4, 9, 0], 10, [2, 9, 2, 9, 9])
+    assert ev == [0, 2, 0, 3, 0] and first == [0, 0, 2, 2, 5]
+    # the candidates in the reverse of node order: the rows follow the caller's order, not the nodes'
+    ev, first, perm = check_group_rows([8, 6, 3, 1], 9, [1, 3, 3, 6, 8, 8])
+    assert ev == [2, 1, 2, 1] and first == [0, 2, 3, 5] and perm == [4, 5, 3, 1, 2, 0]
+    # two candidates whose rows interleave: FIFO within each
+    ev, first, perm = check_group_rows([4, 1], 5, [1, 4, 1, 4, 4, 1])
+    assert ev == [3, 3] and first == [0, 3] and perm == [1, 3, 4, 0, 2, 5]
+    # no row at all
+    assert check_group_rows([3, 0], 4, []) == ([0, 0], [0, 0], [])
+    # every node a candidate, rows in a fixed shuffle
+    rng = np.random.default_rng(20261021)
+    check_group_rows(rng.permutation(300), 300, rng.integers(300, size=5000))
+    # a row on no candidate: the first such row's index
+    assert group_rows([2, 5], 8, [2, 5, 3, 5])[0] == 2      # a node that is no candidate
+    assert group_rows([2, 5], 8, [2, 5, 5, 4, 3])[0] == 3   # ... the first of two
+    assert group_rows([2, 5], 8, [-1, 5])[0] == 0           # below the node range
+    assert group_rows([2, 5], 8, [2, 5, 2, 8])[0] == 3      # node n itself
+    assert group_rows([0], 1, [1])[0] == 0
 
 
 def test_fuzzed_candidate_sequences_tile_at_candidate_boundaries():

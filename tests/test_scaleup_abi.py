@@ -45,7 +45,7 @@ def test_constants_agree_with_the_header():
     for name in ("KS_SCALEUP_MAX_OPTIONS", "KS_SCALEUP_MAX_NODES", "KS_SCALEUP_INFO", "KS_PLACE_MAX_PODS", "KS_ABI_VERSION"):
         m = re.search(r"#define\s+%s\s+\(?(-?\d+)\)?" % name, text)
         assert m and int(m.group(1)) == getattr(_lib, name), name
-    with open(os.path.join(os.path.dirname(HEADER), "..", "kubernetes-simulator_amd", "csrc", "ks_device.h")) as f:
+    with open(os.path.join(os.path.dirname(HEADER), "..", "kubernetes-simulator_amd", "csrc", "ks_query.h")) as f:
         dev = f.read()
     assert "kScaleMaxOptions = 64;" in dev and "kScaleMaxNodes = 65536;" in dev
 

@@ -1,4 +1,4 @@
-"""The scale-up preview's helpers of ks_device.h (scaleup_fresh_key, scaleup_count_start,
+"""The scale-up preview's helpers of ks_query.h (scaleup_fresh_key, scaleup_count_start,
 scaleup_takes_fresh, scaleup_template, scaleup_whole_units) compiled for the host
 (tests/native/scaleup_host.cpp).  A serial restatement of scaleup_resolve_kernel's pod loop — shared
 snapshot lists over the real nodes, the fresh appended node standing for every unchanged one, no
@@ -19,7 +19,8 @@ import test_place_host as tph
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "scaleup_host.cpp")
 CSRC = os.path.join(HERE, "..", "kubernetes-simulator_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h")]
+DEPS = [SRC, os.path.join(CSRC, "ks_carve.h"), os.path.join(CSRC, "ks_device.h"),
+        os.path.join(CSRC, "ks_query.h")]
 REC = tph.REC
 RES = ("ok", "over_capacity", "not_found", "on_new", "nodes_used", "first_unplaced", "path", "pad")
 N_FUZZ = 1500
