@@ -661,8 +661,7 @@ ks_status ks_group_step(ks_group* g, int64_t ticks, ks_bind* out, int64_t cap, i
  * rescanned / reused from the previous batch (cumulative, chunk resolver), [8] the binds of the last
  * batched ks_step that the host had copied back and finished before the step's last wait (the early
  * read-back; 0 when the step took none) and [9] those of them that came back below a snapshot of the
- * start counter, on the copy stream, [16..31] resolver phase cycle
- * sums in a -DKS_STAMPS diagnostic build (tests/dev/diag_resolve.py). */
+ * start counter, on the copy stream. */
 ks_status ks_debug_counters(ks_engine* eng, int64_t* out32);
 /* Between-step invariants of a chunk-resolver engine (diagnostics / regression tests): out4[0] =
  * nodes whose candidate-slot or first-entry mark is set (must be 0: every batch's commit resets the

@@ -4,7 +4,7 @@
 // The reference binds one pod per tick in FIFO order (kubesim/kubesim.go:105-121, 143-166): pod i
 // takes the argmax of its key over every node, on the state that the binds of the pods before it
 // (admitted per kubesim/node/node.go:36-60) and the expiries due by its tick leave.  After the scan
-// (ks_kernels.hip) every pod of the batch has per-block top-L lists; this file turns them into
+// (ks_scan.hip) every pod of the batch has per-block top-L lists; this file turns them into
 // what the resolver needs, in two launches around the scan:
 //
 //   window_prep_kernel   (before the scan) the expiries due before the batch's first pod, applied to
@@ -271,7 +271,7 @@ __device__ __forceinline__ void merge_final_stage(const uint64_t (*wl)[kLL], int
 // Every launch clears the pods' bitmaps and thresholds for the next scan.
 //
 // The merge is the score-class merge of ks_device.h (where its exactness argument stands), not the
-// merge kernel's extraction rounds (ks_kernels.hip: kLL rounds of wave max + ballot per wave, kLL
+// merge kernel's extraction rounds (ks_scan.hip: kLL rounds of wave max + ballot per wave, kLL
 // more over the wave results).  Each thread folds a contiguous range of the lists
 // (merge_list_range) with topl_insert, so its sorted top[] covers a contiguous node range and
 // lane order is node order across the workgroup; a wave then ranks one whole score class per step

@@ -34,7 +34,7 @@ constexpr int kB = kWinMaxB;  // pods per batch
 constexpr int kC = 64;          // pods per chunk: one lane each
 constexpr int kR = kChR;        // static candidates kept per pod
 constexpr int kCid = 1024;      // candidate ids per batch (the batch's candidate slots)
-constexpr int kMaxPGScan = 32;  // pods per scan group (the host's PG bound, ks_kernels.hip kMaxPG)
+constexpr int kMaxPGScan = 32;  // pods per scan group (the host's PG bound, ks_device.h kMaxPG)
 constexpr int kCidSlots = kCid - kR;  // claim-order cids: slots that are cids; the rest: pod 0's private cids
 constexpr int kSlots = kWinSlots;
 constexpr int kSeg = 5;         // stored state segments per replayed node within a chunk

@@ -30,6 +30,13 @@ constexpr int kTopL = 8;  // exact top-L snapshot candidates kept per pod
 #endif
 constexpr int kTopLOverlap = KS_OVERLAP_LIST;
 static_assert(kTopLOverlap >= kTopL && kTopLOverlap <= 16 && kTopLOverlap % 2 == 0, "overlap list length");
+constexpr int kL = kTopL;                // candidate list length per pod
+constexpr int kScanWaves = 4;            // 256-thread scan workgroups, one 256-node block each
+constexpr int kBlockNodes = kScanWaves * kWave;
+#ifndef KS_MAX_PG
+#define KS_MAX_PG 32
+#endif
+constexpr int kMaxPG = KS_MAX_PG;        // pods per scan workgroup (LDS key table rows)
 
 enum : uint32_t { kFilterFit = 1, kFilterTaint = 2, kFilterSelector = 4 };
 
@@ -669,6 +676,10 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return ((uint64_t)mh << 32) | ml;
 }
 
+__device__ __forceinline__ int popc_below(uint64_t mask, int lane) {
+    return __popcll(mask & ((1ull << lane) - 1ull));
+}
+
 // Wave-wide inclusive prefix sum in the same DPP moves: row_shr 1/2/4/8 scans each 16-lane row,
 // row_bcast 15/31 adds the rows before (a lane without a source adds 0).  Lane 63 holds the total.
 __device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v) {
@@ -808,7 +819,7 @@ struct WinWS {
     int32_t e_off[kWinSlots + 1];         // E node k < n_es: its slots e_slot[e_off[k] .. e_off[k+1]) ascending
     int32_t e_slot[kWinSlots];
     // E node k's record after the window's head (put_rec12), staged by the first workgroups of the
-    // scan launch before merge_cl (ks_kernels.hip scan_kernel): each merge_cl workgroup reads three
+    // scan launch before merge_cl (ks_scan.hip scan_kernel): each merge_cl workgroup reads three
     // contiguous 16-byte words per E node instead of gathering ten scattered fields (unused on the
     // two-launch chain, which has no such launch: EngineArgs::two_launch)
     uint32_t e_rec[kEMax][12];
@@ -942,7 +953,8 @@ __host__ __device__ __forceinline__ uint64_t* lthr_of(const EngineArgs& a, int s
     return a.lthr + ((int64_t)set * kThrCopies + copy) * a.B + b;
 }
 
-// Launchers and limits (defined in ks_kernels.hip).  The batch launchers take a device array of
+// Launchers and limits, each defined beside its kernel (the scan family: ks_scan.hip; node-table
+// upkeep and the api shims: ks_table.hip; the usage queries: ks_usage.hip).  The batch launchers take a device array of
 // S engines' arguments (S = 1 for ks_step, the group's scenarios for ks_group_step).
 int max_batch_pods();
 int max_pods_per_scan_wg();
@@ -1001,7 +1013,7 @@ struct MergeOpts {
 };
 hipError_t launch_merge(const EngineArgs* d, int S, int B, const ListSet& in, uint64_t* out, hipStream_t st,
                         const MergeOpts& o = {});
-// the role-split resolver (ks_kernels.hip): batches of up to max_batch_pods() pods, any cluster
+// the role-split resolver (ks_rolesplit.hip): batches of up to max_batch_pods() pods, any cluster
 hipError_t launch_resolve(const EngineArgs* d, int S, int mode, hipStream_t st);
 // the register-table resolver (ks_resolve.hip): batches of <= small_resolver_max_batch() pods of
 // clusters of <= small_resolver_max_nodes() nodes, four per CU
@@ -1156,7 +1168,7 @@ __device__ __forceinline__ void evcase_prune(const EvalCases& e, int col, int64_
     e.tmax[(int64_t)col * e.n + i] = prune_tmax(e.c, f, (float)p.req[0], (float)p.req[1]);
     e.live[(int64_t)col * e.n + i] = (uint32_t)f.live;
 }
-hipError_t launch_evtest_nodev(const EvalCases& e, hipStream_t st);  // ks_kernels.hip
+hipError_t launch_evtest_nodev(const EvalCases& e, hipStream_t st);  // ks_selftest.hip
 hipError_t launch_evtest_rec12(const EvalCases& e, hipStream_t st);  // ks_cand.hip
 hipError_t launch_evtest_ns32(const EvalCases& e, hipStream_t st);   // ks_chunk.hip
 hipError_t launch_evtest_conv(const EvalCases& e, hipStream_t st);   // ks_resolve.hip

@@ -19,7 +19,7 @@ namespace ks_host {
 #endif
 constexpr int kOverlapMaxBlocks = KS_OVERLAP_MAX_BLOCKS;
 
-// Resolvers, the same binds: the role-split resolve_kernel (16 waves, ks_kernels.hip) takes any
+// Resolvers, the same binds: the role-split resolve_kernel (16 waves, ks_rolesplit.hip) takes any
 // engine; the register-table resolver (4 waves, ks_resolve.hip) is lighter — four per CU, so a
 // what-if group's resolvers run side by side (C4 2.29e11 against 2.16e11 evals/s with the
 // role-split kernel's half-size class); the chunk resolver (ks_chunk.hip) takes one

@@ -2,7 +2,7 @@
 //
 // A pod's placement depends on every bind before it (kubesim/kubesim.go:105-121, one pod per
 // tick), so this part of the batch is sequential.  The exactness argument is the scan's (see
-// ks_kernels.hip): a node's key for pod i can differ from the batch snapshot only if a bind or an
+// ks_scan.hip): a node's key for pod i can differ from the batch snapshot only if a bind or an
 // expiry of this batch touched it.  Touched nodes are table entries, re-evaluated exactly for
 // every pod; the best untouched node is the first untouched entry of the pod's snapshot top-L
 // list (every node outside the list scores below every list entry).  winner = max of the two.
@@ -29,7 +29,6 @@
 namespace ks {
 namespace {
 
-constexpr int kL = kTopL;
 constexpr int kEntNone = 1023;  // ikey entry field of an untouched (list) node
 constexpr int kRecDw = 20;      // a node record in dwords: 10 int64 fields, NodeV order
 

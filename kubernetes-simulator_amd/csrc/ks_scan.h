@@ -1,6 +1,6 @@
 // ks_scan.h — one item of the scan (gfx950): a 256-node block against a group of <= PG pods.
 //
-// Shared by the scan kernel (ks_kernels.hip: one item per 256-thread workgroup) and the chunk
+// Shared by the scan kernel (ks_scan.hip: one item per 256-thread workgroup) and the chunk
 // kernel's fused form (ks_chunk.hip: 512-thread workgroups beside the resolver, two items at a
 // time, one per half).  The snapshot key of every (pod, node) pair — fused Filter + Score,
 // kubesim/kubesim.go:168-215 restated in ks_device.h — goes into an LDS table of total+1 words,
@@ -13,13 +13,10 @@ namespace scn {
 
 constexpr int kWaves = 4;               // a group of four waves: one node per thread
 constexpr int kNodes = kWaves * kWave;  // 256
-constexpr int kL = kTopL;
 #ifndef KS_SCAN_UNROLL
 #define KS_SCAN_UNROLL 4
 #endif
 constexpr int kUnroll = KS_SCAN_UNROLL;  // pods evaluated together per loop step
-
-__device__ __forceinline__ int popc_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
 
 // Item `it` (= node block * groups + pod group) of the batch [start, start + nb) on the 256
 // threads lt = 0..255 of one group; kv: the group's [PG][256] table.  has == false: this group has

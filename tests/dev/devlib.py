@@ -1,5 +1,5 @@
 """Dev tools (not tests): where diagnostic engine builds live.  `make -C kubernetes-simulator_amd/csrc
-<stamps|chunkdiag|variant|abl>` writes them to build/diag/ (git-ignored, outside the package);
+<chunkdiag|variant>` writes them to build/diag/ (git-ignored, outside the package);
 the product library stays kubernetes-simulator_amd/kubesim_amd/libks_engine.so."""
 import os
 

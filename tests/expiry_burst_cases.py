@@ -8,7 +8,7 @@ The engine's expiry code has fixed-capacity tables, each with its own overflow p
                                                             ks_engine.cpp flush_expiries)
     128 / 129      in a batch's window                      RSmall::kMaxExp (ks_resolve.hip)
     256 / 257      attached to a batch's first pod          expire_head_kernel's 256 threads
-    512 / 513      in a window                              kWinSlots (ks_prep.h fits_win), RBig::kMaxExp
+    512 / 513      in a window                              kWinSlots (ks_prep.h fits_win), ks_rolesplit.hip kMaxExp
     1,024 / 1,025  head expiries                            window_prep_kernel's kPrepThreads
     2,048          e_cnt + head + touched (+ previous E)    kEMax (EngineArgs::e_lim)
 
@@ -34,8 +34,8 @@ from kubesim_amd import tracegen
 # the table's edges, restated (tests/test_expiry_burst_cases.py compares them with the sources)
 TICK_MAX_EXP = 16      # ks_device.h kTickMaxExp
 SMALL_MAX_EXP = 128    # ks_resolve.hip RSmall::kMaxExp = kTMax - kMaxB = 256 - 128
-HEAD_THREADS = 256     # ks_kernels.hip expire_head_kernel's workgroup
-WIN_SLOTS = 512        # ks_device.h kWinSlots; ks_kernels.hip RBig::kMaxExp = 768 - 256
+HEAD_THREADS = 256     # ks_scan.hip expire_head_kernel's workgroup
+WIN_SLOTS = 512        # ks_device.h kWinSlots; ks_rolesplit.hip kMaxExp = 768 - 256
 BIG_TMAX, BIG_MAX_B = 768, 256
 PREP_THREADS = 1024    # ks_cand.hip kPrepThreads
 E_MAX = 2048           # ks_device.h kEMax

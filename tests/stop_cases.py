@@ -42,7 +42,7 @@ TOP_L = 8          # ks_device.h kTopL: exact snapshot candidates kept per pod
 CHR = 20           # ks_device.h KS_CHR: static candidates the chunk resolver keeps per pod
 KC = 64            # ks_chunk.hip kC: pods per chunk
 B_CHUNK = 192      # ks_engine.cpp kChunkBatch: the chunk-resolver engines' batch
-B_ONE_POD = 256    # RBig's batch (ks_device.h kWinMaxB)
+B_ONE_POD = 256    # the role-split resolver's batch (ks_device.h kWinMaxB)
 B_SMALL = 128      # RSmall::kMaxB
 BLOCK_NODES = 256  # ks::block_nodes(): nodes per scan block
 

@@ -127,3 +127,18 @@ def test_library_built_from_these_sources():
     assert want is not None and len(want) == 16
     assert _lib.load().ks_build_id().decode() == want
     assert _lib.load_run().ks_run_build_id().decode() == want
+
+
+def test_provenance_hash_covers_every_source():
+    """The hash only proves what it covers: a source file that a split adds and the Makefile's HASHED
+    line forgets would leave a stale library that loads without complaint.  Every source in csrc/ is
+    on that line, so is everything the engine is compiled from (SRCS, HDRS), and every name on it
+    exists."""
+    mk = open(os.path.join(_lib.CSRC, "Makefile")).read().split("\n")
+    names = lambda var: next(x for x in mk if x.startswith(var + " =")).split("=", 1)[1].split()
+    hashed = names("HASHED")
+    assert len(hashed) == len(set(hashed))
+    on_disk = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith((".hip", ".cpp", ".h")))
+    assert on_disk and not [f for f in on_disk if f not in hashed]
+    assert not [n for n in names("SRCS") + names("HDRS") if n not in hashed]
+    assert not [n for n in hashed if not os.path.isfile(os.path.join(_lib.CSRC, n))]

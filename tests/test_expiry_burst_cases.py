@@ -191,7 +191,8 @@ def test_pending_bursts_end_with_nothing_queued(name, sizes):
 
 # ---- the edges, restated ---------------------------------------------------------------------------
 def test_restated_edges_agree_with_the_sources():
-    dev, res, ker, cand = _src("ks_device.h"), _src("ks_resolve.hip"), _src("ks_kernels.hip"), _src("ks_cand.hip")
+    dev, res, cand = _src("ks_device.h"), _src("ks_resolve.hip"), _src("ks_cand.hip")
+    role, scan = _src("ks_rolesplit.hip"), _src("ks_scan.hip")
     const = lambda text, name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
     assert const(dev, "kTickMaxExp") == ec.TICK_MAX_EXP == 16
     assert const(dev, "kWinSlots") == ec.WIN_SLOTS == 512
@@ -202,14 +203,13 @@ def test_restated_edges_agree_with_the_sources():
     m = re.search(r"using RSmall = Cfg4<\d+, \d+, (\d+), (\d+), \d+, \d+>;", res)
     assert m and "kMaxExp = kTMax - MAXB" in res
     assert int(m.group(1)) - int(m.group(2)) == ec.SMALL_MAX_EXP == 128 and int(m.group(2)) == 128
-    # RBig = RCfg<THREADS, TMAX, HASH_LOG2, MAXB, ...>, kMaxExp = TMAX - MAXB
-    m = re.search(r"using RBig = RCfg<\w+, (\d+), \d+, (\d+), \d+>;", ker)
-    assert m and "kMaxExp = TMAX - MAXB" in ker
-    assert (int(m.group(1)), int(m.group(2))) == (ec.BIG_TMAX, ec.BIG_MAX_B) == (768, 256)
+    # the role-split resolver: kTMax entries, kMaxBatchR pods, kMaxExp = kTMax - kMaxBatchR
+    assert "constexpr int kMaxExp = kTMax - kMaxBatchR;" in role
+    assert (const(role, "kTMax"), const(role, "kMaxBatchR")) == (ec.BIG_TMAX, ec.BIG_MAX_B) == (768, 256)
     assert ec.BIG_TMAX - ec.BIG_MAX_B == ec.WIN_SLOTS
     # expire_head_kernel: its launch bound and its launch
-    assert re.search(r"__launch_bounds__\((\d+)\) void expire_head_kernel", ker).group(1) == str(ec.HEAD_THREADS)
-    assert re.search(r"expire_head_kernel, dim3\(S\), dim3\((\d+)\)", ker).group(1) == str(ec.HEAD_THREADS)
+    assert re.search(r"__launch_bounds__\((\d+)\) void expire_head_kernel", scan).group(1) == str(ec.HEAD_THREADS)
+    assert re.search(r"expire_head_kernel, dim3\(S\), dim3\((\d+)\)", scan).group(1) == str(ec.HEAD_THREADS)
     # the uses the table names
     assert "myoff - e_base <= kWinSlots" in _src("ks_prep.h")
     assert "a.n_exp == ks::kTickMaxExp" in _src("ks_step.cpp")

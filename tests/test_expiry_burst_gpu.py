@@ -36,7 +36,7 @@ ENGINES = {
     "default": (0, 0, None, True),                     # chunk resolver, fused overlap, two-launch chain
     "plain": (0, CHUNK | NO_OVERLAP, None, True),      # the four-launch chain
     "pruned": (0, CHUNK | PRUNED, None, True),
-    "one_pod_256": (256, ONE_POD, None, False),        # RBig
+    "one_pod_256": (256, ONE_POD, None, False),        # the role-split resolver
     "vshards3": (0, 0, (1, 0, None, 3), True),         # the sharded overlap with its conditional scan
 }
 RESCANS = ("default", "vshards3")   # chains whose window prep counts a rescan when E overflows

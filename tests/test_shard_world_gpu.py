@@ -128,7 +128,7 @@ def test_c5_whole_trace_eight_ranks_deployment_layout_match_oracle_golden():
 def test_ranks_without_scan_blocks_match_oracle():
     """A chunk-resolver cluster smaller than its shard layout: 600 nodes = 3 scan blocks
     over 4 ranks, so rank 0 scans nothing and its scan launch only stages the batch's E records for
-    merge_cl (ks_kernels.hip scan_kernel).  Every rank bind-for-bind against the oracle, up to the
+    merge_cl (ks_scan.hip scan_kernel).  Every rank bind-for-bind against the oracle, up to the
     same aborting error (a 600-node cluster leaves some selector pairs on no node: NotFound,
     kubesim/kubesim.go:217-220, exactly where the oracle stops)."""
     from kubesim_amd.engine import KsError

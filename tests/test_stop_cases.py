@@ -241,7 +241,7 @@ def test_restated_constants_agree_with_the_sources():
     assert sc.BLOCK_NODES == shard.BLOCK_NODES == gc.BLOCK_NODES == 256
     # the stop's four deciders and the host's unwinding, where the cases' docstrings say they are
     assert "stop_code" in chunk and "cend" in chunk
-    assert "err_code" in _src("ks_kernels.hip") and "err_pod" in _src("ks_kernels.hip")
+    assert "err_code" in _src("ks_rolesplit.hip") and "err_pod" in _src("ks_rolesplit.hip")
     assert 'node \\"\\" not found (pod %lld, tick %lld)' in _src("ks_step.cpp")
     assert "pod %lld: invalid pod key or simSpec (tick %lld)" in _src("ks_step.cpp")
     from kubesim_amd import _lib

@@ -3,7 +3,7 @@ inside the batch (tests/stop_cases.py builds the traces; tests/test_stop_cases.p
 alone that each produces its event).
 
 The stop is decided in four places — the chunk resolver (ks_chunk.hip), the small-cluster resolver
-(ks_resolve.hip), the role-split one-pod resolver (ks_kernels.hip) and the per-tick kernel
+(ks_resolve.hip), the role-split one-pod resolver (ks_rolesplit.hip) and the per-tick kernel
 (ks_tick.hip) — and unwound on the host by ks_step.cpp (the speculative scan of the next batch, the
 early read-back, a sharded run's exchange).  A gpu is the scarce resource: the pods before X take
 the last slots inside X's batch (X has candidates in the batch-start snapshot and must still reach
