@@ -691,6 +691,81 @@ func (e *Engine) ConsolidateAt(t int64, nodes []int32, rows, after bool) (*Conso
 	return r, status(e, rc)
 }
 
+// Gang admission preview constants (include/ks_engine.h): the most gangs, pods and shapes per
+// GangAt call, the status of a pod no attempt reached, a gang's outcomes, the words of Gangs.Info.
+const (
+	GangMaxGangs  = 65536
+	GangMaxPods   = 65536
+	GangMaxShapes = 4096
+	GangNotTried  = -2
+	GangBlocked   = 0
+	GangAdmitted  = 1
+	GangSkipped   = 2
+	GangInfo      = 6
+)
+
+// Gang is one gang's answer (ks_gang, 32 bytes): its pods (rows [First, First+Size) of Gangs.Pods),
+// its outcome, the pods its attempt handled (Size when admitted, up to and including the deciding
+// pod when blocked, 0 when skipped), their statuses counted, and the deciding pod's status.
+type Gang struct {
+	First, Size                int32
+	Outcome, Tried             int32
+	Ok, OverCapacity, NotFound int32
+	BlockStatus                int32
+}
+
+// Gangs is the result of GangAt: one Gang per gang in the caller's order, Pods (when asked for) one
+// Placement per pod at its own index (an untried pod has status GangNotTried), After (when asked
+// for) [Nodes()][4] the final private state, and Info = rounds of the device algorithm, admitted,
+// blocked, skipped, gangs decided through the single path, Ok pods of admitted gangs.
+type Gangs struct {
+	Gangs []Gang
+	Pods  []Placement
+	After []int64
+	Info  [GangInfo]int64
+}
+
+// GangAt says which pod groups of a queue would be admitted at tick t <= Tick(), in the given order
+// on one private state, and where their pods would be bound (ks_gang_at).  Pod j has shape
+// shapeOf[j] of s (up to GangMaxShapes shapes); gang g is pods first[g] .. first[g+1]-1, with
+// first[0] = 0 and first[len(first)-1] = len(shapeOf).  A gang's pods go through scheduleOne
+// (kubesim/kubesim.go:143-225) one after another as PlaceAt would handle them; the attempt ends once
+// more than size - minOk[g] of them were not bound Ok (nil minOk: all-or-nothing).  A gang with at
+// least minOk[g] pods bound Ok is admitted and its placements stay for the later gangs; any other is
+// blocked and everything is as it was before it; with strict every gang after the first blocked one
+// is skipped.  No engine state changes.
+func (e *Engine) GangAt(t int64, s *Shapes, shapeOf, first, minOk []int32, strict, rows, after bool) (*Gangs, error) {
+	defer runtime.KeepAlive(e) // e.h must outlive the C call (the finalizer runs ks_destroy)
+	ns := len(s.KeyMask)
+	if ns < 1 || ns > GangMaxShapes || len(s.Req) != 3*ns || len(s.Tol) != ns || len(s.Sel) != ns {
+		return nil, strongerrors.InvalidArgument(errors.New("gang: 1..4096 shapes with consistent array lengths"))
+	}
+	k, m := len(shapeOf), len(first)-1
+	if k < 1 || k > GangMaxPods || m < 1 || m > GangMaxGangs || (minOk != nil && len(minOk) != m) {
+		return nil, strongerrors.InvalidArgument(errors.New("gang: 1..65536 pods in 1..65536 gangs, one minOk per gang"))
+	}
+	r := &Gangs{Gangs: make([]Gang, m)}
+	var pods *C.ks_placement
+	if rows {
+		r.Pods = make([]Placement, k)
+		pods = (*C.ks_placement)(unsafe.Pointer(&r.Pods[0]))
+	}
+	if after {
+		r.After = make([]int64, 4*e.n+1)
+	}
+	var flags C.uint32_t
+	if strict {
+		flags = C.KS_GANG_STRICT
+	}
+	err := status(e, C.ks_gang_at(e.h, C.int64_t(t), C.int32_t(ns), i64p(s.Req), u8p(s.KeyMask), u64p(s.Tol), u64p(s.Sel),
+		C.int32_t(k), i32p(shapeOf), C.int32_t(m), i32p(first), i32p(minOk), flags,
+		(*C.ks_gang)(unsafe.Pointer(&r.Gangs[0])), pods, i64p(r.After), (*C.int64_t)(unsafe.Pointer(&r.Info[0]))))
+	if after {
+		r.After = r.After[:4*e.n]
+	}
+	return r, err
+}
+
 // Scale-up preview constants (include/ks_engine.h): the most options per ScaleUpAt call, the most
 // nodes an option may append, the words of ScaleUps.Info.
 const (

@@ -35,6 +35,8 @@
  *                                 which of them could be taken out
  *   ks_consolidate_at ........... the same candidates handled one after another, as a scale-down pass
  *                                 does: a removal's placements stay, a failed attempt is rolled back
+ *   ks_gang_at .................. ks_place_at's pods in groups (gangs) admitted all-or-nothing, or from
+ *                                 min_ok members up, in queue order: a blocked gang is rolled back
  *   ks_scale_up_at .............. ks_place_at's answer on the cluster plus up to max_nodes empty nodes
  *                                 of a node-group template, for each of G templates on its own
  *   ks_pod_status ............... Pod.BuildStatus phase / times (kubesim/pod/pod.go:78-167)
@@ -530,6 +532,62 @@ ks_status ks_consolidate_at(ks_engine* eng, int64_t t, int32_t m, const int32_t*
                             ks_consolidation* out /* [m] */, ks_eviction* rows_out /* [cap] or NULL */,
                             int64_t cap, int64_t* n_evicted, int64_t* n_rows,
                             int64_t* after_out /* [n][4] or NULL */, int64_t* info_out /* [KS_CONSOLIDATE_INFO] or NULL */);
+
+/* Gang admission preview: which of m pod groups (gangs: the PodGroup minMember of coscheduling,
+ * all-or-nothing admission) a queue would admit when it handles them one after another, and where
+ * their pods would be bound, at any past tick ("at tick t" as above).  No engine state changes.
+ *
+ * Shapes (n_shapes, req, keymask, tol, sel) and the k pods' shape_of are ks_place_at's; shape_of is
+ * required, and a call takes up to KS_GANG_MAX_SHAPES shapes and KS_GANG_MAX_PODS pods.  Gang g is pods
+ * first[g] .. first[g + 1] - 1: first[0] = 0, first is non-decreasing, first[m] = k; an empty gang is
+ * allowed.  min_ok[g] lies in 0 .. size (NULL: size, all-or-nothing).  The call keeps one private
+ * copy of ks_requested_at(t) and handles the gangs in the caller's order.  For gang g:
+ *   - its pods go one after another to scheduleOne (kubesim/kubesim.go:143-225,
+ *     kubesim/node/node.go:36-60) on the private state, exactly as ks_place_at would handle them: filter
+ *     mode, filters, scorers, score, candidates and the lowest-index tie-break are ks_place_at's.  A pod
+ *     bound Ok adds to its node; a pod bound OverCapacity or not found (KS_PLACE_NOT_FOUND) changes
+ *     nothing and the attempt goes on.  The attempt ends as soon as the pods not bound Ok number more
+ *     than size - min_ok; later pods of g are not tried, and that pod's status is block_status.
+ *   - at least min_ok pods bound Ok at its end (also an empty gang, also min_ok = 0): KS_GANG_ADMITTED.
+ *     Every Ok placement stays for the later gangs.
+ *   - otherwise KS_GANG_BLOCKED: the private state is exactly what it was before g.
+ *   - with KS_GANG_STRICT in flags every gang after the first blocked one is KS_GANG_SKIPPED and
+ *     nothing is tried; without it the pass goes on (backfill).
+ * So with every gang admitted the rows are ks_place_at's on the k pods, and gang g's tried rows are
+ * the tail of ks_place_at on the pods of the gangs admitted before g followed by g's pods.
+ *
+ * out[g] answers gang g.  rows_out (may be NULL: summaries only) answers pod j at index j: a tried pod
+ * gets the ks_placement it had in its attempt (a blocked gang's rows show the attempt that was rolled
+ * back), an untried pod {-1, KS_GANG_NOT_TRIED, -1, 0}.  after_out (may be NULL): [n][4] milli-units
+ * and running pods, the final private state.  info_out (may be NULL): {rounds of the device
+ * algorithm, admitted, blocked, skipped, gangs decided through the single path (more pods than one
+ * set of lists decides: KS_PLACE_L), Ok pods of admitted gangs}.
+ * KS_EINVAL, and nothing is written: ks_place_at's argument errors; a NULL shape_of, first or out
+ * (before the handle is read); first[0] != 0, first decreasing or first[m] != k; a min_ok outside
+ * 0 .. size; an unknown flag bit; k outside [1, KS_GANG_MAX_PODS]; m outside [1, KS_GANG_MAX_GANGS];
+ * n_shapes outside [1, KS_GANG_MAX_SHAPES].  It answers after an aborted run, on sharded engines and on
+ * scenario-group members, like ks_place_at. */
+#define KS_GANG_MAX_GANGS  65536
+#define KS_GANG_MAX_PODS   65536   /* = KS_DRAIN_MAX_PODS */
+#define KS_GANG_MAX_SHAPES 4096
+#define KS_GANG_NOT_TRIED  (-2)    /* status of a pod no attempt reached */
+#define KS_GANG_STRICT     1u      /* flags: the first blocked gang ends the pass */
+enum { KS_GANG_BLOCKED = 0, KS_GANG_ADMITTED = 1, KS_GANG_SKIPPED = 2 };
+#define KS_GANG_INFO 6
+typedef struct {
+    int32_t first, size;      /* its pods: rows [first, first + size) */
+    int32_t outcome;          /* KS_GANG_* */
+    int32_t tried;            /* pods the attempt handled: size when admitted; up to and including the
+                                 deciding pod when blocked; 0 when skipped */
+    int32_t ok, over_capacity, not_found;  /* statuses among the tried pods */
+    int32_t block_status;     /* blocked: status of the pod that decided it; else 0 */
+} ks_gang;                    /* 32 bytes */
+ks_status ks_gang_at(ks_engine* eng, int64_t t, int32_t n_shapes, const int64_t* req /* [n_shapes][3] */,
+                     const uint8_t* keymask, const uint64_t* tol, const uint64_t* sel,
+                     int32_t k, const int32_t* shape_of /* [k] */,
+                     int32_t m, const int32_t* first /* [m + 1] */, const int32_t* min_ok /* [m] or NULL */,
+                     uint32_t flags, ks_gang* out /* [m] */, ks_placement* rows_out /* [k] or NULL */,
+                     int64_t* after_out /* [n][4] or NULL */, int64_t* info_out /* [KS_GANG_INFO] or NULL */);
 
 /* Scale-up preview: where k pending pods would be bound if up to max_nodes nodes of a node-group
  * template were added, at any past tick ("at tick t" as above), for n_options templates, each on its

@@ -3,8 +3,8 @@
 // A layout is written once, as a sequence of Carve::take() calls, and run twice: with a null base
 // the cursor only counts and `at` is the size to reserve; with the real base the same calls give
 // the pointers.  The reserved size and the ranges therefore cannot disagree.  The layouts of the
-// placement, drain, scale-up and consolidation previews and of the removal scan live here too, so a
-// stand-alone host program can check them.
+// placement, drain, scale-up, consolidation and gang previews and of the removal scan live here too,
+// so a stand-alone host program can check them.
 #pragma once
 #include <cstdint>
 
@@ -157,6 +157,27 @@ inline ConsolidateScratch carve_consolidate(Carve& qs, int64_t n, int64_t np, in
     s.cands = qs.take<ks::RemovalCand>(m, 2);
     s.out = qs.take<ks::Consolidation>(m);
     s.after = qs.take<long long>(4 * n);
+    return s;
+}
+
+// ks_gang_at: the rounds' buffers on the chain's state (b.shape_of: a round's KS_PLACE_MAX_PODS;
+// b.out: every pod's placement at its own index, a round's at its first pod), the single path's
+// second state copy, the gang table and the answers [m]
+struct GangScratch {
+    ks::PlaceBufs b;
+    int64_t* state2;  // [4][np]
+    ks::GangIn* gangs;
+    ks::Gang* out;
+    long long* after;  // [n][4]
+};
+inline GangScratch carve_gang(Carve& qs, Carve& qi, int64_t n, int64_t np, int64_t nblk, int64_t k, int64_t m) {
+    GangScratch s{};
+    s.b = carve_place(qs, np, nblk, ks::kPlaceMaxPods, k);
+    s.state2 = qs.take<int64_t>(4 * np);
+    s.gangs = qs.take<ks::GangIn>(m, 2);
+    s.out = qs.take<ks::Gang>(m);
+    s.after = qs.take<long long>(4 * n);
+    s.b.cnt = qi.take<int32_t>(ks::kPlaceMaxShapes * nblk);
     return s;
 }
 

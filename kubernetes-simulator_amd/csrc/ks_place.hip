@@ -14,7 +14,7 @@
 //   resolve_kernel<false> one workgroup decides pods in order until one cannot be decided from the
 //                         lists and the changed nodes, commits the changed nodes to the scratch and
 //                         reports the first undecided pod (the pod loop is ks_place_resolve.h's, which
-//                         ks_consolidate.hip instantiates a third time).
+//                         ks_consolidate.hip and ks_gang.hip instantiate again).
 // The scale-up preview (ks_scale_up_at, ks_scaleup.hip) runs the same pod loop on the same lists:
 //   resolve_kernel<true>  one workgroup per option decides the k pods in order, its changed set
 //                         private in LDS, the unchanged appended nodes stood for by the first of

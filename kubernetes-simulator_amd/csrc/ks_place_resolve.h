@@ -1,7 +1,7 @@
 // ks_place_resolve.h — the previews' resolver: one pod loop on the snapshot lists (gfx950, wave64).
 //
 // ks_place.hip instantiates it for the placement rounds and the scale-up preview,
-// ks_consolidate.hip for the consolidation rounds.  Device code only; each translation unit gets its
+// ks_consolidate.hip for the consolidation rounds, ks_gang.hip for the gang admission rounds.  Device code only; each translation unit gets its
 // own instantiations.
 #pragma once
 #include "ks_query.h"
@@ -16,7 +16,7 @@ static_assert(kPlaceMaxPods <= kPRes, "a resolver thread per changed node, and o
 __device__ __forceinline__ bool shape_active(uint64_t active, int sh) { return (active >> sh) & 1ull; }
 
 // ---------------------------------------------------------------------------------------------
-// Resolver: one pod loop, instantiated three times, a workgroup of kPRes threads each.  LDS holds the
+// Resolver: one pod loop, instantiated four times, a workgroup of kPRes threads each.  LDS holds the
 // lists and their flags, the shapes, the pods' shape indices, the running candidate counts and the
 // changed set (node + its ten words, current state; the call's units, PlaceCfg::sc).  Every global
 // read is issued before the pod loop: list entry (shape, e) belongs to thread (shape * L + e) %
@@ -82,6 +82,18 @@ __device__ __forceinline__ bool shape_active(uint64_t active, int sh) { return (
 // The round commits the changed nodes like the placement rounds, sets their `received` bits and
 // reports the next candidate in rb.  Cordon and received bits are set with global atomic ORs whose
 // results nobody reads in this launch: ORs commute.
+// kGang = true, the gang admission preview's rounds (ks_gang_at): one workgroup walks the gangs
+// [g0, g1) of GangRound in order; pods [0, k) are their pods, gang after gang.  A gang is the same
+// transaction with less around it (the argument is in ks_query.h, above gang_route):
+//   open    lflag[], cc[] (copies in LDS) and nchg are kept; nothing is flagged, no count corrected;
+//   pods    the loop below; pod i's slot is kept; a pod not bound Ok counts (uniform) and the attempt
+//           ends once more than size - min_ok of them did;
+//   admit   (at least min_ok pods bound Ok at the gang's end) the kept values are dropped;
+//   block   thread j of a tried pod whose own status is Ok takes its requests and one running pod
+//           back out of its kept slot; lflag, cc and nchg get their kept values back; the gang's
+//           later pods are not tried; with GangRound::strict the round ends and reports m;
+//   stop    (kPlaceStop inside a gang) the same roll-back, and the round ends: the gang opens the next.
+// Inside the loop it reads global memory once per gang: its table entry (a scalar load).
 // ---------------------------------------------------------------------------------------------
 template <bool kScale>
 struct ScaleRegs {};
@@ -123,7 +135,21 @@ struct ConsKept<true> {
 };
 struct NoRound {};
 
-template <bool kScale, bool kCons = false>
+// What a gang round keeps between a gang's opening and its end (in LDS: ConsKept<true>).
+template <bool kGang>
+struct GangRegs {};
+template <>
+struct GangRegs<true> {
+    int32_t a, first = 0, size = 0, allow = 0;  // the gang: its index, rows, and size - min_ok
+    int32_t beg = 0, end = 0, tried = 0;        // its pods among the round's; the end of those tried
+    bool open = false, blocked = false, strict_end = false;
+    int32_t nchg_s = 0;                         // nchg at the opening
+    int32_t n_ok = 0, n_over = 0, n_nf = 0, blk_status = 0;
+};
+template <bool kCons, bool kGang>
+using RoundArg = std::conditional_t<kCons, ConsRound, std::conditional_t<kGang, GangRound, NoRound>>;
+
+template <bool kScale, bool kCons = false, bool kGang = false>
 __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditional_t<kScale, const int64_t*, int64_t*> state,
                                                         int64_t n_pad, PlaceCfg pc, const PodRec* __restrict__ shapes,
                                                         const int32_t* __restrict__ shape_of,
@@ -131,8 +157,8 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
                                                         const long long* __restrict__ ccount,
                                                         const ScaleOption* __restrict__ opt, Placement* rows,
                                                         ScaleResult* __restrict__ res, int32_t first, uint64_t active,
-                                                        int32_t* rb, std::conditional_t<kCons, ConsRound, NoRound> cr) {
-    static_assert(!(kScale && kCons), "a consolidation round commits; an option does not");
+                                                        int32_t* rb, RoundArg<kCons, kGang> cr) {
+    static_assert(!(kScale && (kCons || kGang)) && !(kCons && kGang), "a round of transactions commits; an option does not");
     __shared__ NodeV chg[kPlaceMaxPods];
     __shared__ int32_t chg_node[kPlaceMaxPods];
     __shared__ uint64_t lst[kPlaceMaxShapes][kPlaceL];
@@ -157,7 +183,7 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
         first = 0;
         rows += (int64_t)blockIdx.x * pc.k;
     }
-    if constexpr (kCons) first = 0;
+    if constexpr (kCons || kGang) first = 0;
     const auto listed = [&](int sh) { return sh < pc.n_shapes && (kScale || shape_active(active, sh)); };
 
     // ---- every global read of the round / the option ----
@@ -200,9 +226,63 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
     [[maybe_unused]] bool stopped = false;
     Placement mine{};  // pod tid's result: every thread knows every decision, thread i keeps pod i's
     ConsRegs<kCons> cn;
-    [[maybe_unused]] __shared__ ConsKept<kCons> kept;
+    GangRegs<kGang> gn;
+    [[maybe_unused]] __shared__ ConsKept<kCons || kGang> kept;
     if constexpr (kCons) cn.a = cr.c0 - 1;
-    for (; kCons || i < k; ++i) {
+    if constexpr (kGang) {
+        gn.a = cr.g0 - 1;
+        mine = Placement{-1, kGangNotTried, -1, 0};  // (a pod no attempt reached)
+    }
+    for (; kCons || kGang || i < k; ++i) {
+        if constexpr (kGang) {
+            // uniform: no gang is open, or the open one has no pod left to try (or never had one)
+            while (i == gn.end) {
+                if (gn.open && (gn.blocked || stopped)) {  // roll back
+                    __syncthreads();  // the last pod's slot is written, every read of lflag / cc / chg is done
+                    if (tid >= gn.beg && tid < gn.tried && mine.status == kPlaceOk && kept.slot[tid] < gn.nchg_s) {
+                        const PodRec& q = shp[sof[tid]];  // an Ok pod on a kept slot
+                        unsigned long long* v = (unsigned long long*)&chg[kept.slot[tid]].rc;  // rc rm rg nr
+                        for (int c = 0; c < 3; ++c)
+                            if (q.keymask >> c & 1) atomicAdd(v + c, 0ull - (unsigned long long)q.req[c]);
+                        atomicAdd(v + 3, ~0ull);
+                    }
+                    if (tid < kPlaceMaxShapes) {
+                        lflag[tid] = kept.lflag[tid];
+                        cc[tid] = kept.cc[tid];
+                    }
+                    nchg = gn.nchg_s;
+                    if (!stopped && tid == 0)
+                        cr.out[gn.a] = Gang{gn.first, gn.size, kGangBlocked, gn.tried - gn.beg, gn.n_ok, gn.n_over, gn.n_nf,
+                                            gn.blk_status};
+                    if (!stopped && cr.strict) gn.strict_end = true;
+                    __syncthreads();
+                } else if (gn.open && tid == 0) {  // at least min_ok pods bound Ok: admitted
+                    cr.out[gn.a] = Gang{gn.first, gn.size, kGangAdmitted, gn.size, gn.n_ok, gn.n_over, gn.n_nf, 0};
+                }
+                gn.open = false;
+                gn.blocked = false;
+                if (stopped || gn.strict_end || ++gn.a >= cr.g1) break;  // (stopped: the rolled-back gang opens the next round)
+                // ---- the next gang opens ----
+                const GangIn gd = sload(cr.gangs + gn.a);
+                gn.first = gd.first;
+                gn.size = gd.size;
+                const int64_t b0 = (int64_t)gd.first - cr.row0, b1 = b0 + gd.size;
+                gn.beg = b0 < 0 ? 0 : b0 > k ? k : (int32_t)b0;  // (the host's rows: within [0, k])
+                gn.end = b1 < gn.beg ? gn.beg : b1 > k ? k : (int32_t)b1;
+                gn.tried = gn.end;
+                const int32_t mo = gd.min_ok < 0 ? 0 : gd.min_ok > gd.size ? gd.size : gd.min_ok;  // (the host checked)
+                gn.allow = gd.size - mo;
+                gn.n_ok = gn.n_over = gn.n_nf = gn.blk_status = 0;
+                if (tid < kPlaceMaxShapes) {  // (read back by the same thread alone)
+                    kept.lflag[tid] = lflag[tid];
+                    kept.cc[tid] = cc[tid];
+                }
+                gn.nchg_s = nchg;
+                gn.open = true;
+                i = gn.beg;  // (== gn.end for an empty gang: admitted by the next turn of this loop)
+            }
+            if (stopped || gn.strict_end || gn.a >= cr.g1) break;
+        }
         if constexpr (kCons) {
             // uniform: no candidate is open, or the open one has no pod left (or never had one)
             while (i == cn.end) {
@@ -302,6 +382,12 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
                 i = cn.end - 1;
                 continue;
             }
+            if constexpr (kGang) {  // the open gang is rolled back (above) and starts the next round
+                stopped = true;
+                gn.tried = i;
+                i = gn.end - 1;
+                continue;
+            }
             break;
         }
         const long long cand = cc[sh];
@@ -315,6 +401,15 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
                 cn.blk = i;
                 cn.blk_status = kPlaceNotFound;
                 i = cn.end - 1;
+            }
+            if constexpr (kGang) {
+                ++gn.n_nf;
+                if (gn.n_over + gn.n_nf > gn.allow) {
+                    gn.blocked = true;
+                    gn.blk_status = kPlaceNotFound;
+                    gn.tried = i + 1;
+                    i = gn.end - 1;
+                }
             }
             continue;
         }
@@ -356,7 +451,7 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
         const int32_t status = place_bind(p, after);
         if (status == kPlaceOk && tid < pc.n_shapes) cc[tid] += place_cand_delta(pc.c, shp[tid], before, after);
         if (tid == i) mine = Placement{(int32_t)X, status, (int64_t)(W >> 32) - 1, cand};
-        if constexpr (kCons)
+        if constexpr (kCons || kGang)
             if (tid == i) kept.slot[i] = (uint16_t)idx;
         if constexpr (kScale) {
             if (status == kPlaceOk) {
@@ -378,10 +473,21 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
                 cn.blk_status = status;
                 i = cn.end - 1;
             }
+        if constexpr (kGang) {
+            if (status == kPlaceOk) {
+                ++gn.n_ok;
+            } else if (++gn.n_over + gn.n_nf > gn.allow) {
+                gn.blocked = true;
+                gn.blk_status = status;
+                gn.tried = i + 1;
+                i = gn.end - 1;
+            }
+        }
     }
     __syncthreads();
     // ---- the decided pods' rows (consolidation: a skipped pod's row is never read) ----
     if constexpr (kCons) i = stopped ? cn.beg : k;  // (stopped: cn.a is still the rolled-back candidate)
+    if constexpr (kGang) i = stopped ? gn.beg : k;  // (an untried pod's row says so)
     if (tid >= first && tid < i) rows[tid] = mine;
     if constexpr (kScale) {
         // the option's summary; appended nodes that hold a pod: the template starts with none running
@@ -410,6 +516,13 @@ __global__ __launch_bounds__(kPRes) void resolve_kernel(NodeSoA s, std::conditio
             if (tid == 0) {  // the next candidate, 1 if the round decided none, the changed nodes, the pods before it
                 rb[0] = cn.a;
                 rb[1] = cn.a == cr.c0 ? 1 : 0;
+                rb[2] = nchg;
+                rb[3] = i;
+            }
+        } else if constexpr (kGang) {
+            if (tid == 0) {  // the next gang (m: a strict pass is over), 1 if the round decided none
+                rb[0] = gn.strict_end ? cr.m : gn.a;
+                rb[1] = !gn.strict_end && gn.a == cr.g0 ? 1 : 0;
                 rb[2] = nchg;
                 rb[3] = i;
             }

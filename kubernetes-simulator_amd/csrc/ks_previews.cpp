@@ -1,6 +1,6 @@
-// ks_previews.cpp — the five previews of include/ks_engine.h: what scheduleOne would do on a private
+// ks_previews.cpp — the six previews of include/ks_engine.h: what scheduleOne would do on a private
 // copy of the state at a past tick (ks_place_at, ks_drain_at, ks_removable_at, ks_consolidate_at,
-// ks_scale_up_at).  They open like the past-tick queries of ks_queries.cpp (ks_queries.h), read the
+// ks_gang_at, ks_scale_up_at).  They open like the past-tick queries of ks_queries.cpp (ks_queries.h), read the
 // engine and write nothing a later ks_step reads; their device contract is ks_query.h.
 #include <cstring>
 
@@ -245,11 +245,12 @@ static ks_status gather_open(ks_engine* e, const char* what, int64_t t, int32_t 
 // uploads its shapes and place_rounds decides its pods with `cordon` on b.state, which carries from
 // one segment to the next; row i's placement goes to out[i].  what and pod_base name a row in the
 // messages; *rounds and *segments (null: not counted) grow by those run.  after (empty: none) is
-// called once the segment [start, start + k) is decided and says whether to go on.
+// called once the segment [start, start + k) is decided and says whether to go on.  sc: the records'
+// units (evicted pods' own records: device units).
 using SegmentHook = std::function<ks_status(int64_t start, int32_t k, bool* go_on)>;
 static ks_status drain_rounds(ks_engine* e, ks::PlaceBufs b, ks::Placement* out, const ks::PodRec* recs, int64_t count,
                               const uint32_t* cordon, const char* what, int64_t pod_base, int64_t* rounds,
-                              int64_t* segments, const SegmentHook& after = {}) {
+                              int64_t* segments, const SegmentHook& after = {}, const ks::QScale& sc = kDeviceUnits) {
     const std::string round_what = std::string(what) + ": the round from evicted pod";
     std::vector<unsigned long long> h_up;
     std::vector<int32_t> so(KS_PLACE_MAX_PODS);
@@ -263,7 +264,7 @@ static ks_status drain_rounds(ks_engine* e, ks::PlaceBufs b, ks::Placement* out,
             return fail(e, KS_EDEVICE, "%s: empty segment at evicted pod %lld", what, (long long)(pod_base + start));
         if (ks_status r = upload_shapes(e, b, h_up, seg_shapes, ns, so.data(), k); r != KS_OK) return r;
         b.out = out + start;
-        const ks::PlaceCfg pc{e->dc, kDeviceUnits, (int32_t)e->n, k, ns, (int32_t)((e->n + 255) / 256)};
+        const ks::PlaceCfg pc{e->dc, sc, (int32_t)e->n, k, ns, (int32_t)((e->n + 255) / 256)};
         if (ks_status r = place_rounds(e, e->s, pc, b, so.data(), cordon, round_what.c_str(), pod_base + start, rounds); r != KS_OK)
             return r;
         if (segments) ++*segments;
@@ -638,6 +639,197 @@ ks_status ks_consolidate_at(ks_engine* e, int64_t t, int32_t m, const int32_t* n
     *n_rows = row;
     std::memcpy(out, h_out.data(), sizeof(ks_consolidation) * m);
     if (info_out) std::copy(info, info + KS_CONSOLIDATE_INFO, info_out);
+    return KS_OK;
+}
+
+// ---- gang admission preview (ks_gang.hip) --------------------------------------------------------
+// ks_place_at's pods in groups, each a transaction.  The gangs in order: a round (scan + merge, then
+// the resolver's transactions: ks::launch_gang_round) takes gangs up to KS_PLACE_MAX_SHAPES distinct
+// shapes and KS_PLACE_MAX_PODS pods (ks::gang_segment; the caller's shapes are numbered again per
+// round) and reports where it ended in 16 bytes; a gang with more pods than one set of lists decides
+// (ks::gang_route) heads no round: the host runs ks_drain_at's segmented rounds for it on a copy of
+// the state, applies the early end to the finished rows and adopts the copy iff the gang is
+// admitted.  Answers and placements are read back once, at the end.
+static_assert(KS_GANG_MAX_GANGS == ks::kGangMaxGangs && KS_GANG_MAX_PODS == ks::kDrainMaxPods &&
+              KS_GANG_MAX_SHAPES == ks::kGangMaxShapes && KS_GANG_NOT_TRIED == ks::kGangNotTried && KS_GANG_INFO == 6 &&
+              KS_GANG_BLOCKED == ks::kGangBlocked && KS_GANG_ADMITTED == ks::kGangAdmitted &&
+              KS_GANG_SKIPPED == ks::kGangSkipped && sizeof(ks_gang) == sizeof(ks::Gang) && SAME_FIELD(ks_gang, Gang, first) &&
+              SAME_FIELD(ks_gang, Gang, size) && SAME_FIELD(ks_gang, Gang, outcome) && SAME_FIELD(ks_gang, Gang, tried) &&
+              SAME_FIELD(ks_gang, Gang, ok) && SAME_FIELD(ks_gang, Gang, over_capacity) &&
+              SAME_FIELD(ks_gang, Gang, not_found) && SAME_FIELD(ks_gang, Gang, block_status),
+              "ks_gang_at constants and record");
+
+// A gang's answer from the rows of its attempt, read in order: *go_on turns false at the pod that
+// blocks it (more than size - min_ok pods not bound Ok), which ends the attempt.
+static void gang_tally(ks::Gang& o, int32_t min_ok, const ks::Placement* rows, int32_t count, bool* go_on) {
+    for (int32_t i = 0; i < count && *go_on; i++) {
+        const int32_t st = rows[i].status;
+        (st == KS_POD_OK ? o.ok : st == KS_POD_OVER_CAPACITY ? o.over_capacity : o.not_found)++;
+        o.tried++;
+        if (o.over_capacity + o.not_found > o.size - min_ok) {
+            o.outcome = KS_GANG_BLOCKED;
+            o.block_status = st;
+            *go_on = false;
+        }
+    }
+}
+
+ks_status ks_gang_at(ks_engine* e, int64_t t, int32_t n_shapes, const int64_t* req, const uint8_t* keymask,
+                     const uint64_t* tol, const uint64_t* sel, int32_t k, const int32_t* shape_of, int32_t m,
+                     const int32_t* first, const int32_t* min_ok, uint32_t flags, ks_gang* out, ks_placement* rows_out,
+                     int64_t* after_out, int64_t* info_out) {
+    if (!shape_of || !first || !out) return KS_EINVAL;
+    if (!e || !req || !keymask || !tol || !sel) return KS_EINVAL;
+    if (!e->nodes_loaded) return fail(e, KS_EINVAL, "no nodes loaded");
+    if (flags & ~KS_GANG_STRICT) return fail(e, KS_EINVAL, "gang: unknown flag bits %#x", (unsigned)(flags & ~KS_GANG_STRICT));
+    if (k < 1 || k > KS_GANG_MAX_PODS) return fail(e, KS_EINVAL, "gang: %d pods outside [1, %d]", (int)k, KS_GANG_MAX_PODS);
+    if (m < 1 || m > KS_GANG_MAX_GANGS) return fail(e, KS_EINVAL, "gang: %d gangs outside [1, %d]", (int)m, KS_GANG_MAX_GANGS);
+    if (ks_status r = head_shapes(e, n_shapes, req, keymask, tol, sel, "gang", KS_GANG_MAX_SHAPES); r != KS_OK) return r;
+    for (int32_t j = 0; j < k; j++)
+        if (shape_of[j] < 0 || shape_of[j] >= n_shapes)
+            return fail(e, KS_EINVAL, "gang: pod %d has shape %d outside [0, %d)", (int)j, (int)shape_of[j], (int)n_shapes);
+    if (first[0] != 0 || first[m] != k) return fail(e, KS_EINVAL, "gang: first[0] = %d, first[m] = %d, not 0 and %d", (int)first[0], (int)first[m], (int)k);
+    std::vector<ks::GangIn> gangs(m);
+    for (int32_t g = 0; g < m; g++) {
+        if (first[g + 1] < first[g]) return fail(e, KS_EINVAL, "gang %d: first decreases", (int)g);
+        const int32_t size = first[g + 1] - first[g], mo = min_ok ? min_ok[g] : size;
+        if (mo < 0 || mo > size) return fail(e, KS_EINVAL, "gang %d: min_ok %d outside [0, %d]", (int)g, (int)mo, (int)size);
+        gangs[g] = ks::GangIn{first[g], size, mo, 0};
+    }
+    if (ks_status r = check_tick(e, "", t); r != KS_OK) return r;
+    const bool strict = flags & KS_GANG_STRICT;
+    int64_t info[KS_GANG_INFO] = {0, 0, 0, 0, 0, 0};
+    std::vector<ks::Gang> h_out(m);
+    std::vector<ks::Placement> placed(k, ks::Placement{-1, ks::kPlaceNotFound, -1, 0});
+    std::vector<char> by_host(m, 0);  // answered here: the single path (and every gang of a cluster of no node)
+    for (int32_t g = 0; g < m; g++) h_out[g] = ks::Gang{gangs[g].first, gangs[g].size, ks::kGangUndecided, 0, 0, 0, 0, 0};
+    bool over = false;  // a strict pass met its blocked gang
+    const int64_t n = e->n, np = e->n_pad, nblk = (n + 255) / 256;
+    GangScratch s{};
+    ks::PlaceBufs b{};
+    ks::QScale back = kDeviceUnits;  // the scratch state's units in milli-units
+    if (n == 0) {
+        // no node: every pod is not found, the gangs follow from that
+        for (int32_t g = 0; g < m && !over; g++) {
+            ks::Gang& o = h_out[g];
+            by_host[g] = 1;
+            o.outcome = KS_GANG_ADMITTED;
+            bool go_on = true;
+            gang_tally(o, gangs[g].min_ok, placed.data() + o.first, o.size, &go_on);
+            over = strict && o.outcome == KS_GANG_BLOCKED;
+        }
+    } else {
+        const int64_t q_hi = bound_by(e, t);
+        int64_t nb = 0;
+        if (ks_status r = query_blocks(e, t, q_hi, &nb); r != KS_OK) return r;
+        CARVE_SCRATCH(e, s = carve_gang(qs, qi, n, np, nblk, k, m));
+        b = s.b;
+        // whole-unit requests: the call runs in device units, as ks_place_at does
+        const ks::QScale milli = milli_scale(e);
+        const bool whole = ks::place_whole_units(e->h_shapes.data(), n_shapes, milli);
+        const ks::QScale sc = call_units(e, whole, milli);
+        back = whole ? milli : kDeviceUnits;
+        if (ks_status r = rebuild_state(e, nb, q_hi, t, sc, 1, np, (unsigned long long*)b.state); r != KS_OK) return r;
+        std::vector<ks::PodRec> recs(k);
+        for (int32_t j = 0; j < k; j++) recs[j] = e->h_shapes[shape_of[j]];
+        HIPCHK(e, hipMemcpyAsync((void*)s.gangs, gangs.data(), sizeof(ks::GangIn) * m, hipMemcpyHostToDevice, e->st));
+        HIPCHK(e, hipMemcpyAsync((void*)s.out, h_out.data(), sizeof(ks::Gang) * m, hipMemcpyHostToDevice, e->st));
+        // ---- the chain ----
+        std::vector<unsigned long long> h_up;
+        std::vector<int32_t> so(KS_PLACE_MAX_PODS);
+        std::vector<ks::Placement> seg_rows;
+        ks::PodRec seg_shapes[KS_PLACE_MAX_SHAPES];
+        for (int32_t cur = 0; cur < m && !over;) {
+            const ks::GangIn& gd = gangs[cur];
+            if (ks::gang_route(gd.size) == ks::kGangSingle) {
+                // the single path: the chain's state copied, ks_drain_at's rounds without a cordon
+                ks::Gang& o = h_out[cur];
+                by_host[cur] = 1;
+                HIPCHK(e, hipMemcpyAsync(s.state2, b.state, sizeof(int64_t) * 4 * np, hipMemcpyDeviceToDevice, e->st));
+                ks::PlaceBufs x = b;
+                x.state = s.state2;
+                o.outcome = KS_GANG_ADMITTED;
+                ks::Placement* rows = s.b.out + gd.first;
+                // a segment's rows are read back at once: the attempt ends at the pod that blocks the gang
+                const SegmentHook until_blocked = [&](int64_t start, int32_t kk, bool* go_on) -> ks_status {
+                    seg_rows.resize(kk);
+                    HIPCHK(e, hipMemcpyAsync(seg_rows.data(), rows + start, sizeof(ks::Placement) * kk, hipMemcpyDeviceToHost, e->st));
+                    HIPCHK(e, hipStreamSynchronize(e->st));
+                    gang_tally(o, gd.min_ok, seg_rows.data(), kk, go_on);
+                    return KS_OK;
+                };
+                if (ks_status r = drain_rounds(e, x, rows, recs.data() + gd.first, gd.size, nullptr, "gang", gd.first, &info[0],
+                                               nullptr, until_blocked, sc);
+                    r != KS_OK)
+                    return r;
+                if (o.outcome == KS_GANG_ADMITTED)  // adopted
+                    HIPCHK(e, hipMemcpyAsync(b.state, s.state2, sizeof(int64_t) * 4 * np, hipMemcpyDeviceToDevice, e->st));
+                over = strict && o.outcome == KS_GANG_BLOCKED;
+                info[4]++;
+                cur++;
+                continue;
+            }
+            int32_t ns = 0, kk = 0;
+            const int64_t end = ks::gang_segment(recs.data(), gangs.data(), m, cur, seg_shapes, &ns, so.data(), &kk);
+            if (end <= cur) return fail(e, KS_EDEVICE, "gang: empty round at gang %d", (int)cur);
+            if (kk)
+                if (ks_status r = upload_shapes(e, b, h_up, seg_shapes, ns, so.data(), kk); r != KS_OK) return r;
+            b.out = s.b.out + gd.first;
+            const ks::PlaceCfg pc{e->dc, sc, (int32_t)n, kk, ns, (int32_t)nblk};
+            const ks::GangRound gr{s.gangs, cur, (int32_t)end, m, strict ? 1 : 0, gd.first, s.out};
+            HIPCHK(e, ks::launch_gang_round(e->s, pc, b, gr, e->st));
+            int32_t rb[4] = {0, 1, 0, 0};
+            HIPCHK(e, hipMemcpyAsync(rb, b.rb, sizeof(rb), hipMemcpyDeviceToHost, e->st));  // 16 bytes per round
+            HIPCHK(e, hipStreamSynchronize(e->st));
+            const bool ended = strict && rb[0] == m;  // (its blocked gang is found in the answers, below)
+            if (rb[1] != 0 || rb[0] <= cur || (rb[0] > end && !ended))
+                return fail(e, KS_EDEVICE, "gang: the round from gang %d decided none", (int)cur);
+            cur = rb[0];
+            info[0]++;
+        }
+        // ---- one read-back: the answers and every pod's placement ----
+        std::vector<ks::Gang> got(m);
+        HIPCHK(e, hipMemcpyAsync(got.data(), s.out, sizeof(ks::Gang) * m, hipMemcpyDeviceToHost, e->st));
+        if (rows_out) HIPCHK(e, hipMemcpyAsync(placed.data(), s.b.out, sizeof(ks::Placement) * k, hipMemcpyDeviceToHost, e->st));
+        std::vector<int64_t> h_after(after_out ? 4 * n : 0);
+        if (ks_status r = finish_after(e, b, back, s.after, after_out ? h_after.data() : nullptr); r != KS_OK) return r;
+        over = false;
+        for (int32_t g = 0; g < m; g++) {
+            ks::Gang& o = h_out[g];
+            if (!by_host[g]) {
+                const ks::Gang& v = got[g];
+                const int32_t allow = o.size - gangs[g].min_ok, bad = v.over_capacity + v.not_found;
+                const bool sane = over ? v.outcome == ks::kGangUndecided
+                                  : v.outcome == KS_GANG_ADMITTED
+                                      ? v.tried == v.size && v.ok + bad == v.size && bad <= allow && v.block_status == 0
+                                  : v.outcome == KS_GANG_BLOCKED
+                                      ? v.tried >= 1 && v.tried <= v.size && v.ok + bad == v.tried && bad == allow + 1 &&
+                                            (v.block_status == KS_POD_OVER_CAPACITY || v.block_status == KS_PLACE_NOT_FOUND)
+                                      : false;
+                if (v.first != o.first || v.size != o.size || !sane)
+                    return fail(e, KS_EDEVICE, "gang: gang %d was not decided", (int)g);
+                o = v;
+            } else if (over && o.outcome != ks::kGangUndecided) {
+                return fail(e, KS_EDEVICE, "gang: gang %d was tried after the pass ended", (int)g);
+            }
+            if (!over && o.outcome == ks::kGangUndecided) return fail(e, KS_EDEVICE, "gang: gang %d was not decided", (int)g);
+            over = over || (strict && o.outcome == KS_GANG_BLOCKED);
+        }
+        if (after_out) std::memcpy(after_out, h_after.data(), sizeof(int64_t) * h_after.size());
+    }
+    for (int32_t g = 0; g < m; g++) {
+        ks::Gang& o = h_out[g];
+        if (o.outcome == ks::kGangUndecided) o = ks::Gang{o.first, o.size, KS_GANG_SKIPPED, 0, 0, 0, 0, 0};
+        info[o.outcome == KS_GANG_ADMITTED ? 1 : o.outcome == KS_GANG_BLOCKED ? 2 : 3]++;
+        if (o.outcome == KS_GANG_ADMITTED) info[5] += o.ok;
+        if (rows_out)
+            for (int32_t i = 0; i < o.size; i++)
+                rows_out[o.first + i] = i < o.tried ? ks_placement{placed[o.first + i].node, placed[o.first + i].status,
+                                                                   placed[o.first + i].score, placed[o.first + i].candidates}
+                                                    : ks_placement{-1, KS_GANG_NOT_TRIED, -1, 0};
+    }
+    std::memcpy(out, h_out.data(), sizeof(ks_gang) * m);
+    if (info_out) std::copy(info, info + KS_GANG_INFO, info_out);
     return KS_OK;
 }
 

@@ -81,9 +81,8 @@ ks_status copy_result(ks_engine* e, ks_status rc, void* dst, const void* src, si
 }
 
 ks_status head_shapes(ks_engine* e, int32_t k, const int64_t* req, const uint8_t* keymask, const uint64_t* tol,
-                      const uint64_t* sel, const char* what) {
-    if (k < 1 || k > KS_HEADROOM_MAX_SHAPES)
-        return fail(e, KS_EINVAL, "%s: %d shapes outside [1, %d]", what, (int)k, KS_HEADROOM_MAX_SHAPES);
+                      const uint64_t* sel, const char* what, int32_t max_shapes) {
+    if (k < 1 || k > max_shapes) return fail(e, KS_EINVAL, "%s: %d shapes outside [1, %d]", what, (int)k, (int)max_shapes);
     e->h_shapes.assign(k, ks::PodRec{});
     for (int32_t j = 0; j < k; j++) {
         if (keymask[j] & ~7u) return fail(e, KS_EINVAL, "%s shape %d: keymask %u has bits above 4", what, (int)j, (unsigned)keymask[j]);

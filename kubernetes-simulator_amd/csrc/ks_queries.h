@@ -33,8 +33,8 @@ ks_status rebuild_state(ks_engine* e, int64_t nb, int64_t q_hi, int64_t t, const
                         int64_t pitch, unsigned long long* dst);
 // the tail of a query over n > 0 nodes: copy the result out once its kernels are queued (rc: theirs)
 ks_status copy_result(ks_engine* e, ks_status rc, void* dst, const void* src, size_t bytes);
-// the call's shape records (e->h_shapes, requests in milli-units) from k checked shapes
+// the call's shape records (e->h_shapes, requests in milli-units) from k checked shapes, max_shapes at the most
 ks_status head_shapes(ks_engine* e, int32_t k, const int64_t* req, const uint8_t* keymask, const uint64_t* tol,
-                      const uint64_t* sel, const char* what = "headroom");
+                      const uint64_t* sel, const char* what = "headroom", int32_t max_shapes = KS_HEADROOM_MAX_SHAPES);
 
 }  // namespace ks_host

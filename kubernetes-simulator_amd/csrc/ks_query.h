@@ -806,5 +806,112 @@ hipError_t launch_consolidate_take(uint32_t* cordon, int64_t* state, int64_t n_p
 // ... and, once adopted, the nodes of its k placements join `received`
 hipError_t launch_consolidate_mark(const Placement* placed, int64_t k, int32_t n_nodes, uint32_t* received, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------
+// Gang admission preview (ks_gang_at, ks_gang.hip): m pod groups handled in the caller's order as a
+// chain of transactions on one private state.  Gang g's pods go to scheduleOne one after another; a
+// pod bound Ok joins its node, a pod not bound Ok changes nothing and the attempt goes on until
+// more than size - min_ok of them were not bound Ok.  At least min_ok Ok pods at the gang's end: the
+// gang is admitted and its placements stay; otherwise everything is as it was before g.
+//
+// Exactness of a round.  A round scans the committed scratch state with no cordon and then walks
+// gangs in order with one changed set, one set of flags and one set of running counts: the
+// argument above place_decide holds as it stands, a gang's opening sets no flag and corrects no
+// count.  A pod bound OverCapacity may append its node to the changed set with its record as it
+// was: the node is evaluated exactly on D's side from then on, which the argument allows.
+//   admit   nothing is restored: the flags, the counts and the changed set stay for the rest of
+//           the round.
+//   block   the state must be exactly the state before g.  The attempt changed four things: the
+//           changed nodes' records (place_bind adds the masked requests and one pod on Ok and
+//           nothing else, so subtracting them for every tried pod whose own status is Ok restores
+//           a slot that existed before g — a pod not bound Ok added nothing and subtracts nothing;
+//           slots appended by the attempt lie at [nchg before g, nchg) and are dropped), the flag
+//           words, the running counts (both restored from the copies taken when g opened) and
+//           nchg.  A dropped slot's node is unchanged again and its entries are unflagged again: it
+//           has its snapshot key, as the argument needs.
+// The round's commit is the placement rounds': the changed nodes' records, each node once.
+//
+// Progress.  A round's first gang finds fresh lists with nothing flagged, so its pod i (1-based)
+// finds at most i - 1 flagged entries: with at most kGangMaxPods = L pods (so at most L <= 64
+// shapes) it is decided in that round.  kPlaceStop inside a later gang rolls that gang back and ends
+// the round; it opens the next one.  A gang with more pods (gang_route) is answered by the host's
+// single path when it is the next to be decided: a copy of the scratch state, the drain preview's
+// segmented rounds on the gang's pods with no cordon, the early end applied to the finished rows
+// (exact: a pod not bound Ok changes nothing, so the rows up to the deciding pod are the attempt's),
+// adopted iff the gang is admitted.  The segment walk closes before such a gang.
+// ---------------------------------------------------------------------------------------------
+constexpr int kGangMaxPods = kPlaceL;       // pods of a gang the rounds decide
+constexpr int64_t kGangMaxGangs = 65536;    // KS_GANG_MAX_GANGS
+constexpr int32_t kGangMaxShapes = 4096;    // KS_GANG_MAX_SHAPES
+constexpr int32_t kGangNotTried = -2;       // KS_GANG_NOT_TRIED
+enum : int32_t { kGangBlocked = 0, kGangAdmitted = 1, kGangSkipped = 2, kGangUndecided = -1 };  // KS_GANG_*
+enum : int { kGangRound = 0, kGangSingle = 1 };
+static_assert(kGangMaxPods <= kPlaceMaxShapes && kGangMaxPods <= kPlaceMaxPods, "a round-path gang fits a round");
+
+struct Gang {  // = ks_gang
+    int32_t first, size, outcome, tried, ok, over_capacity, not_found, block_status;
+};
+static_assert(sizeof(Gang) == 32, "ks_gang layout");
+struct GangIn {  // a gang as the resolver reads it: rows [first, first + size) of the call's pods
+    int32_t first, size, min_ok, pad;
+};
+static_assert(sizeof(GangIn) == 16, "one scalar load");
+
+// who decides a gang of `pods` pods
+__host__ __device__ __forceinline__ int gang_route(int64_t pods) { return pods <= kGangMaxPods ? kGangRound : kGangSingle; }
+
+// The round that starts at gang `start` of gangs[m] (rows of recs): it closes before the gang that
+// would bring its (kPlaceMaxShapes + 1)-th distinct shape or its (kPlaceMaxPods + 1)-th pod, and
+// before a gang of the single path.  Returns its end (exclusive; > start when gangs[start] is of the
+// round path), its distinct shapes in shapes[0, *n_shapes) in order of first appearance (masked
+// requests, flags 0), shape_of[row - gangs[start].first] for its rows and their number in *n_pods.
+inline int64_t gang_segment(const PodRec* recs, const GangIn* gangs, int64_t m, int64_t start, PodRec* shapes,
+                            int32_t* n_shapes, int32_t* shape_of, int32_t* n_pods) {
+    int32_t ns = 0, np = 0;
+    int64_t a = start;
+    const int64_t row0 = start < m ? gangs[start].first : 0;
+    for (; a < m; ++a) {
+        if (gang_route(gangs[a].size) != kGangRound || np + gangs[a].size > kPlaceMaxPods) break;
+        const int32_t before = ns;
+        bool fits_in = true;
+        for (int64_t row = gangs[a].first; row < (int64_t)gangs[a].first + gangs[a].size; ++row) {
+            int32_t j = 0;
+            while (j < ns && !drain_same_shape(shapes[j], recs[row])) ++j;
+            if (j == ns) {
+                if (ns == kPlaceMaxShapes) {
+                    fits_in = false;
+                    break;
+                }
+                PodRec r{};
+                for (int c = 0; c < 3; ++c) r.req[c] = (recs[row].keymask >> c & 1) ? recs[row].req[c] : 0;
+                r.tol = recs[row].tol; r.sel = recs[row].sel; r.keymask = recs[row].keymask;
+                shapes[ns++] = r;
+            }
+            shape_of[row - row0] = j;
+        }
+        if (!fits_in) {
+            ns = before;  // (the next round numbers this gang's rows again)
+            break;
+        }
+        np += gangs[a].size;
+    }
+    *n_shapes = ns;
+    *n_pods = np;
+    return a;
+}
+
+// One round on the device: gangs [m], every gang in the caller's order; the round's gangs [g0, g1)
+// and row0 = gangs[g0].first; strict: the first blocked gang ends the pass; out [m], the answers.
+struct GangRound {
+    const GangIn* gangs;
+    int32_t g0, g1, m, strict;
+    int64_t row0;
+    Gang* out;
+};
+// scan + merge of pc.n_shapes shapes on b.state (none when the round has no pod: pc.k = pc.n_shapes
+// = 0), then the resolver: pods [0, pc.k) are rows [row0, row0 + pc.k), their placements go to
+// b.out[0, pc.k), b.rb gets {the next gang (m: a strict pass ended), 1 if none was decided, the
+// changed nodes committed, the pods before the next gang}
+hipError_t launch_gang_round(const NodeSoA& s, const PlaceCfg& pc, const PlaceBufs& b, const GangRound& gr, hipStream_t st);
+
 
 }  // namespace ks

@@ -70,6 +70,19 @@ KS_CONSOLIDATE_BLOCKED, KS_CONSOLIDATE_REMOVED, KS_CONSOLIDATE_DESTINATION = 0, 
 KS_CONSOLIDATE_INFO = 6
 KS_CONSOLIDATION_BYTES = 32
 KS_CONSOLIDATE_MAX_ROUND = 31
+# ks_gang_at: gangs, pods and shapes per call, the status of a pod no attempt reached, the flag, a
+# gang's outcome, the info words (rounds, admitted, blocked, skipped, gangs decided through the single
+# path, Ok pods of admitted gangs), sizeof(ks_gang); KS_GANG_MAX_ROUND: the pods of a gang the rounds
+# decide (csrc/ks_query.h kGangMaxPods = KS_PLACE_L)
+KS_GANG_MAX_GANGS = 65536
+KS_GANG_MAX_PODS = 65536
+KS_GANG_MAX_SHAPES = 4096
+KS_GANG_NOT_TRIED = -2
+KS_GANG_STRICT = 1
+KS_GANG_BLOCKED, KS_GANG_ADMITTED, KS_GANG_SKIPPED = 0, 1, 2
+KS_GANG_INFO = 6
+KS_GANG_BYTES = 32
+KS_GANG_MAX_ROUND = 32
 # ks_scale_up_at: options per call, appended nodes per option, the info words (options decided by the
 # batched kernel, options answered through the single path, options in which every pod was bound Ok,
 # distinct shapes); ks_scale_result.path
@@ -91,7 +104,7 @@ EXPORTED_SYMBOLS = ("ks_create", "ks_destroy", "ks_load_nodes", "ks_submit_pods"
                     "ks_shard_layout", "ks_merge_candidates",
                     "ks_requested_at", "ks_filter_at", "ks_score_at", "ks_cluster_series", "ks_node_peaks",
                     "ks_headroom_at", "ks_headroom_series", "ks_place_at", "ks_drain_at",
-                    "ks_removable_at", "ks_scale_up_at", "ks_consolidate_at",
+                    "ks_removable_at", "ks_scale_up_at", "ks_consolidate_at", "ks_gang_at",
                     # include/ks_ingest.h
                     "ks_parse_quantity", "ks_parse_simspec", "ks_cluster_parse", "ks_cluster_free",
                     "ks_cluster_nodes", "ks_cluster_tick", "ks_cluster_start_clock", "ks_cluster_arrays",
@@ -260,11 +273,12 @@ def load():
     L.ks_removable_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, C.c_int64, C.POINTER(C.c_int64), p]
     L.ks_consolidate_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, C.c_int64, C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64), p, p]
+    L.ks_gang_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, C.c_int32, p, p, C.c_uint32, p, p, p, p]
     L.ks_scale_up_at.argtypes = [p, C.c_int64, C.c_int32, p, p, p, p, C.c_int32, p, C.c_int32, p, p, p, p]
     for f in ("ks_load_nodes", "ks_submit_pods", "ks_step", "ks_filter", "ks_score", "ks_usage", "ks_usage_at",
               "ks_usage_digest", "ks_pod_lookup", "ks_node_pods", "ks_requested_at", "ks_filter_at", "ks_score_at",
               "ks_cluster_series", "ks_node_peaks", "ks_headroom_at", "ks_headroom_series", "ks_place_at",
-              "ks_drain_at", "ks_removable_at", "ks_scale_up_at", "ks_consolidate_at"):
+              "ks_drain_at", "ks_removable_at", "ks_scale_up_at", "ks_consolidate_at", "ks_gang_at"):
         getattr(L, f).restype = C.c_int
     L.ks_current_tick.argtypes = [p]
     L.ks_current_tick.restype = C.c_int64

@@ -23,6 +23,8 @@ scheduleOne, what-if   ``place_at``: where k more pods would be bound at a past 
                        answer for each of m candidate nodes on its own;
                        ``consolidate_at``: the candidates one after another as a scale-down
                        pass handles them, removals kept, failed attempts rolled back;
+                       ``gang_at``: ``place_at``'s pods in groups admitted all-or-nothing
+                       (or from ``min_ok`` members up), in queue order;
                        ``scale_up_at``:
                        ``place_at`` on the cluster plus up to M empty nodes of a node-group
                        template, for each of G templates on its own
@@ -72,6 +74,11 @@ assert REMOVAL_DTYPE.itemsize == 32
 CONSOLIDATION_DTYPE = np.dtype([("node", np.int32), ("evicted", np.int32), ("outcome", np.int32), ("rows", np.int32),
                                 ("block_status", np.int32), ("pad", np.int32), ("first_row", np.int64)])
 assert CONSOLIDATION_DTYPE.itemsize == _lib.KS_CONSOLIDATION_BYTES
+# ks_gang (include/ks_engine.h)
+GANG_DTYPE = np.dtype([("first", np.int32), ("size", np.int32), ("outcome", np.int32), ("tried", np.int32),
+                       ("ok", np.int32), ("over_capacity", np.int32), ("not_found", np.int32),
+                       ("block_status", np.int32)])
+assert GANG_DTYPE.itemsize == _lib.KS_GANG_BYTES
 # ks_scale_option, ks_scale_result (include/ks_engine.h)
 SCALE_OPTION_DTYPE = np.dtype([("alloc", np.int64, (4,)), ("taint", np.uint64), ("label", np.uint64),
                                ("max_nodes", np.int32), ("pad", np.int32)])
@@ -437,6 +444,48 @@ class Engine:
             rec = rec[:n_rows.value]
             res["rows"] = dict(pod=rec["pod"].copy(), from_node=rec["from"].copy(), node=rec["node"].copy(),
                                status=rec["status"].copy(), score=rec["score"].copy(),
+                               candidates=rec["candidates"].copy())
+        return res
+
+    # -- gang admission preview (include/ks_engine.h, ks_gang_at) --------------------------------
+    def gang_at(self, t: int, shapes: dict, shape_of, first, min_ok=None, strict: bool = False, rows: bool = True,
+                after: bool = False):
+        """Which pod groups of a queue would be admitted at tick t, in the given order on one private
+        state, and where their pods would be bound: gang g is pods ``first[g] .. first[g + 1] - 1`` of
+        the k pods (``shapes`` / ``shape_of`` as for ``place_at``; ``first`` has m + 1 entries, from 0
+        to k).  Its pods go to scheduleOne one after another as ``place_at`` would handle them; the
+        attempt ends once more than ``size - min_ok[g]`` of them were not bound Ok (``min_ok`` None:
+        all-or-nothing).  A gang with at least ``min_ok`` Ok pods is admitted and its placements stay;
+        a blocked gang is rolled back; with ``strict`` every gang after the first blocked one is
+        skipped — no engine state changes.  Returns a dict of arrays over the gangs — ``first``,
+        ``size``, ``outcome`` (KS_GANG_BLOCKED / _ADMITTED / _SKIPPED), ``tried``, ``ok``,
+        ``over_capacity``, ``not_found``, ``block_status`` — plus ``info`` (rounds, admitted, blocked,
+        skipped, gangs decided through the single path, Ok pods of admitted gangs), ``rows``: with
+        ``rows=True`` ``place_at``'s arrays over the k pods (an untried pod has status
+        KS_GANG_NOT_TRIED), else None; and ``after``: with ``after=True`` the [n][4] final private
+        state, else None."""
+        ns, req, km, tol, sel = self._shapes(shapes)
+        so = _c(shape_of, np.int32).reshape(-1)
+        fi = _c(first, np.int32).reshape(-1)
+        k, m = len(so), len(fi) - 1
+        mo = None if min_ok is None else _c(min_ok, np.int32).reshape(-1)
+        if mo is not None and len(mo) != m:
+            raise ValueError(f"min_ok has {len(mo)} entries for {m} gangs")
+        out = np.zeros(max(m, 1), GANG_DTYPE)
+        rec = np.zeros(max(k, 1), PLACEMENT_DTYPE) if rows else None
+        aft = np.zeros((self.n, 4), np.int64) if after else None
+        info = np.zeros(_lib.KS_GANG_INFO, np.int64)
+        self._check(self._L.ks_gang_at(self.h, t, ns, _p(req), _p(km), _p(tol), _p(sel), k, _p(so), m, _p(fi),
+                                       None if mo is None else _p(mo), _lib.KS_GANG_STRICT if strict else 0, _p(out),
+                                       _p(rec) if rows else None, _p(aft) if after else None, _p(info)))
+        out = out[:max(m, 0)]
+        res = {f: out[f].copy() for f in GANG_DTYPE.names}
+        res["info"] = info
+        res["after"] = aft
+        res["rows"] = None
+        if rows:
+            rec = rec[:k]
+            res["rows"] = dict(node=rec["node"].copy(), status=rec["status"].copy(), score=rec["score"].copy(),
                                candidates=rec["candidates"].copy())
         return res
 
