@@ -11,8 +11,9 @@ merge the all-gather feeds (ks_engine.cpp, ks_shard).  Checked:
     window by window against the oracle's committed digests (tests/golden/full_run.json);
   * the invariants of test_engine_gpu_large.py on the full run: FIFO one bind per tick, every
     bind Ok and satisfying the taint / selector filters, usage within capacity.
-At 1M nodes the resolver's touched-node filter is the hashed one (nodes > the exact-bitmap range),
-so this is also the full-size parity test of that path.
+These runs take the chunk resolver.  The role-split resolver's hashed touched-node filter (clusters
+past its exact bitmap's 65,536 nodes) and the wide merges of the plain chain are not covered here:
+tests/test_width_gpu.py runs them against the oracle.
 """
 import os
 
